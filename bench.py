@@ -1,13 +1,15 @@
 #!/usr/bin/env python
 """bench.py -- flow samples/s (forward + log|det J|) of the BASELINE workload on N MI355X GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg5] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg5] [--batch B] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (prior sample already resident in HBM -> flow forward -> x, dlogp) over one batch of
 B synthetic samples PER RANK (weak scaling: the batch is sharded data-parallel, parameters replicated, no data-path collective
 in sampling).  With --gpus N > 1 and no torchrun environment the script launches its N ranks itself
 (``python -m torch.distributed.run --nproc-per-node N``, rendezvous on 127.0.0.1); under torchrun it is one of the ranks.
-Rank 0 prints ONE JSON line:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes its outputs if asked to and prints the
+line with the headline figure, the roofline of the timed steps and (N > 1) the devices behind the ranks; the other records below
+take runs of their own and are measured only with --full:
 
   value / ms_per_step   whole-job samples/s over the timed K steps (barrier + synchronize on both sides, max over ranks)
   roofline              the dominant kernel (the fused coupling layer, one launch per coupling block): SURVEY.md 8(d)'s algorithmic
@@ -24,6 +26,10 @@ Rank 0 prints ONE JSON line:
   rccl                  (N > 1) backend, world size, the device behind every rank, a same-run one-rank pass and the weak-scaling
                         efficiency against it, the [sum loss, n] all-reduce alone
   exact_f32_mode, cfg2, cfg5, kl   side measurements (HIP events, >= 10 steps each)
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed -- the flow's outputs x (x0, x1, ...
+for several) and dlogp -- as DIR/<name>.npy (f32).  Above DUMP_BYTES in all, every array is cut to the same fixed, seeded
+sample of rows (sorted indices).  The inputs and weights are seeded, so two builds compare output for output.
 """
 import argparse
 import json
@@ -45,6 +51,9 @@ MFMA_F32_PEAK_TFLOPS = 157.3   # dense f32-input MFMA peak (gemm_mode "f32" only
 
 # algorithmic bytes per sample of the hand-written kernels (fp32), whole step
 ALG_BYTES = {"cfg3": 26800.0, "cfg2": 4672.0, "cfg5": 24384.0}
+
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: at most this many bytes of .npy data in all
+DUMP_SEED = 0                  # seed of the row sample taken when the outputs are larger
 
 
 def default_batch(gpus, workload):
@@ -142,12 +151,43 @@ N_INPUT_SETS = 2      # the timed loops rotate this many synthetic input sets (2
 
 def timed_steps(gen, zsets, steps, inverse=False, first=0):
     """K passes of the flow with HIP events around every segment, pass k on input set (first + k) mod len(zsets).  Returns
-    [(segment index, start event, end event), ...]."""
+    ([(segment index, start event, end event), ...], the outputs of the last pass)."""
     timer = _SegmentTimer()
+    last = None
     with torch.no_grad():
         for k in range(steps):
-            gen.flow.run(tuple(zsets[(first + k) % len(zsets)]), inverse=inverse, around=timer)
-    return timer.events
+            if k == steps - 1:
+                last = gen.flow.run(tuple(zsets[(first + k) % len(zsets)]), inverse=inverse, around=timer)
+            else:
+                gen.flow.run(tuple(zsets[(first + k) % len(zsets)]), inverse=inverse, around=timer)
+    return timer.events, last
+
+
+def dump_outputs(outs, dirname):
+    """DIR/<name>.npy of one pass's outputs (x or x0, x1, ..., then dlogp), f32 / f64.  Larger than DUMP_BYTES together: the same
+    fixed, seeded sample of rows (the largest power-of-two count that fits, indices sorted) from every array."""
+    from bgflow_amd.flow import as_tensor
+    *xs, dlogp = outs
+    names = ["x"] if len(xs) == 1 else [f"x{i}" for i in range(len(xs))]
+    arrays = dict(zip(names, [as_tensor(x) for x in xs]))
+    arrays["dlogp"] = as_tensor(dlogp)
+    n = arrays["dlogp"].shape[0]
+    row_bytes = sum(t[:1].numel() * t.element_size() for t in arrays.values())
+    rows = n
+    while rows > 1 and rows * row_bytes > DUMP_BYTES:
+        rows = 1 << ((rows - 1).bit_length() - 1)       # the largest power of two below
+    idx = None
+    if rows < n:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(DUMP_SEED))[:rows].sort().values
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if idx is not None:
+            t = t[idx.to(t.device)]
+        a = t.cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32)
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def event_ms_per_call(fn, steps, warmup):
@@ -253,7 +293,7 @@ def pmc_traffic(kernel, args):
     if shutil.which("rocprofv3") is None:
         return None, "rocprofv3 not on PATH"
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--batch", str(args.batch), "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-extras", "--kl-steps", "0"] + (["--gemm", args.gemm] if args.gemm else [])
+           "--full", "--no-cpu-baseline", "--no-extras", "--kl-steps", "0"] + (["--gemm", args.gemm] if args.gemm else [])
     means = {}
     root = tempfile.mkdtemp(prefix="bgk_pmc_", dir=os.environ.get("TMPDIR", "/tmp"))
     try:
@@ -532,9 +572,15 @@ def main():
                     help="conditioner GEMM mode of the fused coupling kernel (default: bgflow_amd.dense.GEMM_MODE)")
     ap.add_argument("--batch", type=int, default=None,
                     help="samples per GPU per step (default: 2^20; with --gpus 8: 2^19 = BASELINE cfg 4, 2^22 samples sharded over 8 GPUs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (x, dlogp) as DIR/<name>.npy (f32, at most 64 MB in all: "
+                         "a fixed, seeded sample of rows when larger)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: inverse leg, exact-f32 / cfg 2 / cfg 5 / KL legs, CPU baseline, the rccl "
+                         "one-rank pass and all-reduce timings (off: the headline alone)")
     ap.add_argument("--pmc", action="store_true",
-                    help="measure roofline.traffic in this run: two extra short passes of this workload under rocprofv3 --pmc (FETCH_SIZE, "
-                         "WRITE_SIZE; separate passes, no trace domain)")
+                    help="(with --full) measure roofline.traffic in this run: two extra short passes of this workload under rocprofv3 --pmc "
+                         "(FETCH_SIZE, WRITE_SIZE; separate passes, no trace domain)")
     ap.add_argument("--cpu-samples", type=int, default=1 << 16, help="samples of the C-oracle leg of cpu_baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the exact-f32, cfg-2 and cfg-5 side measurements")
@@ -542,6 +588,10 @@ def main():
     ap.add_argument("--kl-steps", type=int, default=10, help="extra: time this many KL-loss training steps (0 = skip)")
     ap.add_argument("--kl-batch", type=int, default=1 << 18, help="samples per GPU per KL step")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.pmc and not args.full:
+        ap.error("--pmc takes runs of its own: give it together with --full")
     cfg4 = args.batch is None and default_batch(args.gpus, args.workload)[1]
     if args.batch is None:
         args.batch = default_batch(args.gpus, args.workload)[0]
@@ -594,7 +644,7 @@ def main():
         torch.distributed.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    evs = timed_steps(gen, zsets, args.steps, first=args.warmup)
+    evs, last_outputs = timed_steps(gen, zsets, args.steps, first=args.warmup)
     torch.cuda.synchronize(dev)
     if world > 1:
         torch.distributed.barrier()
@@ -607,9 +657,12 @@ def main():
         torch.distributed.all_gather(allt, tl)
         elapsed = max(float(v.item()) for v in allt)
         per_rank = [args.batch * args.steps / float(v.item()) for v in allt]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_outputs, args.dump_outputs)
+    del last_outputs
     solo = rank == 0 and world == 1
     E, W = args.extra_steps, 2
-    if world > 1:
+    if world > 1 and args.full:
         # same-run single-rank pass (the other ranks idle at the barrier): weak-scaling efficiency = (value_N / N) / value_1
         torch.distributed.barrier()
         if rank == 0:
@@ -629,7 +682,7 @@ def main():
 
     # ---- the other direction of the path: x -> (xyz -> IC, cdf maps, 16 inverse couplings) -> z, log|det J| (the NLL direction)
     inverse_leg = None
-    if args.workload != "cfg2" and rank == 0:
+    if args.full and args.workload != "cfg2" and rank == 0:
         try:
             with torch.no_grad():
                 xsets = [gen.flow(*z)[:-1] for z in zsets]
@@ -643,7 +696,7 @@ def main():
 
     # ---- extra: the same workload with the conditioner GEMMs in exact-f32 MFMA mode (bit-identical to the CPU oracle)
     exact = None
-    if args.workload == "cfg3" and gemm_mode != "f32" and solo and not args.no_extras:
+    if args.full and args.workload == "cfg3" and gemm_mode != "f32" and solo and not args.no_extras:
         try:
             _dense.GEMM_MODE = "f32"
             ms = event_ms_per_call(flow_pass(gen, zsets), E, W)
@@ -658,7 +711,7 @@ def main():
 
     # ---- extra: BASELINE.json configs[1] (8 affine coupling blocks, dim 64, batch 2^20)
     cfg2 = None
-    if args.workload == "cfg3" and solo and not args.no_extras:
+    if args.full and args.workload == "cfg3" and solo and not args.no_extras:
         try:
             gen2, sampler2, desc2 = make_workload("cfg2", dev)
             g2 = torch.Generator(device=dev).manual_seed(1234)
@@ -675,7 +728,7 @@ def main():
 
     # ---- extra: BASELINE.json configs[4] (augmented flow, fp32 vs bf16, batch 2^20)
     cfg5 = None
-    if args.workload == "cfg3" and solo and not args.no_extras:
+    if args.full and args.workload == "cfg3" and solo and not args.no_extras:
         try:
             gen5, sampler5, desc5 = make_workload("cfg5", dev)
             g5 = torch.Generator(device=dev).manual_seed(1234)
@@ -701,7 +754,7 @@ def main():
     # ---- extra (second half of BASELINE.json's metric): KL-loss training steps/s.  One step = kldiv(B).mean() -> backward through
     # the hand-written backward kernels -> ONE all-reduce of [sum, n] (+ one flat gradient bucket) -> optimizer step.
     kl = None
-    if args.kl_steps > 0 and args.workload != "cfg2":
+    if args.full and args.kl_steps > 0 and args.workload != "cfg2":
         try:
             from bgflow_amd.training import FlatAdam
             params = [p for p in gen.flow.parameters()]
@@ -798,7 +851,7 @@ def main():
 
     # ---- extra: the KL step of the configs with affine couplings (BASELINE configs[1] at 2^20, configs[4] at 2^18)
     kl_cfg2 = kl_cfg5 = None
-    if args.kl_steps > 0 and args.workload == "cfg3" and solo and not args.no_extras:
+    if args.full and args.kl_steps > 0 and args.workload == "cfg3" and solo and not args.no_extras:
         for nm, bt in (("cfg2", 1 << 20), ("cfg5", 1 << 18)):
             try:
                 leg = kl_side_leg(nm, dev, bt, max(2, args.kl_steps // 2))
@@ -878,7 +931,7 @@ def main():
         roof["block_ms"] = [round(v, 3) for v in block_ms]
         roof["block_labels"] = [lbl for lbl, _ in segs]
         out = dict(metric="flow samples/s (fwd+log|detJ|) at batch 2^20", value=value, unit="samples/s", n_gpus=world,
-                   steps=args.steps, warmup=args.warmup, ms_per_step=ms_per_step, higher_is_better=True,
+                   steps=args.steps, warmup=args.warmup, ms_per_step=ms_per_step, higher_is_better=True, full=args.full,
                    scaling="weak", vs_baseline=None,
                    dtype={"bf16": "bf16", "f32": "f32", "f16x2": "f32 (split-f16 conditioner GEMMs: hi+lo f16 operand pairs, f32 accumulate)"}[gemm_mode],
                    arithmetic={"bf16": "spline / log-det / coordinate arithmetic f32; conditioner GEMMs bf16 inputs, f32 accumulate (reduced precision)",
@@ -909,7 +962,7 @@ def main():
             out["rccl"] = rccl
         if inverse_leg is not None:
             out["inverse"] = inverse_leg
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.workload, gen, dev, args.cpu_samples, args.kl_batch)
         if exact is not None:
             out["exact_f32_mode"] = exact

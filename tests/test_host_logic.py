@@ -1075,3 +1075,24 @@ def test_bench_default_batches_name_the_baseline_configs():
     assert bench.default_batch(2, "cfg3") == (1 << 20, False) and bench.default_batch(4, "cfg3") == (1 << 20, False)
     assert bench.default_batch(8, "cfg3") == (1 << 19, True)
     assert bench.default_batch(8, "cfg2") == (1 << 20, False)
+
+
+def test_bench_dump_outputs_is_a_fixed_sample_under_the_cap(tmp_path):
+    """bench.py --dump-outputs: x and dlogp as f32 .npy, the same seeded rows of every array once the whole would pass DUMP_BYTES"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = 1 << 20
+    x = torch.arange(n, dtype=torch.float32)[:, None].repeat(1, 66)
+    dlogp = -torch.arange(n, dtype=torch.float32)[:, None]
+    for d in ("a", "b"):
+        bench.dump_outputs((x, dlogp), str(tmp_path / d))
+    a = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in ("x", "dlogp")}
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BYTES and a["x"].dtype == np.float32 and a["dlogp"].dtype == np.float32
+    assert a["x"].shape == (1 << 17, 66) and a["dlogp"].shape == (1 << 17, 1)
+    rows = a["x"][:, 0]
+    assert (np.diff(rows) > 0).all() and np.array_equal(a["dlogp"][:, 0], -rows) and (a["x"] == rows[:, None]).all()
+    assert all(np.array_equal(a[k], np.load(tmp_path / "b" / (k + ".npy"))) for k in a)
+    bench.dump_outputs((x[:1000], dlogp[:1000]), str(tmp_path / "small"))
+    assert np.array_equal(np.load(tmp_path / "small" / "x.npy"), x[:1000].numpy())

@@ -5,7 +5,7 @@ TAG=${1:-r04}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-SHORT="--no-cpu-baseline --kl-steps 0"
+SHORT="--full --no-cpu-baseline --kl-steps 0"
 # 1. kernel trace + stats of the bench command (default flags except the CPU leg / KL extra, which launch no hot-path kernels)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python bench.py $SHORT > $OUT/bench_under_rocprof.log 2>&1
 grep '"metric"' $OUT/bench_under_rocprof.log > $OUT/bench_line_under_rocprof.json
@@ -39,11 +39,11 @@ bash tools/prof_kl.sh > $OUT/kl_stats.txt 2>&1
 cp $(find gpurun_out/prof_kl/stats -name "*kernel_stats.csv" | head -1) $OUT/kl_step_kernel_stats.csv
 bash tools/pmc_kl.sh > $OUT/kl_pmc.txt 2>&1
 bash tools/pmc_ic.sh > $OUT/ic_tail_pmc.txt 2>&1
-# 4. un-profiled bench line (full default command incl. cpu_baseline + KL extra) and the multi-rank self-test of bench.py
-python bench.py > $OUT/bench_plain.json 2>$OUT/bench_plain.err
-BGK_BENCH_TEST_SHARED_GPU=1 python bench.py --gpus 2 --steps 3 --warmup 1 --batch 262144 --kl-steps 2 --kl-batch 65536 2>$OUT/bench_2rank_selftest.err | grep "\"metric\"" > $OUT/bench_2rank_selftest.json
+# 4. un-profiled bench line (--full: incl. cpu_baseline + KL extra) and the multi-rank self-test of bench.py
+python bench.py --full > $OUT/bench_plain.json 2>$OUT/bench_plain.err
+BGK_BENCH_TEST_SHARED_GPU=1 python bench.py --full --gpus 2 --steps 3 --warmup 1 --batch 262144 --kl-steps 2 --kl-batch 65536 2>$OUT/bench_2rank_selftest.err | grep "\"metric\"" > $OUT/bench_2rank_selftest.json
 # 5. roofline.traffic measured inside the bench run (bench.py --pmc: its own rocprofv3 --pmc passes), cfg 5's two coupling kernels side by side
-python bench.py --pmc --no-cpu-baseline --no-extras --kl-steps 0 > $OUT/bench_pmc_line.json 2>$OUT/bench_pmc_line.err
+python bench.py --full --pmc --no-cpu-baseline --no-extras --kl-steps 0 > $OUT/bench_pmc_line.json 2>$OUT/bench_pmc_line.err
 bash tools/pmc_cfg5.sh > $OUT/cfg5_pmc.txt 2>&1
 head -c 600 $OUT/bench_plain.json; echo
 cat $OUT/traffic.txt

@@ -8,7 +8,7 @@ BGK_BATCHED=$v timeout 200 python - <<PY
 import os, json, subprocess, sys
 from bgflow_amd import dense
 dense.BATCHED_REPACK = dense.DEFERRED_WGRAD_REDUCE = os.environ["BGK_BATCHED"] == "1"
-sys.argv = ["bench.py", "--no-cpu-baseline", "--no-extras", "--steps", "1", "--warmup", "1", "--kl-steps", "20"]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--no-extras", "--steps", "1", "--warmup", "1", "--kl-steps", "20"]
 import runpy
 runpy.run_path("bench.py", run_name="__main__")
 PY

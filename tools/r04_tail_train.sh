@@ -8,7 +8,7 @@ BGK_FUSED_TAIL=$v timeout 200 python - <<PY
 import os, sys
 from bgflow_amd.flow import SequentialFlow
 SequentialFlow.FUSE_TRAINING_TAIL = os.environ["BGK_FUSED_TAIL"] == "1"
-sys.argv = ["bench.py", "--no-cpu-baseline", "--no-extras", "--steps", "1", "--warmup", "1", "--kl-steps", "20"]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--no-extras", "--steps", "1", "--warmup", "1", "--kl-steps", "20"]
 import runpy
 runpy.run_path("bench.py", run_name="__main__")
 PY

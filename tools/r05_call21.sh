@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r05c21; mkdir -p $O
 timeout 1500 python -m pytest tests -x -q -m gpu 2>&1 | grep -E "passed|failed|^FAILED|^ERROR|^E " | cut -c1-300 | tail -8 | tee $O/suite.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee $O/smoke.txt
-timeout 900 python bench.py > $O/bench_plain.json 2>$O/bench_plain.err; tail -2 $O/bench_plain.err
+timeout 900 python bench.py --full > $O/bench_plain.json 2>$O/bench_plain.err; tail -2 $O/bench_plain.err
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r05c21/bench_plain.json").read().strip().splitlines()[-1])

@@ -9,6 +9,6 @@ BGK_LIB=$PWD/gpurun_variants/lib_dxts.so timeout 300 python tools/r05_dx_ts.py 1
 BGK_LIB=$PWD/gpurun_variants/lib_vjpfast.so timeout 900 python -m pytest tests -m gpu -q -k "rqs or spline or grad or train or kl or chain" --deselect tests/test_gpu_round4.py::test_kl_gradient_at_the_bench_batch 2>&1 | grep -E "passed|failed|^FAILED" | tail -12 | tee $O/vjpfast_tests.txt
 for v in base vjpfast base vjpfast; do
   if [ "$v" = base ]; then lib=""; else lib="$PWD/gpurun_variants/lib_$v.so"; fi
-  BGK_LIB=$lib timeout 300 python bench.py --no-cpu-baseline --no-extras --steps 2 --warmup 1 --kl-steps 20 2>/dev/null | grep '"metric"' | python -c 'import sys,json; k=json.loads(sys.stdin.read())["kl"]; print("   '$v' kl", round(k["steps_per_s"],2), round(k["ms_per_step"],3))' | tee -a $O/vjpfast.txt
+  BGK_LIB=$lib timeout 300 python bench.py --full --no-cpu-baseline --no-extras --steps 2 --warmup 1 --kl-steps 20 2>/dev/null | grep '"metric"' | python -c 'import sys,json; k=json.loads(sys.stdin.read())["kl"]; print("   '$v' kl", round(k["steps_per_s"],2), round(k["ms_per_step"],3))' | tee -a $O/vjpfast.txt
 done
 BGK_LIB=$PWD/gpurun_variants/lib_vjpfast.so bash tools/prof_kl.sh 2>&1 | grep -E "rqs_bwd|dense_bwd|wgrad_kernel|train_kernel" | tee $O/vjpfast_kernels.txt

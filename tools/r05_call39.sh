@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests -m gpu -x -q -k "recomputed or element_major"
 timeout 900 python -m pytest tests -m gpu -x -q -k "train or kl or chain or narrow or backward or trainer" 2>&1 | tail -5 | tee $O/pytest2.txt
 for v in 0 1 0 1; do
   OUT=gpurun_out/ab_rc_$v; rm -rf $OUT; mkdir -p $OUT
-  BGK_RECOMPUTE_PARAMS=$v rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o kl -- python bench.py --no-cpu-baseline --no-extras --steps 1 --warmup 1 --kl-steps 5 > $OUT/log.txt 2>&1
+  BGK_RECOMPUTE_PARAMS=$v rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o kl -- python bench.py --full --no-cpu-baseline --no-extras --steps 1 --warmup 1 --kl-steps 5 > $OUT/log.txt 2>&1
   echo "== recompute=$v $(grep '"metric"' $OUT/log.txt | python -c 'import sys,json; print(json.loads(sys.stdin.read())["kl"]["steps_per_s"])')"
   python - <<PY
 import csv,glob

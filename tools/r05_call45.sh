@@ -10,7 +10,7 @@ for v in base:0 base:1 early:1 rd6:1 base:0 base:1 early:1 rd6:1; do
   rc=${v#*:}; v=${v%:*}
   if [ "$v" = base ]; then lib=""; else lib="$PWD/gpurun_variants/lib_$v.so"; fi
   OUT=gpurun_out/ab_rc_${v}_$rc; rm -rf $OUT; mkdir -p $OUT
-  BGK_LIB=$lib BGK_RECOMPUTE_PARAMS=$rc rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o kl -- python bench.py --no-cpu-baseline --no-extras --steps 1 --warmup 1 --kl-steps 5 > $OUT/log.txt 2>&1
+  BGK_LIB=$lib BGK_RECOMPUTE_PARAMS=$rc rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o kl -- python bench.py --full --no-cpu-baseline --no-extras --steps 1 --warmup 1 --kl-steps 5 > $OUT/log.txt 2>&1
   echo "== $v recompute=$rc $(grep '"metric"' $OUT/log.txt | python -c 'import sys,json; print(json.loads(sys.stdin.read())["kl"]["steps_per_s"])')"
   python - <<PY
 import csv,glob
