@@ -46,9 +46,6 @@ struct DenseBwdArgs {
 #ifndef BGK_SBD_TS
 #define BGK_SBD_TS 0
 #endif
-#ifndef BGK_DBWD_DRAIN
-#define BGK_DBWD_DRAIN 0      /* experiment: 1 drain the queue behind the z requests, 2 behind the g_z stores, 3 both */
-#endif
 #if BGK_SBD_TS
 #define SBD_TS(k) do { __builtin_amdgcn_sched_barrier(0); if (lane == 0) reinterpret_cast<unsigned*>(s_f)[(k) * H2_SLAB + 130] = (unsigned)__builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
@@ -92,7 +89,7 @@ __device__ __forceinline__ void act_backward_tiles(h2_f32x16 (&t)[4], float c, i
 #pragma unroll
         for (int q = 0; q < 4; ++q) zall[4 * m + q] = *reinterpret_cast<const float4*>(z + row + 32 * m + 8 * q + 4 * hh);
     __builtin_amdgcn_sched_barrier(0);
-#if BGK_SBD_TS || BGK_DBWD_DRAIN
+#if BGK_SBD_TS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     SBD_TS(tsb);
 #endif
@@ -128,7 +125,7 @@ __device__ __forceinline__ void act_backward_tiles(h2_f32x16 (&t)[4], float c, i
         h2_store_rows<ZT>(hv, h_out, s_buf, b0, rows, lane);
     }
     h2_store_rows<ZT>(t, gz_out, s_buf, b0, rows, lane);
-#if BGK_SBD_TS || (BGK_DBWD_DRAIN & 2)
+#if BGK_SBD_TS
     SBD_TS(tsb + 2);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     SBD_TS(tsb + 3);

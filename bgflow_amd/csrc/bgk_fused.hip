@@ -44,18 +44,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#ifndef BGK_PIPE_SPLINE
-#define BGK_PIPE_SPLINE 0
-#endif
-#ifndef BGK_PIPE_ACT
-#define BGK_PIPE_ACT 0
-#endif
-#ifndef BGK_ABL
-#define BGK_ABL 0   /* timing ablations of the split-f16 kernel (tools/ablate_h2.sh): 1 no spline, 2 no chunk GEMMs, 4 no activation,
-                     * 8 no layer-2 LDS transpose, 16 A operands always from block 0 (L1-resident / hoisted: -3.5 % only, i.e. the
-                     * weight stream from L2 is not what limits the GEMM phases; a 3-deep ring gave nothing either) */
-#endif
-
 constexpr int FW = 4;                 /* waves per workgroup */
 constexpr int FTHREADS = FW * 64;
 constexpr int HID = 128;              /* hidden width (both hidden layers) */
@@ -205,13 +193,9 @@ template <int ACT, int S>
 struct ActGemm {
     static __device__ __forceinline__ void run(Stream& st, f32x16 (&out)[4], f32x16 (&in)[4]) {
         gstep<S>(st, out, in);
-#if BGK_PIPE_ACT
-        if constexpr (S < 48) in[1 + S / 16][S % 16] = act_fn<ACT>(in[1 + S / 16][S % 16]);
-#else
         if constexpr (S == 0) {
             act_tile<ACT>(in[1]); act_tile<ACT>(in[2]); act_tile<ACT>(in[3]);
         }
-#endif
         if constexpr (S + 1 < HSTEPS) ActGemm<ACT, S + 1>::run(st, out, in);
     }
 };
@@ -227,11 +211,7 @@ struct PlainSteps {
     }
 };
 
-/* hook policies for the pipelined spline: a live GEMM, or nothing (last chunk) */
-struct LiveGemm {
-    Stream& st; f32x16 (&out)[4]; const f32x16 (&in)[4];
-    template <int S> __device__ __forceinline__ void step() { if constexpr (S < HSTEPS) gstep<S>(st, out, in); }
-};
+/* hook policy of the spline element: nothing runs at its hook points */
 struct NoGemm {
     template <int S> __device__ __forceinline__ void step() {}
 };
@@ -251,51 +231,24 @@ template <> struct SpMath<false> {
     static __device__ __forceinline__ float rcp(float d) { return bgk_rcp_refined(d); }
     static __device__ __forceinline__ bgk_f2 softplus2(bgk_f2 x, float beta) { return bgk_softplusf2(x, beta); }
 };
-#ifndef BGK_HW_EXP
-#define BGK_HW_EXP 1
-#endif
-#ifndef BGK_HW_LOG
-#define BGK_HW_LOG 1
-#endif
-#ifndef BGK_HW_DIV
-#define BGK_HW_DIV 0      /* measured (tools/exp_hw_combos.sh, cfg 3 vs the f64 goldens): exp + log cost nothing in accuracy
-                           * (1.8e-6 vs 1.6e-6 max relative log-det error) and give the whole speed-up (13.8 -> 12.25 ms);
-                           * unrefined reciprocals on top are no faster and 3x less accurate (5.9e-6) */
-#endif
+/* exp + log on the hardware ops cost nothing in accuracy and give the whole speed-up (cfg 3: 13.8 -> 12.25 ms); unrefined
+ * reciprocals on top are no faster and 3x less accurate (5.9e-6 max relative log-det error): divisions stay refined */
 template <> struct SpMath<true> {
     static __device__ __forceinline__ bgk_f2 exp2(bgk_f2 x) {
-#if BGK_HW_EXP
         const bgk_f2 y = x * bgk_splat2(1.44269504088896341f);
         bgk_f2 r; r.x = __builtin_amdgcn_exp2f(y.x); r.y = __builtin_amdgcn_exp2f(y.y); return r;
-#else
-        return bgk_expf2(x);
-#endif
     }
     static __device__ __forceinline__ bgk_f2 log2(bgk_f2 x) {
-#if BGK_HW_LOG
         bgk_f2 r; r.x = __builtin_amdgcn_logf(x.x); r.y = __builtin_amdgcn_logf(x.y); return r * bgk_splat2(0.693147180559945309f);
-#else
-        return bgk_logf2(x);
-#endif
     }
-#if BGK_HW_DIV
-    static __device__ __forceinline__ float div(float n, float d) { return n * __builtin_amdgcn_rcpf(d); }
-    static __device__ __forceinline__ bgk_f2 divr2(bgk_f2 n, bgk_f2, bgk_f2 r) { return n * r; }
-    static __device__ __forceinline__ float rcp(float d) { return __builtin_amdgcn_rcpf(d); }
-#else
     static __device__ __forceinline__ float div(float n, float d) { return bgk_div_safe(n, d); }
     static __device__ __forceinline__ bgk_f2 divr2(bgk_f2 n, bgk_f2 d, bgk_f2 r) { return bgk_div_r2(n, d, r); }
     static __device__ __forceinline__ float rcp(float d) { return bgk_rcp_refined(d); }
-#endif
     static __device__ __forceinline__ bgk_f2 softplus2(bgk_f2 x, float beta) {
-#if BGK_HW_EXP && BGK_HW_LOG
         const bgk_f2 z = x * bgk_splat2(beta);
         bgk_f2 l = log2(bgk_splat2(1.0f) + exp2(z)) * bgk_splat2(__builtin_amdgcn_rcpf(beta));
         l.x = z.x > 20.0f ? x.x : l.x; l.y = z.y > 20.0f ? x.y : l.y;
         return l;
-#else
-        return bgk_softplusf2(x, beta);
-#endif
     }
 };
 
@@ -492,15 +445,10 @@ template <int INV, class G, int ST = 32, bool HW = false>
 __device__ __forceinline__ void spline_chunk(G& g, const FusedArgs& a, const float* s_p, float* s_y, int c, int nd,
                                              int hh, int j, int rows, float& run, int& oob_local, int (&bins)[3]) {
     spline_slot<INV, 0, G, ST, HW>(g, a, s_p, s_y, c, nd, hh, j, rows, run, oob_local, bins);
-#if BGK_PIPE_SPLINE
-    spline_slot<INV, 1, G, ST, HW>(g, a, s_p, s_y, c, nd, hh, j, rows, run, oob_local, bins);
-    spline_slot<INV, 2, G, ST, HW>(g, a, s_p, s_y, c, nd, hh, j, rows, run, oob_local, bins);
-#else
     /* slots whose two dims both lie beyond the chunk's last dim are skipped (wave-uniform branch) */
     bins[1] = bins[2] = 0;
     if (nd > 2) spline_slot<INV, 1, G, ST, HW>(g, a, s_p, s_y, c, nd, hh, j, rows, run, oob_local, bins);
     if (nd > 4) spline_slot<INV, 2, G, ST, HW>(g, a, s_p, s_y, c, nd, hh, j, rows, run, oob_local, bins);
-#endif
 }
 
 /* ---- any even bin count K (the K = 8 routines above carry hand-placed hook points for the software-pipelined exact-f32 kernel;
@@ -759,12 +707,6 @@ __global__ __launch_bounds__(FTHREADS, 2) void coupling_rqs_dense_kernel(FusedAr
             if (c + 1 < a.n_chunks) {
                 zero4(h);
                 const float4* Wn = a.W2 + (size_t)(c + 1) * HSTEPS * 64;
-#if BGK_PIPE_SPLINE
-                gstart(st, Wn, lane);
-                LiveGemm g{st, h, acc};
-                spline_chunk<INV>(g, a, s_p, s_y, c, nd, hh, j, rows, run, oob_local, bins);
-                PlainSteps<3 * HOOKS, HSTEPS>::run(st, h, acc);
-#else
                 /* the last chunk holds d - 5 (n_chunks - 1) dims = ceil(25 nd / 32) live row tiles: skip the rest */
                 /* NB: the asm loads of gstart() and the waits that retire them must sit in ONE basic block --
                  * across a branch hipcc may copy the (still in flight) destination registers */
@@ -772,7 +714,6 @@ __global__ __launch_bounds__(FTHREADS, 2) void coupling_rqs_dense_kernel(FusedAr
                 else { gstart(st, Wn, lane); PlainSteps<0, HSTEPS>::run(st, h, acc); }
                 NoGemm g;
                 spline_chunk<INV>(g, a, s_p, s_y, c, nd, hh, j, rows, run, oob_local, bins);
-#endif
             } else {
                 NoGemm g;
                 spline_chunk<INV>(g, a, s_p, s_y, c, nd, hh, j, rows, run, oob_local, bins);
@@ -858,13 +799,8 @@ template <bool BF>
 __device__ __forceinline__ void h2_load(AFrag& f, const uint4* W, int s, int lane) {
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-#if (BGK_ABL & 16)   /* timing experiment: every k-step re-reads block 0 (L1-resident): is the A stream the limiter? */
-        f.v[m][0] = W[((0 * 4 + m) * 2 + 0) * 64 + lane + (s & 0)];
-        if constexpr (!BF) f.v[m][1] = W[((0 * 4 + m) * 2 + 1) * 64 + lane + (s & 0)];
-#else
         f.v[m][0] = W[((s * 4 + m) * 2 + 0) * 64 + lane];
         if constexpr (!BF) f.v[m][1] = W[((s * 4 + m) * 2 + 1) * 64 + lane];
-#endif
     }
 }
 __device__ __forceinline__ void h2_load_bias(AFrag& f, const uint4* W, int lane) {
@@ -921,7 +857,8 @@ __device__ __forceinline__ void h2_mfma(f32x16 (&out)[4], const AFrag& a, const 
 
 /* A-operand ring of one 128-row GEMM: the first H2_RING - 1 steps are requested by h2_gemm_start (possibly long before the
  * GEMM runs -- e.g. ahead of the previous chunk's spline, which hides the L2 round trip), step s + H2_RING - 1
- * while step s computes. */
+ * while step s computes.  The weight stream from L2 does not limit the GEMM phases: A operands read from one L1-resident block
+ * were only 3.5 % faster, and a 3-deep ring gave nothing. */
 constexpr int H2_RING = 2;
 struct H2Ring { AFrag f[H2_RING]; };
 
@@ -938,12 +875,8 @@ __device__ __forceinline__ void h2_gemm_run(f32x16 (&out)[4], H2Ring& r, const B
 #pragma unroll
     for (int s = 0; s < H2_STEPS; ++s) {
         constexpr int D = H2_RING - 1;
-#if (BGK_ABL & 32)   /* timing experiment: the A stream of steps 2.. is not loaded (is the vector-memory path the limiter?) */
-        if (s == 0) h2_load<BF>(r.f[(s + D) % H2_RING], W, s + D, lane);
-#else
         if (s + D < H2_STEPS) h2_load<BF>(r.f[(s + D) % H2_RING], W, s + D, lane);
         else if (s + D == H2_STEPS) h2_load_bias(r.f[(s + D) % H2_RING], W, lane);
-#endif
         __builtin_amdgcn_sched_barrier(0);   /* keep the prefetch above this step's MFMAs */
         h2_mfma<BF>(out, r.f[s % H2_RING], b.hi[s], b.lo[s]);
     }
@@ -965,9 +898,7 @@ template <int ACT>
 __device__ __forceinline__ void act_tile_scaled(f32x16& t, float c) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) t[r] *= c;
-#if !(BGK_ABL & 4)
     act_tile_fast<ACT>(t);
-#endif
 }
 
 template <int ACT, int INV, bool SAVE, bool BF, int KT = KB>
@@ -1069,14 +1000,10 @@ __global__ __launch_bounds__(FTHREADS, 2) void coupling_rqs_dense_h2_kernel(Fuse
         zero4(h);
         h2_gemm_run<BF>(h, ring, bf, ah.A2, lane);
         for (int c = 0; c < a.n_chunks; ++c) {
-#if !(BGK_ABL & 8)
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s_p[drow(m, r, hh) * ST + j] = h[m][r] * ah.c2;
-#else
-            s_p[lane] = h[0][0] + h[1][1] + h[2][2] + h[3][3];
-#endif
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
             if constexpr (SAVE) {
@@ -1096,11 +1023,7 @@ __global__ __launch_bounds__(FTHREADS, 2) void coupling_rqs_dense_h2_kernel(Fuse
             if constexpr (KT == KB) {
                 int bins[3] = {0, 0, 0};
                 NoGemm g;
-#if !(BGK_ABL & 1)
                 spline_chunk<INV, NoGemm, ST, true>(g, a, s_p, s_y, c, nd, hh, j, rows, run, oob_local, bins);
-#else
-                run += s_p[(lane & 127) * ST + j];
-#endif
                 if (a.bin_idx) {
 #pragma unroll
                     for (int it = 0; it < 3; ++it) {
@@ -1112,12 +1035,8 @@ __global__ __launch_bounds__(FTHREADS, 2) void coupling_rqs_dense_h2_kernel(Fuse
                 spline_chunk_k<INV, KT, ST, true>(a, s_p, s_y, c, nd, hh, j, rows, b0, run, oob_local);
             }
             if (more) {
-#if !(BGK_ABL & 2)
                 zero4(h);
                 h2_gemm_run<BF>(h, ring, bf, Wn, lane);
-#else
-                h[0][0] += ring.f[0].v[0][0].x;
-#endif
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -1663,9 +1582,6 @@ int launch_h2(const char* what, const float* cond, int64_t ldc, int32_t d_c, int
     ah.c0 = c0; ah.c1 = c1; ah.c2 = c2; ah.cs_dev = cs_dev;
     ah.z0 = z0; ah.z1 = z1; ah.params = params; ah.ldp = ldp; ah.src_col = src_col;
     size_t shmem = sizeof(float) * (size_t)FW * a.lds_per_wave;
-#ifdef BGK_DBG_EXTRA_LDS
-    shmem += BGK_DBG_EXTRA_LDS;   /* occupancy experiments (tools/ablate_h2.sh): e.g. 20000 -> one workgroup per CU */
-#endif
     int64_t n_wg = ((B + 31) / 32 + FW - 1) / FW;
     BGK_CHECK_ARG(n_wg < (int64_t)0x7fffffff, "%s: batch too large for one launch", what);
     int grid = (int)n_wg;

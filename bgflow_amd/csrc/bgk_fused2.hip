@@ -59,9 +59,7 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef const __attribute__((address_space(1))) char* gptr_t;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(1))) u32x4* gptr4_t;
 
 constexpr int FW = 4;                 /* waves per workgroup */
 constexpr int FTHREADS = FW * 64;
@@ -72,30 +70,11 @@ constexpr int SROW = 33;              /* padded row stride of the y / input tile
 constexpr int ST = BGK_V2_SAVE ? 33 : 32;   /* row stride of the parameter chunk in LDS (33: the training variant also reads the chunk row-wise) */
 constexpr int KS = 8;                 /* k16-steps of a 128-wide hidden layer */
 constexpr int GBLK = KS * 8 + 4;      /* 1 KiB blocks per packed 128-row GEMM incl. the 4 bias blocks */
-#ifndef BGK_V2_ABL
-#define BGK_V2_ABL 0                /* timing ablations (wrong results): 1 no spline, 2 no activation math, 4 no LDS transposition, 8 no staging / output */
-#endif
-#ifndef BGK_V2_ASMSPLIT
-#define BGK_V2_ASMSPLIT 1            /* f16 hi / lo split of the activations: v_cvt_pk_f16_f32 + 2 x v_fma_mix (3 instructions per pair) */
-#endif
-#ifndef BGK_V2_ACT2
-#define BGK_V2_ACT2 1                /* hidden activations: the two values of a pair interleaved (0: one chain after the other) */
-#endif
 #ifndef BGK_V2_KARG
 #define BGK_V2_KARG 2                /* spline constants: 0 SGPR-resident, 1 scalar loads at their uses, 2 per direction (see rqs_fast) */
 #endif
 #ifndef BGK_V2_RD
 #define BGK_V2_RD 4
-#endif
-#ifndef BGK_V2_PINSEL
-#define BGK_V2_PINSEL 1
-#endif
-#ifndef BGK_V2_BSEARCH
-#define BGK_V2_BSEARCH 1             /* bin search: 1 = 3-level binary search with windowed selects, 0 = linear count + select chains */
-#endif
-#ifndef BGK_V2_OVFL
-#define BGK_V2_OVFL 1                 /* 1: the kernel sets MODE.FP16_OVFL -- f16 conversions saturate at +-65504 instead of producing inf (whose lo part
-                                       * would be inf - inf), so the activation code carries no clamp instructions */
 #endif
 #ifndef BGK_V2_TS
 #define BGK_V2_TS 0                   /* profiling build (tools/r04_phase_ts.py): lane 0 of every wave stores s_memtime at phase boundaries into bin_idx[tile * 32 * d + k] instead of the bin indices */
@@ -104,12 +83,6 @@ constexpr int GBLK = KS * 8 + 4;      /* 1 KiB blocks per packed 128-row GEMM in
 #define V2_TS(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0 && a.bin_idx) a.bin_idx[b0 * d + (k)] = (int)(unsigned)t_; } while (0)
 #else
 #define V2_TS(k) do { } while (0)
-#endif
-#ifndef BGK_V2_EORD
-#define BGK_V2_EORD 0                 /* event order of a GEMM: 0 = the three products of a tile-step back to back, 1 = part-major over the tiles of a k-step */
-#endif
-#ifndef BGK_V2_BUF
-#define BGK_V2_BUF 1                  /* A stream through buffer loads: one s_mov per 4 KiB group instead of a 64-bit SALU add per tile-step */
 #endif
 constexpr int RD = BGK_V2_RD;         /* A-fragment ring depth in tile-steps */
 constexpr int EH = 34;                /* hook points per spline element */
@@ -158,23 +131,6 @@ struct TFrag { u32x4 hi, lo; };             /* A operand of one (k-step, tile): 
 
 __device__ __forceinline__ int drow(int m, int r, int hh) { return 32 * m + (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
-/* block BLK (1 KiB) of a packed operand: uniform SGPR base (advanced by SALU in 4 KiB steps) + per-lane VGPR offset + immediate */
-template <int BLK>
-__device__ __forceinline__ u32x4 ld_block(const uint4* base, unsigned voff) {
-    unsigned long long gb = (unsigned long long)base + (unsigned long long)((BLK * 1024) & ~4095);
-    asm volatile("" : "+s"(gb));
-    return *(gptr4_t)((gptr_t)gb + voff + ((BLK * 1024) & 4095));
-}
-/* blocks BLK (even) and BLK + 1: the hi / lo parts of one (k-step, tile) share their 4 KiB group and its SGPR base */
-template <int BLK>
-__device__ __forceinline__ void ld_pair(u32x4& hi, u32x4& lo, const uint4* base, unsigned voff) {
-    static_assert((BLK & 1) == 0, "hi / lo pairs start at even blocks");
-    unsigned long long gb = (unsigned long long)base + (unsigned long long)((BLK * 1024) & ~4095);
-    asm volatile("" : "+s"(gb));
-    hi = *(gptr4_t)((gptr_t)gb + voff + ((BLK * 1024) & 4095));
-    lo = *(gptr4_t)((gptr_t)gb + voff + ((BLK * 1024) & 4095) + 1024);
-}
-
 /* ---- one 128-row (NT live tiles) x 128 GEMM as a stream of single-MFMA events ----------------------------------------
  * tile-step T = s * NT + m (k-step s, tile m), then NT bias tile-steps; event E = 3 T + p: p = 0 lo*hi, 1 hi*lo, 2 hi*hi
  * (small terms first), bias events one MFMA each.  The ring slot of tile-step T is refilled with T + RD right after its
@@ -188,42 +144,21 @@ struct Live {
     const uint4* W;
     unsigned voff;
     TFrag (&ring)[RDX];
-#if BGK_V2_BUF
-    __amdgpu_buffer_rsrc_t rs;
-#endif
+    __amdgpu_buffer_rsrc_t rs;        /* A stream through buffer loads: one s_mov per 4 KiB group instead of a 64-bit SALU add per tile-step */
 
     template <int BLK>
     __device__ __forceinline__ u32x4 blk() {
-#if BGK_V2_BUF
         return __builtin_amdgcn_raw_buffer_load_b128(rs, voff + ((BLK * 1024) & 4095), (BLK * 1024) & ~4095, 0);
-#else
-        return ld_block<BLK>(W, voff);
-#endif
-    }
-    /* the hi / the lo block of tile-step T alone (event order 1 refills the two halves of a ring slot at different times) */
-    template <int T>
-    __device__ __forceinline__ void load_hi() {
-        if constexpr (T < NTS) ring[T % RDX].hi = blk<((T / NT) * MS + T % NT) * 2>();
-        else if constexpr (T < NTS + NT) ring[T % RDX].hi = blk<KS * MS * 2 + (T - NTS)>();
-    }
-    template <int T>
-    __device__ __forceinline__ void load_lo() {
-        if constexpr (T < NTS) ring[T % RDX].lo = blk<((T / NT) * MS + T % NT) * 2 + 1>();
     }
     template <int T>
     __device__ __forceinline__ void load() {
-#ifdef BGK_V2_ABL_NOLOAD     /* timing experiment: only the prologue of each GEMM loads A (wrong results) */
-        if constexpr (T >= RDX) return;
-#endif
         if constexpr (T < NTS) {
             constexpr int s = T / NT, m = T % NT;
 #if BGK_V2_BF16
             ring[T % RDX].hi = blk<(s * MS + m) * 2>();         /* the bf16 values sit in the "hi" blocks of the same layout */
-#elif BGK_V2_BUF
+#else
             ring[T % RDX].hi = blk<(s * MS + m) * 2>();
             ring[T % RDX].lo = blk<(s * MS + m) * 2 + 1>();
-#else
-            ld_pair<(s * MS + m) * 2>(ring[T % RDX].hi, ring[T % RDX].lo, W, voff);
 #endif
         } else if constexpr (T < NTS + NT) {
             ring[T % RDX].hi = blk<KS * MS * 2 + (T - NTS)>();
@@ -235,9 +170,7 @@ struct Live {
     }
     __device__ __forceinline__ void start() {
         __builtin_amdgcn_sched_barrier(0);
-#if BGK_V2_BUF
         rs = __builtin_amdgcn_make_buffer_rsrc((void*)W, 0, 0x7fffffff, 0x00020000);   /* raw buffer, dword3 = gfx9 default format */
-#endif
         loads<0, RDX>();
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -259,32 +192,6 @@ struct Live {
             constexpr int m = E - NTS, T = NTS + m;
             const s16x8 one2 = {(short)0x3f80, (short)0x3f80, 0, 0, 0, 0, 0, 0};
             out[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(s16x8, ring[T % RDX].hi), one2, out[m], 0, 0, 0);
-        }
-#elif BGK_V2_EORD
-        /* event order 1: within a group of G consecutive tile-steps the products run part-major -- lo*hi of the G tiles, hi*lo of
-         * the G tiles, hi*hi of the G tiles -- so that consecutive MFMAs never write the same accumulator: a dependent MFMA that is
-         * not issued back to back with its predecessor (VALU work is threaded between the events) waits for the predecessor's
-         * write-back instead of using the matrix pipe's accumulator forwarding (MI355X_MICROARCH.md: +43 cycles).  The lo half of a
-         * ring slot is free after the first part, the hi half after the third: they are refilled separately. */
-        if constexpr (E < 3 * NTS) {
-            constexpr int G = (RDX < NT ? RDX : NT);
-            static_assert(NTS % G == 0, "groups tile the product tile-steps");
-            constexpr int grp = E / (3 * G), rem = E % (3 * G), p = rem / G, T = grp * G + rem % G, s = T / NT, m = T % NT;
-            const TFrag& f = ring[T % RDX];
-            const h16x8 a = __builtin_bit_cast(h16x8, p == 0 ? f.lo : f.hi);
-            const h16x8 bb = p == 1 ? b.lo[s] : b.hi[s];
-            if constexpr (s == 0 && p == 0) {
-                const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                out[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bb, z, 0, 0, 0);
-            } else {
-                out[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bb, out[m], 0, 0, 0);
-            }
-            if constexpr (p == 0) load_lo<T + RDX>();
-            if constexpr (p == 2) load_hi<T + RDX>();
-        } else if constexpr (E < NEV) {
-            constexpr int m = E - 3 * NTS, T = NTS + m;
-            const h16x8 one2 = {(_Float16)1.0f, (_Float16)1.0f, 0, 0, 0, 0, 0, 0};
-            out[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, ring[T % RDX].hi), one2, out[m], 0, 0, 0);
         }
 #else
         if constexpr (E < 3 * NTS) {
@@ -334,27 +241,10 @@ struct Hooks {
 };
 
 /* ---- hidden activation (hardware exp2 / rcp) of x = t * c and split into f16 hi + lo ---- */
-template <int ACT>
-__device__ __forceinline__ float act_hw(float x) {
-#if (BGK_V2_ABL & 2)
-    return x;
-#endif
-    if constexpr (ACT == 1) {           /* SiLU */
-        const float e = __builtin_amdgcn_exp2f(x * -1.44269504088896341f);
-        return x * __builtin_amdgcn_rcpf(1.0f + e);
-    } else if constexpr (ACT == 2) {    /* ReLU */
-        return x > 0.0f ? x : 0.0f;
-    } else {                            /* tanh = 1 - 2 / (1 + exp(2x)) */
-        const float e = __builtin_amdgcn_exp2f(x * 2.88539008177792681f);
-        return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + e);
-    }
-}
-
 /* tile T of a layer output (accumulator layout, 16 values per lane) -> B operands of k-steps 2T and 2T + 1; three hooks per pair */
 template <int ACT, int T, int P, class H>
 __device__ __forceinline__ void act_split_pair(H& hk, const f32x16& t, float c, BFrag& bf) {
     constexpr int r = 2 * P;
-#if BGK_V2_ACT2 && !(BGK_V2_ABL & 2)
     /* both values of the pair advance together: exp2 of both | MFMA | reciprocals + products of both | MFMA.  The two chains are
      * independent, so no consumer sits directly behind its transcendental (no hazard nop, no wait for the transcendental's latency) */
     float a0, a1;
@@ -379,17 +269,6 @@ __device__ __forceinline__ void act_split_pair(H& hk, const f32x16& t, float c, 
         }
         hk.template at<3 * P + 1>();
     }
-#else
-    float a0 = act_hw<ACT>(t[r] * c);
-    hk.template at<3 * P>();
-    float a1 = act_hw<ACT>(t[r + 1] * c);
-    hk.template at<3 * P + 1>();
-#endif
-#if !BGK_V2_OVFL
-    if constexpr (ACT != 3) {       /* SiLU / ReLU outputs are bounded below; keep the f16 conversion finite above */
-        a0 = __builtin_fminf(a0, 65000.0f); a1 = __builtin_fminf(a1, 65000.0f);
-    }
-#endif
     constexpr int s = 2 * T + (r >> 3), e = r & 7;
 #if BGK_V2_BF16
     typedef __bf16 bf2v __attribute__((ext_vector_type(2)));
@@ -398,7 +277,7 @@ __device__ __forceinline__ void act_split_pair(H& hk, const f32x16& t, float c, 
     const bf2v pb = __builtin_convertvector((f2v){a0, a1}, bf2v);           /* v_cvt_pk_bf16_f32, round to nearest even */
     const h2v ph = __builtin_bit_cast(h2v, pb);
     bf.hi[s][e] = ph[0]; bf.hi[s][e + 1] = ph[1];
-#elif BGK_V2_ASMSPLIT
+#else
     /* hi pair = v_cvt_pk_f16_f32 (RNE); lo = f16(a - hi) by the mixed-precision FMA reading hi as an f16 operand and writing one half
      * of the destination: a - hi is exact in f32, so the single rounding equals (_Float16)(a - (float)hi).  3 instructions per pair. */
     unsigned uh, ul;
@@ -409,10 +288,6 @@ __device__ __forceinline__ void act_split_pair(H& hk, const f32x16& t, float c, 
     const h2v ph = __builtin_bit_cast(h2v, uh), pl = __builtin_bit_cast(h2v, ul);
     bf.hi[s][e] = ph[0]; bf.hi[s][e + 1] = ph[1];
     bf.lo[s][e] = pl[0]; bf.lo[s][e + 1] = pl[1];
-#else
-    const _Float16 h0 = (_Float16)a0, h1 = (_Float16)a1;
-    bf.hi[s][e] = h0; bf.hi[s][e + 1] = h1;
-    bf.lo[s][e] = (_Float16)(a0 - (float)h0); bf.lo[s][e + 1] = (_Float16)(a1 - (float)h1);
 #endif
     hk.template at<3 * P + 2>();
 }
@@ -500,7 +375,6 @@ __device__ __forceinline__ float rqs_fast(H hk, float x, const float* pa, const 
     kn[5] = __builtin_fmaf(E[5], gA, SC.sa.kc[5]);
     kn[6] = __builtin_fmaf(E[6], gA, SC.sa.kc[6]);
     hk.template at<6>();
-#if BGK_V2_BSEARCH
     /* Bin search as a 3-level binary search on the (monotone) knots: idx = #{k : x >= kn[k]} exactly as the linear count (the knots are
      * non-decreasing: fma of non-decreasing prefix sums with a positive gain onto increasing offsets), with the window of candidate
      * knots / other-set prefix sums halved by selects at every level: 3 compares + 20 selects instead of 7 + 36. */
@@ -573,66 +447,6 @@ __device__ __forceinline__ float rqs_fast(H hk, float x, const float* pa, const 
     asm volatile("" : "+s"(top_b));                         /* (a load on one arm would turn the select into a branch) */
     b_ip1 = (g3 && gm && gl) ? top_b : b_ip1;
     const float B_i = b_ip1 - b_i;
-#else
-    const bool g0 = x >= kn[0], g1 = x >= kn[1], g2 = x >= kn[2], g3 = x >= kn[3], g4 = x >= kn[4], g5 = x >= kn[5], g6 = x >= kn[6];
-    hk.template at<7>();
-    int idx = (g0 ? 1 : 0) + (g1 ? 1 : 0) + (g2 ? 1 : 0) + (g3 ? 1 : 0) + (g4 ? 1 : 0) + (g5 ? 1 : 0) + (g6 ? 1 : 0);
-    *bin = idx;
-    hk.template at<8>();
-    /* the two slopes of the bin (dynamic LDS rows; circular dims wrap the last knot's slope to row 0) */
-    const int j1 = circ ? ((idx + 1) & 7) : (idx + 1);
-    const float s_lo = ps[idx * ST], s_hi = ps[j1 * ST];
-    float lo = SC.sa.low;
-    lo = g0 ? kn[0] : lo; lo = g1 ? kn[1] : lo; lo = g2 ? kn[2] : lo;
-    hk.template at<9>();
-    lo = g3 ? kn[3] : lo; lo = g4 ? kn[4] : lo; lo = g5 ? kn[5] : lo; lo = g6 ? kn[6] : lo;
-    hk.template at<10>();
-    float hi = SC.sa.high;
-    hi = g6 ? hi : kn[6]; hi = g5 ? hi : kn[5]; hi = g4 ? hi : kn[4]; hi = g3 ? hi : kn[3];
-    hk.template at<11>();
-    hi = g2 ? hi : kn[2]; hi = g1 ? hi : kn[1]; hi = g0 ? hi : kn[0];
-    const float A_i = hi - lo;
-    /* ---- other set: only knot[idx], knot[idx + 1] ---- */
-    float mB = __builtin_fmaxf(__builtin_fmaxf(vb[0], vb[1]), vb[2]);
-    hk.template at<12>();
-    mB = __builtin_fmaxf(__builtin_fmaxf(mB, vb[3]), vb[4]);
-    mB = __builtin_fmaxf(__builtin_fmaxf(mB, vb[5]), vb[6]);
-    mB = __builtin_fmaxf(mB, vb[7]);
-    const float nmB = -(mB * k.kL);
-    float F[KB];
-    F[0] = __builtin_amdgcn_exp2f(__builtin_fmaf(vb[0], k.kL, nmB));
-    hk.template at<13>();
-    F[1] = __builtin_amdgcn_exp2f(__builtin_fmaf(vb[1], k.kL, nmB));
-    F[2] = __builtin_amdgcn_exp2f(__builtin_fmaf(vb[2], k.kL, nmB));
-    F[3] = __builtin_amdgcn_exp2f(__builtin_fmaf(vb[3], k.kL, nmB));
-    hk.template at<14>();
-    F[4] = __builtin_amdgcn_exp2f(__builtin_fmaf(vb[4], k.kL, nmB));
-    F[5] = __builtin_amdgcn_exp2f(__builtin_fmaf(vb[5], k.kL, nmB));
-    F[6] = __builtin_amdgcn_exp2f(__builtin_fmaf(vb[6], k.kL, nmB));
-    hk.template at<15>();
-    F[7] = __builtin_amdgcn_exp2f(__builtin_fmaf(vb[7], k.kL, nmB));
-    F[1] += F[0]; F[2] += F[1]; F[3] += F[2];
-    hk.template at<16>();
-    F[4] += F[3]; F[5] += F[4]; F[6] += F[5]; F[7] += F[6];
-    const float rB = __builtin_amdgcn_rcpf(F[7]);
-    hk.template at<17>();
-    const float gB = SC.sb.gnum * __builtin_fmaf(__builtin_fmaf(-F[7], rB, 1.0f), rB, rB);
-    float Flo = 0.0f;
-    Flo = g0 ? F[0] : Flo; Flo = g1 ? F[1] : Flo; Flo = g2 ? F[2] : Flo;
-    hk.template at<18>();
-    Flo = g3 ? F[3] : Flo; Flo = g4 ? F[4] : Flo; Flo = g5 ? F[5] : Flo; Flo = g6 ? F[6] : Flo;
-    hk.template at<19>();
-    float Fhi = F[7];
-    Fhi = g6 ? Fhi : F[6]; Fhi = g5 ? Fhi : F[5]; Fhi = g4 ? Fhi : F[4]; Fhi = g3 ? Fhi : F[3];
-    hk.template at<20>();
-    Fhi = g2 ? Fhi : F[2]; Fhi = g1 ? Fhi : F[1]; Fhi = g0 ? Fhi : F[0];
-    const float cb = __builtin_fmaf((float)idx, SC.sb.dstep, SC.sb.low);
-    hk.template at<21>();
-    const float b_i = __builtin_fmaf(Flo, gB, cb);
-    float b_ip1 = __builtin_fmaf(Fhi, gB, cb + SC.sb.dstep);
-    b_ip1 = g6 ? SC.sb.high : b_ip1;
-    const float B_i = b_ip1 - b_i;
-#endif
     /* ---- derivatives: min_d + softplus(beta s) / beta ---- */
     const float z0 = s_lo * k.kz;                           /* log2(e) beta s_true */
     hk.template at<22>();
@@ -642,9 +456,7 @@ __device__ __forceinline__ float rqs_fast(H hk, float x, const float* pa, const 
     const float sm0 = ez0 * __builtin_fmaf(ez0, -0.5f, 1.0f) * 1.44269504088896341f;   /* log1p for tiny arguments */
     hk.template at<23>();
     float l0 = (ez0 < 2.44140625e-4f ? sm0 : lg0) * SC.kout;
-#if BGK_V2_PINSEL
     asm volatile("" : "+v"(l0));                            /* keeps the identity select below a select where SC.kout is a scalar load */
-#endif
     l0 = z0 > 28.8539008177792681f ? s_lo * k.c2 : l0;      /* beta s > 20: identity (torch softplus threshold) */
     const float d_i = SC.min_d + l0;
     const float z1 = s_hi * k.kz;
@@ -655,9 +467,7 @@ __device__ __forceinline__ float rqs_fast(H hk, float x, const float* pa, const 
     const float sm1 = ez1 * __builtin_fmaf(ez1, -0.5f, 1.0f) * 1.44269504088896341f;
     hk.template at<25>();
     float l1 = (ez1 < 2.44140625e-4f ? sm1 : lg1) * SC.kout;
-#if BGK_V2_PINSEL
     asm volatile("" : "+v"(l1));                            /* keeps the identity select below a select where SC.kout is a scalar load */
-#endif
     l1 = z1 > 28.8539008177792681f ? s_hi * k.c2 : l1;
     const float d_ip1 = SC.min_d + l1;
     float cw_i, W_i, ch_i, H_i;
@@ -746,10 +556,6 @@ __device__ __forceinline__ void spline_slot(G& g, const V2Args& a, const SpK& k,
 
 /* accumulator layout [row = feature][lane = (half, sample)] -> LDS [row][sample] (conflict-free both ways) */
 __device__ __forceinline__ void chunk_to_lds(const f32x16 (&h)[4], float* s_p, int hh, int j) {
-#if (BGK_V2_ABL & 4)
-    s_p[threadIdx.x & 63] = h[0][0] + h[1][1] + h[2][2] + h[3][3];
-    return;
-#endif
 #pragma unroll
     for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -765,9 +571,6 @@ __device__ __forceinline__ void chunk_to_lds(const f32x16 (&h)[4], float* s_p, i
  * after the chunk reached LDS and AFTER the next GEMM's first operand loads were requested: vmcnt is one in-order counter for
  * loads and stores on gfx9, so a load requested behind these 64 stores would wait for every one of them to be acknowledged. */
 __device__ __forceinline__ void save_chunk_params(const V2Args& a, const float* s_p, int c, int lane, int64_t b0, int rows) {
-#ifdef BGK_V2_ABL_NOPSAVE      /* timing experiment: the parameters are not written (wrong gradients) */
-    return;
-#endif
     if (a.params == nullptr) return;      /* the backward recomputes them from z1 (coupling_rqs_bwd_recompute_kernel below) */
     if (a.src_col == nullptr) {
         /* element-major layout [B][d][3 K + 1] (round 5): the chunk's rows ARE that order, so a sample's share of the chunk is one
@@ -808,14 +611,9 @@ __device__ __forceinline__ void chunk_piped(const V2Args& a, const SpK& k, float
     if constexpr (SAVEP) save_chunk_params(a, s_p, c, (int)threadIdx.x & 63, b0, rows);
 #endif
     __builtin_amdgcn_sched_barrier(0);
-#if (BGK_V2_ABL & 1)
-    g.template events<0, Live<NT>::NEV>();
-    run += s_p[(threadIdx.x & 127) * ST + j];
-#else
     spline_slot<INV, 0, 3 * EH>(g, a, k, s_p, s_y, c, DPC, hh, j, rows, run, oob_local, bins);
     spline_slot<INV, 1, 3 * EH>(g, a, k, s_p, s_y, c, DPC, hh, j, rows, run, oob_local, bins);
     spline_slot<INV, 2, 3 * EH>(g, a, k, s_p, s_y, c, DPC, hh, j, rows, run, oob_local, bins);
-#endif
 }
 
 /* linear DMA copy of a wave's contiguous, 16-byte aligned tile of n floats (a multiple of 4) into LDS; only the first `valid`
@@ -989,11 +787,7 @@ __device__ __forceinline__ void l0_step(f32x16 (&h)[4], const L0Frag& fr, const 
     h16x8 bhi, blo;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-#if BGK_V2_OVFL
         const float c = v[e];
-#else
-        const float c = __builtin_amdgcn_fmed3f(v[e], -65000.0f, 65000.0f);
-#endif
         const _Float16 hv = (_Float16)c;
         bhi[e] = hv;
         blo[e] = (_Float16)(c - (float)hv);
@@ -1013,9 +807,9 @@ __device__ __forceinline__ void l0_step(f32x16 (&h)[4], const L0Frag& fr, const 
 template <int ACT, int INV, bool SAVEP = true>
 __global__ __launch_bounds__(FTHREADS, 2) void coupling_rqs_dense_h2v2_kernel(V2Args a) {
     if (a.cs_dev) { a.c0 = a.cs_dev[1]; a.c1 = a.cs_dev[3]; a.c2 = a.cs_dev[5]; }   /* wave-uniform scalar loads */
-#if BGK_V2_OVFL
-    asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");                 /* MODE.FP16_OVFL */
-#endif
+    /* MODE.FP16_OVFL: f16 conversions saturate at +-65504 instead of producing inf (whose lo part would be inf - inf), so the
+     * activation code carries no clamp instructions */
+    asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int wave = threadIdx.x >> 6;
     float* s_p = smem + (size_t)wave * a.lds_per_wave;   /* parameter chunk [128][ST]; first the conditioner feature tile [32][nfs] */
@@ -1090,9 +884,7 @@ __global__ __launch_bounds__(FTHREADS, 2) void coupling_rqs_dense_h2v2_kernel(V2
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int r = 0; r < 16; ++r) h[m][r] *= a.c0;
-#ifndef BGK_V2_ABL_NOZSAVE
         h2_store_rows128(h, a.z0, s_p, b0, rows, lane);
-#endif
         const float c0_act = 1.0f;
 #else
         const float c0_act = a.c0;
@@ -1121,9 +913,7 @@ __global__ __launch_bounds__(FTHREADS, 2) void coupling_rqs_dense_h2v2_kernel(V2
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][r] *= a.c1;
-#ifndef BGK_V2_ABL_NOZSAVE
         h2_store_rows128(acc, a.z1, s_p, b0, rows, lane);
-#endif
         const float c1_act = 1.0f;
 #else
         const float c1_act = a.c1;
@@ -1152,13 +942,9 @@ __global__ __launch_bounds__(FTHREADS, 2) void coupling_rqs_dense_h2v2_kernel(V2
 #if BGK_V2_SAVE
             if constexpr (SAVEP) save_chunk_params(a, s_p, c, lane, b0, rows);
 #endif
-#if (BGK_V2_ABL & 1)
-            run += s_p[(threadIdx.x & 127) * ST + j];
-#else
             spline_slot<INV, 0, 1>(none, a, k, s_p, s_y, c, nd, hh, j, rows, run, oob_local, bins);
             if (nd > 2) spline_slot<INV, 1, 1>(none, a, k, s_p, s_y, c, nd, hh, j, rows, run, oob_local, bins);
             if (nd > 4) spline_slot<INV, 2, 1>(none, a, k, s_p, s_y, c, nd, hh, j, rows, run, oob_local, bins);
-#endif
         }
 #if BGK_V2_TS
         V2_TS(5 + c);
@@ -1421,9 +1207,7 @@ __global__ __launch_bounds__(FTHREADS, 2) void coupling_affine_dense_v2_kernel(A
 #if BGK_V2_AFF_TS
     unsigned ats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-#if BGK_V2_OVFL
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");                 /* MODE.FP16_OVFL (act_split_pair carries no clamps) */
-#endif
 #if BGK_V2_AFFTRAIN
     if (a.shift.cs) { a.shift.c0 = a.shift.cs[1]; a.shift.c1 = a.shift.cs[3]; a.shift.c2 = a.shift.cs[5]; }    /* wave-uniform scalar loads */
     if (a.scale.cs) { a.scale.c0 = a.scale.cs[1]; a.scale.c1 = a.scale.cs[3]; a.scale.c2 = a.scale.cs[5]; }
@@ -1748,9 +1532,7 @@ __device__ __forceinline__ void rc_chunk(const RcArgs& a, const RcTile& tl, floa
 template <int ACT, bool FAST>
 __global__ __launch_bounds__(FTHREADS, 2) void coupling_rqs_bwd_recompute_kernel(RcArgs a) {
     if (a.cs_dev) a.c2 = a.cs_dev[5];
-#if BGK_V2_OVFL
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");                 /* MODE.FP16_OVFL, as in the forward */
-#endif
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      /* uniform: the tile's row bases live in scalar registers */
     float* s_p = smem + (size_t)wave * a.lds_per_wave;   /* first the z1 tile [32][128] (16-byte pieces XOR-swizzled by the row), then the parameter chunks [128][ST] */
@@ -1845,7 +1627,7 @@ int bgk_h2_variant = 2;
 #endif
 
 #if BGK_V2_SAVE
-int bgk_rc_vjp_variant = 2;      /* 2 (default): the element VJP's knots on the hardware forms (BGK_VJP_FAST); 1: the deterministic forms of bgk_rqs_backward */
+int bgk_rc_vjp_variant = 2;      /* 2 (default): the element VJP's knots on the hardware forms (FAST); 1: the deterministic forms of bgk_rqs_backward */
 int bgk_launch_rqs_bwd_recompute(const char* what, const float* z1, const void* A2p, float c2, const float* cs_dev, int32_t act,
                                  const float* y, int64_t ldy, int64_t B, int32_t d, uint64_t circ_mask, int32_t inverse,
                                  double left, double right, double bottom, double top,

@@ -41,14 +41,7 @@ struct FusedAffArgs {
 /* ---- shared building blocks of both kernels (A fragments through a pointer: global memory in the streaming kernel, LDS in the
  * weight-resident one) ---- */
 typedef unsigned int r_u32x4 __attribute__((ext_vector_type(4)));
-#ifndef BGK_AFF_ABL
-#define BGK_AFF_ABL 0          /* diagnostic builds: 1 no global loads, 2 no hidden activation math, 4 no output-layer math, 8 no MFMAs */
-#endif
-#ifndef BGK_AFF_NOPRIO
 #define BGK_AFF_PRIO(p) __builtin_amdgcn_s_setprio(p)
-#else
-#define BGK_AFF_PRIO(p)
-#endif
 
 template <int NT>
 struct RA { r_u32x4 v[NT][2]; };
@@ -66,14 +59,6 @@ __device__ __forceinline__ void ra_load(RA<NT>& f, const r_u32x4* W, int s, int 
 template <int NT, bool ZERO, bool NOLO>
 __device__ __forceinline__ void ra_mfma3(h2_f32x16 (&out)[NT], const RA<NT>& a, const h2_h16x8& bhi, const h2_h16x8& blo) {
     const h2_f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#if (BGK_AFF_ABL & 8)
-#pragma unroll
-    for (int m = 0; m < NT; ++m) {
-        if (ZERO) out[m] = z;
-        out[m][0] += __builtin_bit_cast(float, a.v[m][0][0] ^ a.v[m][1][1]) + (float)bhi[0] + (float)blo[1];
-    }
-    return;
-#endif
 #pragma unroll
     for (int m = 0; m < NT; ++m)
         out[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h2_h16x8, a.v[m][1]), bhi, ZERO ? z : out[m], 0, 0, 0);
@@ -126,16 +111,12 @@ __device__ __forceinline__ void ra_gemm_hidden_pre(h2_f32x16 (&out)[NT], const R
 #pragma unroll
             for (int m = 0; m < NT; ++m) ring[(s + 1) & 1].v[m][0] = W[(S * NT * 2 + m) * 64 + lane];
         }
-#ifndef BGK_AFF_NOPIN
         /* keep the next step's LDS reads IN FRONT of this step's MFMAs: left alone, the scheduler sinks every ds_read_b128 to its use
          * (ds_read; s_waitcnt lgkmcnt(0); v_mfma -- the whole LDS latency exposed per k-step at two waves per SIMD) */
         __builtin_amdgcn_sched_barrier(0);
-#endif
         if (s == 0) ra_mfma3<NT, true, false>(out, ring[0], __builtin_bit_cast(h2_h16x8, b.hi[0]), __builtin_bit_cast(h2_h16x8, b.lo[0]));
         else ra_mfma3<NT, false, false>(out, ring[s & 1], __builtin_bit_cast(h2_h16x8, b.hi[s]), __builtin_bit_cast(h2_h16x8, b.lo[s]));
-#ifndef BGK_AFF_NOPIN
         __builtin_amdgcn_sched_barrier(0);
-#endif
     }
     const h2_h16x8 one2 = {(_Float16)1.0f, (_Float16)1.0f, 0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -148,9 +129,6 @@ __device__ __forceinline__ void ra_gemm_hidden_pre(h2_f32x16 (&out)[NT], const R
  * ACT 0 identity, 1 SiLU, 2 ReLU, 3 Tanh.  k = c (ACT 0, 2), c * log2(e) (1), 2 c log2(e) (3). */
 template <int ACT>
 __device__ __forceinline__ float r_act(float t, float c, float k) {
-#if (BGK_AFF_ABL & 2)
-    return t * c;
-#endif
     if constexpr (ACT == 2) return __builtin_amdgcn_fmed3f(t * c, 0.0f, 65000.0f);
     else if constexpr (ACT == 3) return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t * k));
     else if constexpr (ACT == 1) {
@@ -193,9 +171,6 @@ __device__ __forceinline__ void r_act_split(RB<HT>& b, const h2_f32x16 (&in)[HT]
 /* tanh for the OUTPUT layer (log sigma): hardware exp2 + Newton-refined rcp above 0.625 (abs error ~1e-7), odd polynomial below
  * (same coefficients as bgk_tanhf2) */
 __device__ __forceinline__ float r_tanh_out(float x) {
-#if (BGK_AFF_ABL & 4)
-    return x;
-#endif
     const float ax = __builtin_fabsf(x);
     const float d = 1.0f + __builtin_amdgcn_exp2f(ax * 2.88539008177792681f);
     float r = __builtin_amdgcn_rcpf(d);
@@ -409,16 +384,6 @@ struct ResOff { int a0, a1, a2; };          /* offsets (16-byte units) of a netw
 template <int HT, int OT>
 __device__ __forceinline__ void res_net_tail(h2_f32x16 (&res)[OT], h2_f32x16 (&h)[HT], const AffNet& n, const r_u32x4* s_w, ResOff o, int lane) {
     RB<HT> bf;
-#ifdef BGK_AFF_NOPRE
-    r_act_split<HT>(bf, h, n.c0, n.act);
-    BGK_AFF_PRIO(1);               /* matrix phases first: the other waves of the SIMD fill the gaps with their activation arithmetic */
-    ra_gemm_hidden<HT, HT>(h, bf, s_w + o.a1, lane);
-    BGK_AFF_PRIO(0);
-    r_act_split<HT>(bf, h, n.c1, n.act);
-    BGK_AFF_PRIO(1);
-    ra_gemm_hidden<OT, HT>(res, bf, s_w + o.a2, lane);
-    BGK_AFF_PRIO(0);
-#else
     RA<HT> f1;
     ra_load<HT>(f1, s_w + o.a1, 0, lane);          /* the GEMM's first fragments travel while the activation code runs */
     r_act_split<HT>(bf, h, n.c0, n.act);
@@ -431,7 +396,6 @@ __device__ __forceinline__ void res_net_tail(h2_f32x16 (&res)[OT], h2_f32x16 (&h
     BGK_AFF_PRIO(1);
     ra_gemm_hidden_pre<OT, HT>(res, bf, s_w + o.a2, lane, f2);
     BGK_AFF_PRIO(0);
-#endif
 }
 
 /* ---- both networks of a coupling layer as ONE software pipeline (round 5).  res_net_tail runs a network as activation -> GEMM ->
@@ -441,10 +405,7 @@ __device__ __forceinline__ void res_net_tail(h2_f32x16 (&res)[OT], h2_f32x16 (&h
  * the other network's 16 activation pairs, laid out MFMA / VALU / VALU ... by sched_group_barrier.
  *   stage A  act(hs)                       stage B  GEMM1_s  ||  act(ht)          stage C  GEMM1_t  ||  act(h1s)
  *   stage D  GEMM2_s || act(h1t)           stage E  GEMM2_t
- * BGK_AFF_PIPE2=0: the two networks one after the other (res_net_tail). */
-#ifndef BGK_AFF_PIPE2
-#define BGK_AFF_PIPE2 1
-#endif
+ * BGK_AFFINE_NO_PIPE2 (run time): the two networks one after the other (res_net_tail). */
 #ifndef BGK_AFF_PIPE2_VPM
 #define BGK_AFF_PIPE2_VPM 7            /* VALU instructions the pattern asks for behind every MFMA */
 #endif
@@ -557,12 +518,7 @@ __global__ __launch_bounds__(RW * 64, 1) void coupling_affine_resident_kernel(Fu
             } else {
                 float v[8];
                 if (!a.periodic && a.cvec4 && 16 * s + 16 <= d_c) {
-#if (BGK_AFF_ABL & 1)
-                    const float fl = (float)lane * 0.01f;
-                    const float4 t0 = make_float4(fl, fl + 1.f, fl - 1.f, fl), t1 = make_float4(-fl, fl + .5f, fl - .5f, fl);
-#else
                     const float4 t0 = *reinterpret_cast<const float4*>(crow + f0), t1 = *reinterpret_cast<const float4*>(crow + f0 + 4);
-#endif
                     v[0] = t0.x; v[1] = t0.y; v[2] = t0.z; v[3] = t0.w; v[4] = t1.x; v[5] = t1.y; v[6] = t1.z; v[7] = t1.w;
                 } else {
 #pragma unroll
@@ -657,11 +613,7 @@ __global__ __launch_bounds__(RW * 64, 1) void coupling_affine_resident_kernel(Fu
                     const bool full = a.vec4 && dim0 + 4 <= d;
                     float v[4];
                     if (full) {
-#if (BGK_AFF_ABL & 1)
-                        const float4 t4 = make_float4((float)lane, 1.f, 2.f, 3.f);
-#else
                         const float4 t4 = *reinterpret_cast<const float4*>(yr + dim0);
-#endif
                         v[0] = t4.x; v[1] = t4.y; v[2] = t4.z; v[3] = t4.w;
                     } else {
 #pragma unroll
@@ -673,11 +625,7 @@ __global__ __launch_bounds__(RW * 64, 1) void coupling_affine_resident_kernel(Fu
                         const int r = 4 * q + u;
                         const float mm = a.has_shift ? mu[m][r] * a.shift.c2 : 0.0f;
                         const float ls = sr[m][r];
-        #if (BGK_AFF_ABL & 4)
-                        const float sg = ls;
-#else
                         const float sg = __builtin_amdgcn_exp2f((a.inverse ? -ls : ls) * 1.44269504088896341f);     /* |ls| <= exp(log_alpha): 1 ulp */
-#endif
                         float t = a.inverse ? sg * (v[u] - mm) : sg * v[u] + mm;
                         if (a.is_circular) { t = t - __builtin_truncf(t); if (t < 0.0f) t = t + 1.0f; }
                         o[u] = t;
@@ -709,7 +657,7 @@ __global__ __launch_bounds__(RW * 64, 1) void coupling_affine_resident_kernel(Fu
  * writes linearly (lane l of request i -> granule 64 i + l), so the rotation is applied to the global SOURCE address of each lane;
  * it makes the per-lane-row ds_read_b128 / ds_write_b128 of the B-operand build and of the epilogue bank-conflict free (row
  * stride 128 B = half the LDS width).  Envelope: d_c = d = 32 (G = 8), two hidden layers of 64, no periodic featuriser, 16-byte
- * aligned rows; everything else runs on the kernels above.  Measured (tools/r04_cfg2_ab.sh, same box, ms per 8-layer flow at 2^20): this
+ * aligned rows; everything else runs on the kernels above.  Measured (same box, ms per 8-layer flow at 2^20; profiles/README.md): this
  * kernel 1.57, the kernel above 1.62; a three-waves-per-SIMD form of it (one tile buffer per wave, networks one after the other to
  * fit 168 VGPRs: 25 spilled registers, the next conditioner half requested behind the stores) 1.83 -- not shipped.  Per-phase wave
  * cycles (BGK_AFF_TS, tools/r04_cfg2_ts.py): of 21 k cycles per tile 0.6 k wait for the conditioner half, i.e. the memory latency is
@@ -748,11 +696,7 @@ __device__ __forceinline__ float res_half_sum(float v) {
     return l0 + l1;
 }
 
-#ifdef BGK_RES_SHFL
-#define BGK_RES_SUM(v) ((v) + __shfl_xor((v), 32))
-#else
 #define BGK_RES_SUM(v) res_half_sum(v)
-#endif
 
 template <int N> __device__ __forceinline__ void res_wait_vm() {
     if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -855,15 +799,11 @@ __global__ __launch_bounds__(RW * 64, 1) void coupling_affine_resident_dma_kerne
 #pragma unroll
             for (int s = 0; s <= KR; ++s) {
                 if (s < KR) ra_load<HT>(fr[(s + 1) & 1], W, s + 1, lane);
-#ifndef BGK_AFF_NOPIN
                 __builtin_amdgcn_sched_barrier(0);       /* (see ra_gemm_hidden_pre) */
-#endif
                 if (s == 0) ra_mfma3<HT, true, false>(h, fr[s & 1], bh[s], bl[s]);
                 else if (s == KR) ra_mfma3<HT, false, true>(h, fr[s & 1], bh[s], bl[s]);
                 else ra_mfma3<HT, false, false>(h, fr[s & 1], bh[s], bl[s]);
-#ifndef BGK_AFF_NOPIN
                 __builtin_amdgcn_sched_barrier(0);
-#endif
             }
         };
         if (a.has_shift) layer0(hs, s_w + os.a0);
@@ -1022,17 +962,14 @@ static int affine_dense_launch(const float* cond, int64_t ldc, int32_t d_c, int3
         constexpr int DRW = 8;
         const size_t dma_shmem = res_shmem + (size_t)DRW * 2 * 32 * 8 * 16;
         if (bgk_affine_variant == 2 && d_c == 32 && d == 32 && !periodic && a.cvec4 && a.vec4 && (ldc % 4 == 0) && dma_shmem <= 160 * 1024
-            && ldc < (1 << 20) && ldy < (1 << 20) && ldo < (1 << 20) && a.S0 == 3
-            && !getenv("BGK_AFFINE_NO_DMA")) {
+            && ldc < (1 << 20) && ldy < (1 << 20) && ldo < (1 << 20) && a.S0 == 3) {
             const int64_t n_tiles = (B + 31) / 32;
             int64_t grid = (n_tiles + DRW - 1) / DRW;
             if (grid > 256) grid = 256;
             const int c_s = has_shift, c_t = has_scale;
             int pact = 0;                                     /* 16 AS + AT of the pipelined instances: equal activations, or the RealNVP pair ReLU / Tanh */
-#if BGK_AFF_PIPE2
             if (has_shift && has_scale && s_act >= 1 && s_act <= 3 && (s_act == t_act || (s_act == 2 && t_act == 3)) && !getenv("BGK_AFFINE_NO_PIPE2"))
                 pact = 16 * s_act + t_act;
-#endif
 #define BGK_LAUNCH_DMA(SA, TA) do { auto K = coupling_affine_resident_dma_kernel<DRW, 8, SA, TA>; \
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
             hipLaunchKernelGGL(K, dim3((int)grid), dim3(DRW * 64), dma_shmem, st, a, os, ot, c_s * n0, c_s * n1, c_s * n2, c_t * n0, c_t * n1, c_t * n2, top); } while (0)

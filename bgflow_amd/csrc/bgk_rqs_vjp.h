@@ -39,16 +39,13 @@ __device__ __forceinline__ void bgk_softmax_knots(const float (&u)[KT], float mn
     kn[KT] = high;
 }
 
-/* BGK_VJP_FAST: the knots on the hardware forms too, in the regrouped form of the fused forward kernels (bgk_fused2.hip::rqs_fast):
+/* The knots on the hardware forms too (FAST of bgk_rqs_vjp_element_lds), in the regrouped form of the fused forward kernels (bgk_fused2.hip::rqs_fast):
  * knot_k = low + span min (k + 1) + (span scale / sum e) prefix_k(e) -- exp2, one Newton-refined reciprocal, 7 adds + 8 fma per set
  * instead of 8 polynomial exps and 8 correctly rounded quotients (~330 fewer instructions per set; the stand-alone backward kernel
  * is VALU-bound: 1.3 k instructions per element x 4.5 M elements = 170 us of the chip's VALU time at 2^18 samples x 17 dims).
  * The knots then differ from the deterministic forward's by ~1e-7: an input within that distance of a knot may be evaluated in the
  * neighbouring bin -- the spline is C1 there, so the output gradient is continuous across the knot (the training forward
  * of the fused layers uses the same hardware forms anyway). */
-#ifndef BGK_VJP_FAST
-#define BGK_VJP_FAST 0
-#endif
 template <int KT>
 __device__ __forceinline__ void bgk_softmax_knots_fast(const float (&u)[KT], float mn, float sc, float span, float low, float high,
                                                        float (&p)[KT], float (&kn)[KT + 1]) {
@@ -178,13 +175,8 @@ __device__ __forceinline__ void bgk_rqs_vjp_element(const BgkRqsCfg& c, int inve
                                                     const float (&rs)[K], float s_K, bool has_slot, float x, float gy, float gl,
                                                     float (&ow)[K], float (&oh)[K], float (&os)[K], float& g_slot, float& gx_out) {
     float pw[K], ph[K], cw[K + 1], ch[K + 1];
-#if BGK_VJP_FAST
-    bgk_softmax_knots_fast<K>(rw, c.min_w, c.w_scale, c.xspan, c.left, c.right, pw, cw);
-    bgk_softmax_knots_fast<K>(rh, c.min_h, c.h_scale, c.yspan, c.bottom, c.top, ph, ch);
-#else
     bgk_softmax_knots<K>(rw, c.min_w, c.w_scale, c.xspan, c.left, c.right, pw, cw);
     bgk_softmax_knots<K>(rh, c.min_h, c.h_scale, c.yspan, c.bottom, c.top, ph, ch);
-#endif
     const bool clamped = (x < c.left) | (x > c.right);
     x = x < c.left ? c.left : (x > c.right ? c.right : x);
     int idx = -1;
@@ -239,7 +231,7 @@ __device__ __forceinline__ void bgk_rqs_vjp_element(const BgkRqsCfg& c, int inve
 
 /* The same VJP for an element whose parameters sit in LDS: u[k * st] (k = 0 .. 3 K: widths | heights | slopes | slot row; true
  * parameter = value * c2) and whose gradients take their places.  Operation for operation the arithmetic of bgk_rqs_vjp_element
- * (identical results with FAST = BGK_VJP_FAST) -- but a parameter set is in registers only while its softmax runs, the two slopes of the bin are READ at their
+ * (identical results with FAST = false) -- but a parameter set is in registers only while its softmax runs, the two slopes of the bin are READ at their
  * (run-time) row instead of selected out of eight registers, and the gradients are written where they are formed: ~50 live
  * registers instead of ~110 (bgk_fused2.hip::coupling_rqs_bwd_recompute_kernel holds a 64-register B operand across this).
  * `wr`: the lane writes (false: an invalid slot working on a duplicate).  Returns the largest gradient magnitude. */
@@ -251,7 +243,7 @@ __device__ __forceinline__ float bgk_rqs_vjp_element_lds(const BgkRqsCfg& c, int
         float r[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) r[k] = u[k * st] * c2;
-        if constexpr (FAST) bgk_softmax_knots_fast<K>(r, c.min_w, c.w_scale, c.xspan, c.left, c.right, pw, cw);       /* (see BGK_VJP_FAST) */
+        if constexpr (FAST) bgk_softmax_knots_fast<K>(r, c.min_w, c.w_scale, c.xspan, c.left, c.right, pw, cw);       /* (see bgk_softmax_knots_fast) */
         else bgk_softmax_knots<K>(r, c.min_w, c.w_scale, c.xspan, c.left, c.right, pw, cw);
     }
     {

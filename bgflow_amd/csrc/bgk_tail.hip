@@ -28,9 +28,6 @@
 
 namespace {
 
-#ifndef BGK_TAIL_ABL
-#define BGK_TAIL_ABL 0                 /* timing ablations (wrong results): 1 one output store per lane, 2 no input loads, 4 one placement only */
-#endif
 constexpr int TW = 4;                  /* waves per workgroup (independent: they share nothing but the launch) */
 constexpr int DSC = 20;                /* floats per channel descriptor (bgflow_amd/cdf.py::tail_descriptor) */
 #ifndef BGK_TAIL_KMAX
@@ -136,41 +133,12 @@ __device__ __forceinline__ float icdf_chan(float v, const Desc& dsc, const CdfCl
     return y;
 }
 
-/* cos(2 pi x), sin(2 pi x): exact quadrant reduction + Cephes polynomials (bgk_detmath.h::bgk_sincos2pif), selects instead of
- * the quadrant branches */
-#ifndef BGK_TAIL_HWSIN
-#define BGK_TAIL_HWSIN 1       /* 1: the hardware sin / cos (argument in revolutions; max abs error 1.24e-7 on [-2, 2], tools/ubench/hw_sincos.hip):
-                                * 3 instructions instead of 26, twice per placement.  0: the reproducible polynomial form */
-#endif
+/* cos(2 pi x), sin(2 pi x) on the hardware sin / cos (argument in revolutions; max abs error 1.24e-7 on [-2, 2],
+ * tools/ubench/hw_sincos.hip): 3 instructions instead of the 26 of the reproducible polynomial form, twice per placement */
 __device__ __forceinline__ void sincos2pi(float x, float& so, float& co) {
-#if BGK_TAIL_HWSIN
     const float fr = __builtin_amdgcn_fractf(x);
     so = __builtin_amdgcn_sinf(fr);
     co = __builtin_amdgcn_cosf(fr);
-    return;
-#endif
-    const float magic = 12582912.0f;
-    const float t = __builtin_fmaf(x, 4.0f, magic);
-    const float kq = t - magic;
-    const unsigned q = __builtin_bit_cast(unsigned, t);                 /* low two bits = quadrant */
-    const float f = __builtin_fmaf(kq, -0.25f, x);
-    const float th = f * 6.28318530717958647692f;
-    const float z = th * th;
-    float sp = -1.9515295891e-4f;
-    sp = __builtin_fmaf(sp, z, 8.3321608736e-3f);
-    sp = __builtin_fmaf(sp, z, -1.6666654611e-1f);
-    sp = sp * z;
-    const float sn = __builtin_fmaf(sp, th, th);
-    float cp = 2.443315711809948e-5f;
-    cp = __builtin_fmaf(cp, z, -1.388731625493765e-3f);
-    cp = __builtin_fmaf(cp, z, 4.166664568298827e-2f);
-    cp = cp * z;
-    cp = cp * z;
-    const float cs = __builtin_fmaf(z, -0.5f, cp) + 1.0f;
-    const bool odd = q & 1u, neg_s = q & 2u, neg_c = (q + 1u) & 2u;      /* q: 0 (s, c)  1 (c, -s)  2 (-s, -c)  3 (-c, s) */
-    const float a = odd ? cs : sn, b = odd ? sn : cs;
-    so = neg_s ? -a : a;
-    co = neg_c ? -b : b;
 }
 
 __device__ __forceinline__ float rcp1(float d) {                          /* 1 / d, one Newton step: ~1 ulp */
@@ -220,11 +188,7 @@ __device__ __forceinline__ void stage_field(float* s_in, const float* __restrict
     const int total = rows * w;
     for (int k = 0; k < w; ++k) {
         const int e = k * 64 + lane;
-#if (BGK_TAIL_ABL & 2)
-        s_in[e] = 0.25f + 0.001f * (float)(e & 255);
-#else
         s_in[e] = e < total ? src[e] : 0.5f;
-#endif
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -337,7 +301,7 @@ __global__ __launch_bounds__(TW * 64) void icdf_ic2xyz_reg_kernel(TailArgs a) {
     int warn = 0;
     const float eps2 = a.eps * a.eps;
     Rec r = load_rec(recs, 0);
-    for (int i = 0; i < ((BGK_TAIL_ABL & 4) ? 1 : n); ++i) {
+    for (int i = 0; i < n; ++i) {
         const Rec rn = load_rec(recs, i + 1 < n ? i + 1 : i);
         const int at = r.at, i1 = r.i1, i2 = r.i2, i3 = r.i3;
         r = rn;
@@ -373,16 +337,9 @@ __global__ __launch_bounds__(TW * 64) void icdf_ic2xyz_reg_kernel(TailArgs a) {
         if (a.accumulate) a.dlogp[b] += acc; else a.dlogp[b] = acc;
         float* row = a.x + b * a.ldx;
         const int n_atoms = n + a.n_fixed;
-#if (BGK_TAIL_ABL & 1)
-        float sx = 0.f, sy = 0.f, sz = 0.f;
-#pragma unroll
-        for (int k = 0; k < NA; ++k) if (k < n_atoms) { sx += px[k]; sy += py[k]; sz += pz[k]; }
-        *reinterpret_cast<F3*>(row) = F3{sx, sy, sz};
-#else
 #pragma unroll
         for (int k = 0; k < NA; ++k)
             if (k < n_atoms) *reinterpret_cast<F3*>(row + 3 * k) = F3{px[k], py[k], pz[k]};
-#endif
     }
     if (warn && a.warn_count) atomicAdd(a.warn_count, warn);
 }

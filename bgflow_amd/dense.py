@@ -56,9 +56,6 @@ def column_sum(g, nblk=1024):
     return out
 
 
-LAYER_BACKWARD = os.environ.get("BGK_LAYER_BACKWARD", "1") != "0"    # backward of a Linear on the hand-written kernels (0: library GEMMs, the A/B leg)
-
-
 def linear_weight_grad(g, h, gW=None, gb=None, want_bias=True):
     """(g^T h [n, k], sum_rows g [n]) of 2-d f32 HIP tensors on bgk_linear_weight_grad (any widths); ``gW`` / ``gb``: destinations the
     result is ADDED to (the flat gradient bucket of training.FlatAdam) instead of fresh tensors"""
@@ -86,8 +83,8 @@ class _LinearFn(torch.autograd.Function):
     """A Linear layer under autograd.  On HIP tensors (``lin``: the module): forward on bgk_dense_layer; backward (round 6) on the
     hand-written kernels too -- dX = g W as one more bgk_dense_layer call on the operands of W^T (bgk_refresh_linear_layer,
     transposed), dW = g^T x and db = sum g on bgk_linear_weight_grad, added straight into the FlatAdam bucket inside
-    direct_grad_accumulation().  Rounds 1 - 5 ran F.linear + torch.bmm (hipBLASLt) + bgk_column_sum here; that form stays as the
-    A/B leg (LAYER_BACKWARD = False) and for tensors the layer kernel does not take (``lin`` None)."""
+    direct_grad_accumulation().  Rounds 1 - 5 ran F.linear + torch.bmm (hipBLASLt) + bgk_column_sum here; that form stays for
+    tensors the layer kernel does not take (``lin`` None)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, lin=None):
@@ -103,7 +100,7 @@ class _LinearFn(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         g = g.contiguous()
         need = ctx.needs_input_grad
-        if ctx.lin is not None and LAYER_BACKWARD and g.is_cuda and g.dtype == torch.float32:
+        if ctx.lin is not None and g.is_cuda and g.dtype == torch.float32:
             gx = dense_layer(g, ctx.lin, 0, transposed=True) if need[0] else None
             gw = gb = None
             if need[1] or need[2]:
@@ -295,7 +292,7 @@ def _run_layers(layers, x):
             x = _LinearFn.apply(x, m.weight, m.bias, None)
             i += 1
             continue
-        elif LAYER_KERNEL and LAYER_BACKWARD and grad and type(m) in _LAYER_ACTS and x.is_cuda and x.dtype == torch.float32 and x.requires_grad \
+        elif LAYER_KERNEL and grad and type(m) in _LAYER_ACTS and x.is_cuda and x.dtype == torch.float32 and x.requires_grad \
                 and x.dim() >= 1 and not m._forward_hooks and not m._forward_pre_hooks:
             x = _ActFn.apply(x, _LAYER_ACTS[type(m)])      # the activation and its VJP on bgk_activation / _backward (round 6; before: aten)
             i += 1
@@ -899,9 +896,6 @@ def pack_dense_for_fused_deep(linears, nc_slot_host, d, n_bins):
     return A0, A1, A2, 2.0 ** -e0, c1s, 2.0 ** -e2
 
 
-DEVICE_PACK = True     # pack split-f16 operands with bgk_pack_dense_h2 (no host sync); False: the torch reference packer
-
-
 def pack_dense_for_fused_h2_device(linears, src_col_dev, n_chunks, bufs=None, bf16=False):
     """Device-side twin of pack_dense_for_fused_h2 (bgk_pack_dense_h2): returns (A0, A1, A2, cs) with cs the
     device scale table {2^s, 2^-s} x 3.  ``bufs`` = previous result to overwrite in place."""
@@ -1091,7 +1085,7 @@ def _fused_plan(transformer, y_dim, nc_slot_host):
         if H_run == 256:       # the width-256 kernel (inference): operands from the torch packer
             cache.update(common, packed=pack_dense_for_fused_w256((l0, l1, l2), nc_slot_host, y_dim, n_bins), cs=None)
             cache.pop("bufs", None)
-        elif mode == "bf16" or (mode == "f16x2" and DEVICE_PACK and dev.type == "cuda"):
+        elif mode == "bf16" or (mode == "f16x2" and dev.type == "cuda"):
             if "src_col_dev" not in cache:
                 cache["src_col_dev"] = _src_col_table(y_dim, n_bins, nc_slot_host, dev)
             n_chunks = cache["src_col_dev"].numel() // 128
@@ -1216,12 +1210,9 @@ def _featurise(x, periodic):
     return torch.cat([torch.cos(ang), torch.sin(ang)], dim=-1)
 
 
-HALF_PAD_ROWS = int(os.environ.get("BGK_HALF_PAD_ROWS", "0"))      # rows of padding between the [B, 128] halves of one allocation
-PACKED_PARAMS = os.environ.get("BGK_PACKED_PARAMS", "1") != "0"   # the fused training forward saves the spline parameters element-major
+PACKED_PARAMS = True     # the fused training forward saves the spline parameters element-major
 # ... or not at all (round 5): bgk_coupling_rqs_dense_h2_backward recomputes them from z1 with the forward's operands (bit-identical)
-RECOMPUTE_PARAMS = os.environ.get("BGK_RECOMPUTE_PARAMS", "1") != "0"
-
-FUSED_MLP_BACKWARD = True    # input-gradient chain of the conditioner on bgk_dense_backward_dx (False: three GEMMs + torch act ops)
+RECOMPUTE_PARAMS = True
 
 
 def absmax_of(*tensors):
@@ -1254,10 +1245,8 @@ def _dense_backward_dx(g_p, z1, z0, x, W0, W1, W2, cs, act_code, periodic, want_
     g2, ldg = _lib.rowmajor(g_p)
     x2, ldc = _lib.rowmajor(x.detach())
     d_c = x2.shape[1]
-    # (the halves of ONE allocation: at B = 2^18 they would sit exactly 2^27 bytes apart -- row r of g_z1 and row r of g_z0, which a
-    # wave writes back to back, on the same memory channel and bank.  HALF_PAD_ROWS rows between them break the power-of-two stride.)
     n_out = 4 if want_h else 2
-    out = torch.empty((n_out, B + HALF_PAD_ROWS, 128), dtype=torch.float32, device=dev)[:, :B]
+    out = torch.empty((n_out, B, 128), dtype=torch.float32, device=dev)
     g_x = (gx_out if gx_out is not None else torch.empty((B, d_c), dtype=torch.float32, device=dev)) if want_gx else None
     add2, lda = _lib.rowmajor(gx_add) if (gx_add is not None and want_gx) else (None, 0)
     ws = [w.detach().contiguous() for w in (W0, W1, W2)]
@@ -1275,8 +1264,6 @@ def _dense_backward_dx(g_p, z1, z0, x, W0, W1, W2, cs, act_code, periodic, want_
         _lib.check(st, "bgk_dense_backward_dx")
     return out[0], out[1], (out[2] if want_h else None), (out[3] if want_h else None), g_x
 
-
-FUSED_WEIGHT_GRAD = True     # weight / bias gradients on bgk_dense_weight_grad (False: split-K bmm + bgk_column_sum)
 
 _DIRECT_GRADS = [False]
 
@@ -1394,8 +1381,8 @@ def _train_forward_launch(x, y, W2, plan, tcfg, inverse, oob, dlogp=None, accumu
     out = torch.empty((B, d), dtype=torch.float32, device=dev)
     if dlogp is None:
         dlogp, accumulate = torch.empty((B,), dtype=torch.float32, device=dev), False
-    zz = torch.empty((2, B + HALF_PAD_ROWS, 128), dtype=torch.float32, device=dev)      # (see _dense_backward_dx on the padding)
-    z0, z1 = zz[0, :B], zz[1, :B]
+    zz = torch.empty((2, B, 128), dtype=torch.float32, device=dev)
+    z0, z1 = zz[0], zz[1]
     left, right, bottom, top, s = tcfg
 
     def launch(layout):
@@ -1459,9 +1446,9 @@ def _train_backward_layer(lc, x, y, W0, W1, W2, z0, z1, params, nc_dev, g_out, g
     act_code, periodic, rcfg, cs = lc.act, lc.periodic, lc.rcfg, lc.cs
     act, act_bwd = _act_fwd_bwd(act_code)
     need = [need_gx, True] + list(need_w)
-    fused_wg = FUSED_WEIGHT_GRAD and y.is_cuda and W0.shape[1] <= 128
+    fused_wg = y.is_cuda and W0.shape[1] <= 128
     recompute_h = False
-    fused_dx = cs is not None and FUSED_MLP_BACKWARD and W0.shape[1] <= T_OPERAND_MAX_IN
+    fused_dx = cs is not None and W0.shape[1] <= T_OPERAND_MAX_IN
     # largest magnitudes of g_params | g_z1 | g_z0, raised by the kernels that write them: the power-of-two scales under which the
     # backward GEMMs split these gradients into f16 hi + lo operand pairs (f32-class products whatever the loss scale)
     if absmax is None:
@@ -1717,7 +1704,7 @@ def fused_spline_coupling_train(transformer, x, y, nc_dev, nc_host, inverse, oob
 # direct_grad_accumulation()).  Before round 6 an affine coupling under autograd ran its networks layer by layer and their backward
 # through _LinearFn (F.linear / bmm -> hipBLASLt) + aten activation kernels.  Reference: nn/flow/transformer/affine.py:35-70,
 # nn/dense.py:30-48, nn/flow/coupling.py:152-182, nn/training/trainers.py:156-163.
-AFFINE_TRAIN = os.environ.get("BGK_AFFINE_TRAIN", "1") != "0"     # 0: the layer-by-layer path (A/B measurements)
+AFFINE_TRAIN = True     # False: the layer-by-layer path
 
 _AFF_TRAIN_TRANSFORMERS = weakref.WeakSet()     # affine transformers whose training plan ran a forward since the last repack
 
@@ -1880,7 +1867,7 @@ def _affine_net_backward(e, plan, g_net, ldg, z1, z0, x2, ldc, absmax, want_gx, 
     ldz = plan["ldz"]
     if FUSED_BWD64 and ldz == 64 and d <= 32 and n_in <= 32 and not periodic and (all(need_w) or not any(need_w)):
         return _affine_net_backward64(e, plan, g_net, ldg, z1, z0, x2, ldc, absmax, want_gx, gx_buf, gx_add, need_w)
-    gz = torch.empty((2, B + HALF_PAD_ROWS, ldz), dtype=torch.float32, device=dev)[:, :B]
+    gz = torch.empty((2, B, ldz), dtype=torch.float32, device=dev)
     lib = _lib.lib()
     add2, lda = (gx_add, gx_add.stride(0)) if (gx_add is not None and want_gx) else (None, 0)
     with torch.cuda.device(dev):
@@ -1926,9 +1913,9 @@ def _affine_net_backward(e, plan, g_net, ldg, z1, z0, x2, ldc, absmax, want_gx, 
     return tuple(g if n else None for g, n in zip((gW0, gb0, gW1, gb1, gW2, gb2), need_w))
 
 
-FUSED_FWD64 = os.environ.get("BGK_FUSED_FWD64", "1") != "0"      # ... and their training forward on the kernel sized for them
-FUSED_BWD64 = os.environ.get("BGK_FUSED_BWD64", "1") != "0"      # networks of <= 64 hidden units: chain + weight gradients in one launch
-TAIL_FUSED64 = os.environ.get("BGK_TAIL_FUSED64", "1") != "0"    # ... with the affine tail's backward inside the scale network's launch (one call per layer)
+FUSED_FWD64 = True      # ... and their training forward on the kernel sized for them
+FUSED_BWD64 = True      # networks of <= 64 hidden units: chain + weight gradients in one launch
+TAIL_FUSED64 = True     # ... with the affine tail's backward inside the scale network's launch (one call per layer)
 # ... and nothing saved by the forward, the backward recomputing both networks: 1.3 KB per sample and layer less memory, 7 % slower than
 # the saved form at cfg 2's shapes (profiles/r06_ab_runs.txt) -- opt-in
 RECOMPUTE64 = os.environ.get("BGK_RECOMPUTE64", "0") != "0"
@@ -1991,11 +1978,11 @@ def _affine_train_forward(x, y, log_alpha, plan, cfg, dlogp=None, accumulate=Fal
         zz = ms = None                    # nothing saved: bgk_affine_coupling_backward64 recomputes the networks
         zp = [None] * 6
     elif fused_bwd:                       # ... or reads z0 / z1 of both networks and s_raw (ms of ONE array marks this form); mu is not needed
-        zz = torch.empty((4, B + HALF_PAD_ROWS, plan["ldz"]), dtype=torch.float32, device=dev)[:, :B]
+        zz = torch.empty((4, B, plan["ldz"]), dtype=torch.float32, device=dev)
         ms = torch.empty((1, B, ldms), dtype=torch.float32, device=dev)
         zp = [_lib.ptr(zz[0]), _lib.ptr(zz[1]), _lib.ptr(zz[2]), _lib.ptr(zz[3]), None, _lib.ptr(ms[0])]
     else:
-        zz = torch.empty((4, B + HALF_PAD_ROWS, plan["ldz"]), dtype=torch.float32, device=dev)[:, :B]
+        zz = torch.empty((4, B, plan["ldz"]), dtype=torch.float32, device=dev)
         ms = torch.empty((2, B, ldms), dtype=torch.float32, device=dev)
         zp = [_lib.ptr(zz[0]), _lib.ptr(zz[1]), _lib.ptr(zz[2]), _lib.ptr(zz[3]), _lib.ptr(ms[0]), _lib.ptr(ms[1])]
     ops = []

@@ -8,7 +8,6 @@ transformer.py / ic.py and run hand-written HIP kernels.
 Reference files mirrored here (names, constructor signatures, error behaviour):
   bgflow/nn/flow/base.py, sequential.py, inverted.py, coupling.py.
 """
-import os
 import warnings
 from collections.abc import Sequence
 
@@ -149,7 +148,7 @@ class SequentialFlow(Flow):
     FUSE_GENERATION_TAIL = True   # icdf domain maps + IC -> xyz as one kernel in the sampling direction (bgk_icdf_ic2xyz)
     FUSE_TRAINING_TAIL = True     # ... also when the inputs need gradients: one-launch forward that keeps the mapped fields for the backward
     FUSE_COUPLING_STACKS = True   # Split -> (affine Coupling | Swap)* -> Merge on ONE [B, D] buffer: no cat / per-layer outputs
-    FUSE_TRAINING_CHAINS = os.environ.get("BGK_TRAIN_CHAIN", "1") != "0"   # training: runs of fused spline couplings as ONE autograd node
+    FUSE_TRAINING_CHAINS = True   # training: runs of fused spline couplings as ONE autograd node
 
     _bgk_acc = True
     ACCUMULATE_IN_KERNELS = True   # one running log-det buffer, written by the kernels themselves, when no gradient is needed
@@ -157,7 +156,7 @@ class SequentialFlow(Flow):
     def forward(self, *xs, inverse=False, **kwargs):
         return self.run(xs, inverse=inverse, kwargs=kwargs)
 
-    FUSE_KL_EPILOGUE = os.environ.get("BGK_KL_EPILOGUE", "1") != "0"   # kl_sums: the target energy inside the generation tail's launch
+    FUSE_KL_EPILOGUE = True   # kl_sums: the target energy inside the generation tail's launch
 
     def kl_sums(self, xs, target, temperature=1.0, drop_nonfinite=False):
         """f64 [sum_b (u_target(x_b) - dlogp_b), samples kept] of ``x, dlogp = self(*xs)`` (BoltzmannGenerator.kldiv, bg.py:140-147, summed)
@@ -440,7 +439,7 @@ class _FusedCouplingStack:
     is not a contiguous f32 HIP matrix, or a layer's conditioners are outside the fused envelope."""
 
     _bgk_acc = True
-    FUSE_TRAINING_STACK = os.environ.get("BGK_TRAIN_STACK", "1") != "0"    # under autograd: the stack as one node (dense._AffineStackTrainFn)
+    FUSE_TRAINING_STACK = True    # under autograd: the stack as one node (dense._AffineStackTrainFn)
 
     def __init__(self, blocks):
         self._blocks = blocks

@@ -97,14 +97,14 @@ def param_state_key(p):
     return (p.data_ptr(), p._version, getattr(p, "_bgk_generation", 0))
 
 
-ROW_PITCH_FLOATS = int(__import__("os").environ.get("BGK_ROW_PITCH", "32"))
-PARAM_PITCH_FLOATS = int(__import__("os").environ.get("BGK_PARAM_PITCH", "4"))
+ROW_PITCH_FLOATS = 32
+PARAM_PITCH_FLOATS = 4
 
 
 def param_pitch(n_cols):
     """row stride of the saved spline parameters [B, P]: 16-byte aligned rows only -- the streaming spline backward reads 32-byte
     pieces of every row at once, and a 128-byte multiple pitch (1792 B) measured 4 % SLOWER there than the natural 1712 B"""
-    q = max(4, PARAM_PITCH_FLOATS)
+    q = PARAM_PITCH_FLOATS
     return (n_cols + q - 1) // q * q
 
 
@@ -113,5 +113,5 @@ def row_pitch(n_cols):
     of 32 floats = 128 bytes, so that the 32- and 64-byte pieces the backward kernels read per lane (one piece of 32 different rows
     per load instruction) never straddle a memory sector -- with the natural 1712-byte pitch of P = 425 + 3 floats
     bgk_dense_backward_dx fetched 885 MB for 717 MB of operands"""
-    q = max(4, ROW_PITCH_FLOATS)
+    q = ROW_PITCH_FLOATS
     return (n_cols + q - 1) // q * q
