@@ -1,9 +1,10 @@
 /* bgk_act.hip -- the hidden activations of a DenseNet as stand-alone elementwise kernels and their VJP (round 6): what the
  * layer-by-layer TRAINING path of a conditioner outside the one-launch envelopes runs between its bgk_dense_layer calls (nn/dense.py:30-48:
  * `activation` after every hidden Linear; autograd of it in loss.backward(), nn/training/trainers.py:156-163).  Before round 6 these
- * were torch's aten kernels (silu / tanh / threshold and their backward forms).  Same reproducible SiLU / Tanh forms as the epilogue of
- * bgk_dense_layer (bgk_detmath_pk.h), so a forward that fuses the activation into the layer kernel and one that runs it here agree
- * bit for bit.  Roofline: HBM, 8 B (forward) / 12 B (backward) per element.
+ * were torch's aten kernels (silu / tanh / threshold and their backward forms).  The reproducible SiLU / Tanh forms of bgk_detmath_pk.h;
+ * the epilogue of bgk_dense_layer uses the hardware exp2 + a refined reciprocal instead (since round 6), so a no-grad forward that fuses
+ * the activation into the layer kernel and a grad-mode one that runs it here differ by 1 - 2 ulp; both saturate as torch does
+ * (tests/test_gpu_saturation.py).  Roofline: HBM, 8 B (forward) / 12 B (backward) per element.
  */
 #include "bgk_common.h"
 #include "bgk_detmath_pk.h"

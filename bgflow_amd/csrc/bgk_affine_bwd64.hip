@@ -56,8 +56,7 @@ constexpr int FWB = 12 + 18 + 9;   /* forward operand blocks in LDS (RECOMP): A0
 __device__ __forceinline__ float q_tanh_out(float x) {
     const float ax = __builtin_fabsf(x);
     const float dn = 1.0f + __builtin_amdgcn_exp2f(ax * 2.88539008177792681f);
-    const float rc = __builtin_amdgcn_rcpf(dn);
-    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, __builtin_fmaf(__builtin_fmaf(-dn, rc, 1.0f), rc, rc), 1.0f), x);
+    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, bgk_rcp_sat(dn), 1.0f), x);
     const float z = x * x;
     float p = -5.70498872745e-3f;
     p = __builtin_fmaf(p, z, 2.06390887954e-2f);

@@ -35,15 +35,11 @@ struct Fwd64Args {
     int vec_y, vec_o;                       /* rows of y / out start on 16-byte boundaries (float4 accesses) */
 };
 
-__device__ __forceinline__ float f64_rcp_nr(float d) {
-    const float r = __builtin_amdgcn_rcpf(d);
-    return __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
-}
 /* tanh of the OUTPUT layer (log sigma): the form of the other fused affine kernels (bgk_fused2.hip::aff_tanh_out) */
 __device__ __forceinline__ float f64_tanh_out(float x) {
     const float ax = __builtin_fabsf(x);
     const float dn = 1.0f + __builtin_amdgcn_exp2f(ax * 2.88539008177792681f);
-    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, f64_rcp_nr(dn), 1.0f), x);
+    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, bgk_rcp_sat(dn), 1.0f), x);
     const float z = x * x;
     float p = -5.70498872745e-3f;
     p = __builtin_fmaf(p, z, 2.06390887954e-2f);

@@ -47,19 +47,15 @@ struct LayerArgs {
     int bias_lds;                                /* the bias vector (zero-padded to 128 G floats) sits in LDS behind the waves' tiles */
 };
 
-/* SiLU / tanh of the epilogue: hardware exp2 + a Newton-refined reciprocal (1 - 2 ulp; the reproducible polynomial forms of
- * bgk_detmath_pk.h cost 3 x the instructions and the epilogue was 40 % of the kernel: tools/r06_layer_ts.py).  tanh keeps the odd
- * polynomial below 0.625, where 1 - 2 / (e + 1) cancels. */
-__device__ __forceinline__ float layer_rcp(float d) {
-    const float r = __builtin_amdgcn_rcpf(d);
-    return __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
-}
+/* SiLU / tanh of the epilogue: hardware exp2 + a Newton-refined reciprocal that saturates (bgk_rcp_sat; 1 - 2 ulp; the reproducible
+ * polynomial forms of bgk_detmath_pk.h cost 3 x the instructions and the epilogue was 40 % of the kernel: tools/r06_layer_ts.py).  tanh
+ * keeps the odd polynomial below 0.625, where 1 - 2 / (e + 1) cancels. */
 __device__ __forceinline__ float layer_silu(float x) {
-    return x * layer_rcp(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896341f));
+    return x * bgk_rcp_sat(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896341f));
 }
 __device__ __forceinline__ float layer_tanh(float x) {
     const float ax = __builtin_fabsf(x);
-    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, layer_rcp(1.0f + __builtin_amdgcn_exp2f(ax * 2.88539008177792681f)), 1.0f), x);
+    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, bgk_rcp_sat(1.0f + __builtin_amdgcn_exp2f(ax * 2.88539008177792681f)), 1.0f), x);
     const float z = x * x;
     float p = -5.70498872745e-3f;
     p = __builtin_fmaf(p, z, 2.06390887954e-2f);

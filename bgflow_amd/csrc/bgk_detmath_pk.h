@@ -158,4 +158,13 @@ __device__ __forceinline__ bgk_f2 bgk_tanhf2_fast(bgk_f2 x) {
     return bgk_fma2(r, bgk_splat2(-2.0f), bgk_splat2(1.0f));
 }
 
+/* 1 / d for d = 1 + exp2(..) >= 1, the reciprocal of the saturating activation forms on the hardware exp2 (SiLU, tanh): v_rcp_f32 + one
+ * Newton step.  When exp2 overflows, d = +inf, r = 0 and the correction fma(-d, r, 1) is -inf * 0 = NaN; fminf drops it (minNum), so the
+ * result is 0 and SiLU -> -0, tanh -> +-1 as in torch.  For finite d the correction is below 2^-22 and fminf returns it unchanged: the
+ * same bits as the plain step.  (tests/test_gpu_saturation.py) */
+__device__ __forceinline__ float bgk_rcp_sat(float d) {
+    const float r = __builtin_amdgcn_rcpf(d);
+    return __builtin_fmaf(__builtin_fminf(__builtin_fmaf(-d, r, 1.0f), 1.0f), r, r);
+}
+
 #endif /* BGK_DETMATH_PK_H */

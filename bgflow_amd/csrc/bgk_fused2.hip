@@ -1177,12 +1177,12 @@ __device__ __forceinline__ void aff_layers(const AffV2Net& n, f32x16 (&X)[4], f3
 }
 #endif
 
-/* tanh for the OUTPUT layer (log sigma): hardware exp2 + Newton-refined rcp above 0.625 (abs error ~1e-7), odd polynomial below
- * (the form of the other fused affine kernels, bgk_fused_affine.hip::r_tanh_out) */
+/* tanh for the OUTPUT layer (log sigma): hardware exp2 + Newton-refined rcp above 0.625 (abs error ~1e-7; +-1 where exp2 overflows),
+ * odd polynomial below (the form of the other fused affine kernels, bgk_fused_affine.hip::r_tanh_out) */
 __device__ __forceinline__ float aff_tanh_out(float x) {
     const float ax = __builtin_fabsf(x);
     const float dn = 1.0f + __builtin_amdgcn_exp2f(ax * 2.88539008177792681f);
-    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, rcp_nr(dn), 1.0f), x);
+    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, bgk_rcp_sat(dn), 1.0f), x);
     const float z = x * x;
     float p = -5.70498872745e-3f;
     p = __builtin_fmaf(p, z, 2.06390887954e-2f);

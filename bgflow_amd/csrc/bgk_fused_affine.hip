@@ -168,14 +168,12 @@ __device__ __forceinline__ void r_act_split(RB<HT>& b, const h2_f32x16 (&in)[HT]
     else r_act_split_t<0, HT>(b, in, c);
 }
 
-/* tanh for the OUTPUT layer (log sigma): hardware exp2 + Newton-refined rcp above 0.625 (abs error ~1e-7), odd polynomial below
- * (same coefficients as bgk_tanhf2) */
+/* tanh for the OUTPUT layer (log sigma): hardware exp2 + Newton-refined rcp above 0.625 (abs error ~1e-7; +-1 where exp2 overflows),
+ * odd polynomial below (same coefficients as bgk_tanhf2) */
 __device__ __forceinline__ float r_tanh_out(float x) {
     const float ax = __builtin_fabsf(x);
     const float d = 1.0f + __builtin_amdgcn_exp2f(ax * 2.88539008177792681f);
-    float r = __builtin_amdgcn_rcpf(d);
-    r = __builtin_fmaf(r, __builtin_fmaf(-d, r, 1.0f), r);
-    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, r, 1.0f), x);
+    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, bgk_rcp_sat(d), 1.0f), x);
     const float z = x * x;
     float p = -5.70498872745e-3f;
     p = __builtin_fmaf(p, z, 2.06390887954e-2f);
