@@ -20,6 +20,8 @@ _MAP = {
     "nn.flow.coupling": "flow",
     "nn.flow.inverted": "flow",
     "nn.flow.cdf": "cdf",
+    "nn.flow.modulo": "modulo",
+    "nn.flow.torchtransform": "modulo",
     "nn.flow.stochastic": "flow",
     "nn.flow.stochastic.augment": "flow",
     "nn.flow.transformer": "transformer",

@@ -259,6 +259,7 @@ def philox_sample(fields, n_samples, device, seed, offset, row0=0, want_energy=F
 _PHILOX_STREAMS = [0]          # next automatically assigned stream id (construction-order fallback, see _FusedSampling)
 _PHILOX_LIVE = {}              # stream id -> weak reference of the live object that draws from it
 PHILOX_MAX_WIDTH = 160         # widest field bgk_philox_fields assembles in its LDS tile (4 waves x 64 rows x d floats)
+COLMAP_MAX_WIDTH = 256         # widest field bgk_colmap stages (a [64][n_in] and a [64][n_out] tile per wave in LDS; BGK_COLMAP_MAX_WIDTH)
 
 
 def _philox_claim(obj, stream):

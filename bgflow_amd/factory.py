@@ -6,8 +6,8 @@ hot path accelerates, with the reference builder's block order, tensor slots and
 transformer_factory.py:15-43, distribution_factory.py:10-57, icmarginals.py:14-77), so a script written against
 ``bgflow.BoltzmannGeneratorBuilder`` runs unchanged and checkpoints line up.  Covered: dense conditioners, spline and affine
 transformers, split / merge / set-constant / arbitrary layers, the default IC marginals, Relative / Mixed / Global coordinate
-transforms.  Not covered (out of the hot path's scope, raise NotImplementedError): GNN conditioners, constraint merging,
-chirality / torsion-multiplicity helpers.
+transforms, constraint merging, chirality / torsion-multiplicity / torsion-shift helpers.  Not covered (out of the hot path's
+scope, raise NotImplementedError): GNN conditioners.
 """
 import warnings
 from collections import OrderedDict, namedtuple
@@ -22,6 +22,7 @@ from .distributions import (NormalDistribution, ProductDistribution, SloppyUnifo
                             UniformDistribution)
 from .flow import CouplingFlow, Flow, InverseFlow, MergeFlow, SequentialFlow, SetConstantFlow, SplitFlow, WrapFlow
 from .ic import GlobalInternalCoordinateTransformation
+from .modulo import CircularShiftFlow, IncreaseMultiplicityFlow, TorchTransform
 from .transformer import AffineTransformer, ConditionalSplineTransformer
 
 __all__ = ["TensorInfo", "ShapeDictionary", "BONDS", "ANGLES", "TORSIONS", "FIXED", "ORIGIN", "ROTATION", "AUGMENTED", "TARGET",
@@ -460,17 +461,48 @@ class BoltzmannGeneratorBuilder:
         if return_layers:
             return added
 
-    def add_merge_constraints(self, *args, **kwargs):
-        raise NotImplementedError("constraint merging (generator_builder.py:461-498) is outside the accelerated hot path")
+    def add_merge_constraints(self, constrained_indices=None, constrained_values=None, field=BONDS):
+        """Augment ``field`` by constant elements (generator_builder.py:461-498): ``constrained_values`` are inserted at
+        ``constrained_indices`` of the resulting tensor.  Appends SetConstantFlow + an index MergeFlow, which a SequentialFlow
+        runs as one column-map launch."""
+        # The reference requires both arguments.  They default to None here only so that the bare call, which used to raise
+        # NotImplementedError while the method was a stub, keeps doing so instead of turning into a TypeError; every call the
+        # reference accepts behaves as in the reference.
+        if constrained_indices is None or constrained_values is None:
+            raise NotImplementedError("add_merge_constraints: constrained_indices and constrained_values are both required")
+        assert field in self.current_dims
+        assert len(constrained_indices) == len(constrained_values)
+        if len(constrained_indices) == 0:
+            warnings.warn("add_merge_constraints was skipped, because no bond indices were specified.", UserWarning)
+            return
+        n_bonds = len(constrained_indices) + self.current_dims[field][-1]
+        constrained_indices = np.array(constrained_indices)
+        unconstrained_indices = np.setdiff1d(np.arange(n_bonds), constrained_indices)
+        if not isinstance(constrained_values, torch.Tensor):
+            constrained_values = torch.tensor(constrained_values, **self.ctx)
+        field_constrained = TensorInfo(f"{field.name}_constrained", field.is_circular)
+        self.add_set_constant(field_constrained, constrained_values)
+        self.add_merge((field, field_constrained), to=field, sizes_or_indices=(unconstrained_indices, constrained_indices))
 
-    def add_constrain_chirality(self, *args, **kwargs):
-        raise NotImplementedError("chirality constraints (generator_builder.py:500-516) are outside the accelerated hot path")
+    def add_constrain_chirality(self, halpha_torsion_indices, right_handed=False, torsions=TORSIONS):
+        """Constrain the chirality of aminoacids by constraining their normalized halpha torsions to [0.5, 1] instead of [0, 1]
+        (generator_builder.py:500-516).  ``halpha_torsion_indices``: an index or boolean array for the torsions."""
+        loc = torch.zeros(*self.current_dims[torsions], **self.ctx)
+        scale = torch.ones(*self.current_dims[torsions], **self.ctx)
+        loc[halpha_torsion_indices] = 0.5 * (1 - right_handed)
+        scale[halpha_torsion_indices] = 0.5
+        affine = TorchTransform(torch.distributions.AffineTransform(loc=loc, scale=scale), 1)
+        return self.add_layer(affine, what=(torsions,))
 
-    def add_torsion_multiplicities(self, *args, **kwargs):
-        raise NotImplementedError("torsion multiplicities (generator_builder.py:518-521) are outside the accelerated hot path")
+    def add_torsion_multiplicities(self, multiplicities, torsions=TORSIONS):
+        """IncreaseMultiplicityFlow on the torsions (generator_builder.py:518-521)"""
+        fmod_layer = IncreaseMultiplicityFlow(multiplicities).to(**self.ctx)
+        return self.add_layer(fmod_layer, what=(torsions,))
 
-    def add_torsion_shifts(self, *args, **kwargs):
-        raise NotImplementedError("torsion shifts (generator_builder.py:523-526) are outside the accelerated hot path")
+    def add_torsion_shifts(self, shifts, torsions=TORSIONS):
+        """CircularShiftFlow on the torsions (generator_builder.py:523-526)"""
+        fmod_layer = CircularShiftFlow(shifts).to(**self.ctx)
+        return self.add_layer(fmod_layer, what=(torsions,))
 
     def _add_to_param_groups(self, parameters, param_groups):
         parameters = list(parameters)

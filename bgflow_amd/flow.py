@@ -149,6 +149,7 @@ class SequentialFlow(Flow):
     FUSE_TRAINING_TAIL = True     # ... also when the inputs need gradients: one-launch forward that keeps the mapped fields for the backward
     FUSE_COUPLING_STACKS = True   # Split -> (affine Coupling | Swap)* -> Merge on ONE [B, D] buffer: no cat / per-layer outputs
     FUSE_TRAINING_CHAINS = True   # training: runs of fused spline couplings as ONE autograd node
+    FUSE_CONSTANT_MERGE = True    # SetConstantFlow -> WrapFlow(index MergeFlow) of add_merge_constraints as ONE column-map launch (bgk_colmap)
 
     _bgk_acc = True
     ACCUMULATE_IN_KERNELS = True   # one running log-det buffer, written by the kernels themselves, when no gradient is needed
@@ -245,7 +246,7 @@ class SequentialFlow(Flow):
         blocks = list(self._blocks)
         # the segment lists (and what the fused segments cache: descriptor tables) are rebuilt only when the blocks or the switches change
         train = bool(train) and self.FUSE_TRAINING_CHAINS
-        key = (self.FUSE_GENERATION_TAIL, self.FUSE_COUPLING_STACKS, tuple(id(b) for b in blocks))
+        key = (self.FUSE_GENERATION_TAIL, self.FUSE_COUPLING_STACKS, self.FUSE_CONSTANT_MERGE, tuple(id(b) for b in blocks))
         cache = self.__dict__.setdefault("_segment_cache", {})
         if cache.get("key") != key:
             cache.clear()
@@ -271,8 +272,15 @@ class SequentialFlow(Flow):
     def _with_coupling_stacks(self, blocks, inverse):
         """[(label, callable)] for ``blocks`` (already in execution order) with every run
         ``split -> (CouplingFlow(AffineTransformer) | SwapFlow)* -> merge`` replaced by one _FusedCouplingStack"""
+        from .modulo import FusedConstantMerge, constant_merge_pair
         out, i = [], 0
         while i < len(blocks):
+            # SetConstantFlow -> WrapFlow(index MergeFlow) over the inserted slot (add_merge_constraints): one column-map launch
+            pair = constant_merge_pair(blocks[i], blocks[i + 1], inverse) if self.FUSE_CONSTANT_MERGE and i + 1 < len(blocks) else None
+            if pair is not None:
+                out.append(("constant merge", FusedConstantMerge(*pair)))
+                i += 2
+                continue
             j = _coupling_stack_end(blocks, i, inverse) if self.FUSE_COUPLING_STACKS else None
             if j is None:
                 out.append((type(blocks[i]).__name__, blocks[i]))

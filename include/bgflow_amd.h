@@ -648,6 +648,27 @@ int bgk_philox_fields(uint64_t seed, uint32_t offset, int64_t row0, int32_t n_fi
                       const int32_t* d, const int32_t* kind, const float* const* p0, const float* const* p1,
                       const float* scale, const float* e_const, double c_out, int64_t B, float* energy, void* stream);
 
+/* Column map of one [B, n_in] f32 field with contiguous rows into a [B, n_out] one, in one launch: output column j is a function of
+ * at most one input column, given by table[j] = (int32 kind, int32 src, float p0, float p1) (device memory, 16 bytes per entry):
+ *   0 COPY        in[src]                           index SplitFlow / MergeFlow (nn/flow/coupling.py:13-110)
+ *   1 CONST       p0                                SetConstantFlow values merged into a field (coupling.py:227-272 + the index
+ *                                                   merge, as appended by generator_builder.py:461-498)
+ *   2 AFFINE_FWD  p0 + p1 * in[src]                 AffineTransform under TorchTransform (torchtransform.py:25-28); also the backward
+ *   3 AFFINE_INV  (in[src] - p0) / p1               its inverse (torchtransform.py:30-33)
+ *   4 SHIFT       remainder(in[src] + p0, 1)        CircularShiftFlow (modulo.py:63-76; p0 = -shift for the inverse)
+ *   5 MULT_INV    remainder(in[src], p1) * p0       IncreaseMultiplicityFlow._inverse (modulo.py:31-35; p0 = m, p1 = 1 / m in f32)
+ *   6 MULT_FWD    (in[src] + floor(u * p0)) / p0    IncreaseMultiplicityFlow._forward (modulo.py:24-29; p0 = m); u = u_in[b, src] if
+ *                                                   u_in != NULL ([B, n_in]), else the Philox4x32-10 uniform of (seed, offset, global
+ *                                                   row row0 + b, column src) in the counter layout of bgk_philox_fields, field 0
+ *   remainder = torch's: fmod, then + divisor if the result is non-zero and negative.  Kinds 4-6 count inputs outside
+ *   [-1e-6, 1 + 1e-6] into bad_count[0] (if not NULL) with an atomic add (modulo.py:42-44 raises there).
+ * dlogp [B] (may be NULL): the constant log|det J| `logdet` of the map; accumulate = 0 writes it, accumulate != 0 adds it (a zero
+ * constant then leaves the buffer untouched).  n_in, n_out <= BGK_COLMAP_MAX_WIDTH (two 64-row tiles in LDS). */
+#define BGK_COLMAP_MAX_WIDTH 256
+int bgk_colmap(const float* in, int32_t n_in, float* out, int32_t n_out, const void* table, const float* u_in,
+               uint64_t seed, uint32_t offset, int64_t row0, int64_t B,
+               float* dlogp, int32_t accumulate, double logdet, int32_t* bad_count, void* stream);
+
 /* Weight and bias gradients of the conditioner MLP [n_in, 128, 128, P] of one coupling layer (autograd of nn/dense.py:47-48 in
  * the training step: dW = g^T h, db = sum over the batch of g) from the tensors bgk_rqs_backward / bgk_dense_backward_dx wrote:
  *   (g_params [B, P], h1) -> gW2 [P, 128], gb2 [P];  (g_z1, h0) -> gW1 [128, 128], gb1 [128];
