@@ -1490,11 +1490,14 @@ int launch_h2(const char* what, const float* cond, int64_t ldc, int32_t d_c, int
               float* z0, float* z1, float* params, int64_t ldp, const int32_t* src_col, void* stream, const BgkCondSegs* segs = nullptr,
               int params_layout = 0) {
     if (segs && segs->n >= 1) { cond = segs->ptr[0]; ldc = segs->ld[0]; }
+    /* operand_dtype 2: split-f16 operands whose output layer is in row order 2 (bgk_pack_rqs_columns_v) -- the second-generation inference kernel only */
+    const int row_order = operand_dtype == 2 ? 2 : 1;
+    if (operand_dtype == 2) operand_dtype = 0;
     BGK_CHECK_ARG(cond && A0p && A1p && A2p && y && out && dlogp, "%s: null pointer", what);
     BGK_CHECK_ARG(B >= 0 && d > 0 && d_c > 0, "%s: bad sizes", what);
     const bool other_k = (K == 4 || K == 12 || K == 16 || K == 32) && operand_dtype == 0;     /* K != 8: split-f16 only (inference and training forward) */
     const bool wide = H0 == 32 * W_T && H1 == 32 * W_T;      /* hidden width 256 (129 .. 255 zero-padded by the packer): split-f16 inference */
-    if (wide && (operand_dtype != 0 || z0 || z1 || params || (segs && segs->n > 1))) {
+    if (wide && (operand_dtype != 0 || row_order != 1 || z0 || z1 || params || (segs && segs->n > 1))) {
         bgk_set_error("%s: hidden width 256 runs fused in split-f16 inference from one conditioning tensor only", what);
         return BGK_EUNSUPPORTED;
     }
@@ -1546,6 +1549,10 @@ int launch_h2(const char* what, const float* cond, int64_t ldc, int32_t d_c, int
     }
     /* second-generation kernels: their staging index math uses 24-bit multiplies (row strides below 2^24 floats) */
     const bool v2_ok = bgk_h2_variant == 2 && K == KB && ldc < (1 << 24) && ldy < (1 << 24) && ldo < (1 << 24);
+    if (row_order == 2 && !(v2_ok && z0 == nullptr)) {
+        bgk_set_error("%s: output-layer row order 2 is read by the second-generation inference kernel only (8 bins, hidden width 128)", what);
+        return BGK_EUNSUPPORTED;
+    }
     if (segs && segs->n > 1 && !v2_ok) return BGK_EUNSUPPORTED;     /* several conditioning tensors: second-generation kernels only */
     if (params_layout == 1 && !(v2_ok && z0 != nullptr && operand_dtype == 0 && params && z1)) return BGK_EUNSUPPORTED;   /* element-major parameters: second-generation kernel only */
     if (params_layout == 2 && !(v2_ok && z0 != nullptr && operand_dtype == 0 && z1)) return BGK_EUNSUPPORTED;             /* no parameter write-out: likewise */
@@ -1561,7 +1568,7 @@ int launch_h2(const char* what, const float* cond, int64_t ldc, int32_t d_c, int
     if (v2_ok && z0 == nullptr && operand_dtype == 0)   /* split-f16 inference: the second-generation kernel */
         return bgk_launch_rqs_dense_h2v2(what, cond, ldc, d_c, periodic, A0p, A1p, A2p, c0, c1, c2, cs_dev, act, y, ldy, B, d, circ_mask,
                                          inverse, left, right, bottom, top, min_bin_width, min_bin_height, min_derivative,
-                                         identity_init, out, ldo, dlogp, accumulate, bin_idx, oob_count, stream, segs);
+                                         identity_init, out, ldo, dlogp, accumulate, bin_idx, oob_count, stream, segs, row_order);
     FusedArgsH2 ah;
     FusedArgs& a = ah.f;
     a.cond = cond; a.ldc = ldc; a.d_c = d_c; a.periodic = periodic;

@@ -8,13 +8,15 @@
  * single (cond, ldc, d_c) tensor of the launcher's own arguments) */
 struct BgkCondSegs { const float* ptr[BGK_MAX_COND]; int64_t ld[BGK_MAX_COND]; int32_t w[BGK_MAX_COND]; int32_t n; };
 
+/* row_order: row order of the output-layer operand A2p -- 1 = bgk_pack_rqs_columns, 2 = bgk_pack_rqs_columns_v(row_order = 2): the
+ * split-f16 inference instance then keeps the spline's widths / heights in the accumulator registers (the other instances take 1 only) */
 int bgk_launch_rqs_dense_h2v2(const char* what, const float* cond, int64_t ldc, int32_t d_c, int32_t periodic,
                               const void* A0p, const void* A1p, const void* A2p, float c0, float c1, float c2, const float* cs_dev,
                               int32_t act, const float* y, int64_t ldy, int64_t B, int32_t d, uint64_t circ_mask, int32_t inverse,
                               double left, double right, double bottom, double top,
                               double min_bin_width, double min_bin_height, double min_derivative, int32_t identity_init,
                               float* out, int64_t ldo, float* dlogp, int32_t accumulate, int32_t* bin_idx, int32_t* oob_count,
-                              void* stream, const BgkCondSegs* segs = nullptr);
+                              void* stream, const BgkCondSegs* segs = nullptr, int32_t row_order = 1);
 
 /* the training forward (bgk_fused2_train.hip): same kernel + z0, z1 [B, 128] and params [B, P] written for the backward */
 int bgk_launch_rqs_dense_h2v2_train(const char* what, float* z0, float* z1, float* params, int64_t ldp, const int32_t* src_col,
@@ -24,7 +26,7 @@ int bgk_launch_rqs_dense_h2v2_train(const char* what, float* z0, float* z1, floa
                                     double left, double right, double bottom, double top,
                                     double min_bin_width, double min_bin_height, double min_derivative, int32_t identity_init,
                                     float* out, int64_t ldo, float* dlogp, int32_t accumulate, int32_t* bin_idx, int32_t* oob_count,
-                                    void* stream, const BgkCondSegs* segs = nullptr);
+                                    void* stream, const BgkCondSegs* segs = nullptr, int32_t row_order = 1);
 
 /* spline backward of a layer the training forward ran WITHOUT writing its parameters (params == NULL there): the output layer of
  * the conditioner redone from z1 on the matrix cores, bgk_rqs_vjp_element on every element (bgk_fused2_train.hip) */
@@ -42,7 +44,7 @@ int bgk_launch_rqs_dense_h2v2_bf16(const char* what, const float* cond, int64_t 
                                    double left, double right, double bottom, double top,
                                    double min_bin_width, double min_bin_height, double min_derivative, int32_t identity_init,
                                    float* out, int64_t ldo, float* dlogp, int32_t accumulate, int32_t* bin_idx, int32_t* oob_count,
-                                   void* stream, const BgkCondSegs* segs = nullptr);
+                                   void* stream, const BgkCondSegs* segs = nullptr, int32_t row_order = 1);
 
 /* affine coupling layer with conditioners of width 128 (two or three hidden layers) on the same event-threaded GEMM stream
  * (bgk_fused2.hip); BGK_EUNSUPPORTED for activation pairs it has no instance for */

@@ -21,6 +21,13 @@
  *     - the exact power-of-two unscale of the last GEMM is folded into the exp2 / softplus constants;
  *     - accumulators start from the inline-constant 0 C operand (no zero fills), dead tiles of the last chunk are
  *       not computed, staging index math uses a magic-number division.
+ *  3. Register-resident spline parameters (REGP; the split-f16 inference instance, operands in row order 2 of
+ *     bgk_pack_rqs_columns_v): an output row of the last Linear is an independent dot product, so the packer places the rows such
+ *     that the accumulator registers of tiles 0 / 2 ARE the widths and heights of the element the lane evaluates in spline slot
+ *     0 / 1.  Only the slope rows (indexed by the bin found) and the fifth dim of a chunk go through LDS (tiles 1, 3 -> a 64-row
+ *     slab); the next chunk's GEMM runs tile-major (LiveTM) and refills the registers in the order the spline releases them.
+ *     Same products in the same order per accumulator: bit-identical to row order 1, which the training forward, the bf16
+ *     instance and the recompute backward keep (they share the LDS chunk with parameter write-out and the VJP).
  *  Accuracy class: like the first split-f16 kernel (hardware exp2 / log2 / rcp / sqrt with one Newton step on the
  *  reciprocals): not bit-identical to the oracle; parity is asserted per sample at 1e-5 relative on log|det J| and
  *  bin indices may differ only where x is within rounding distance of a knot (tests/test_gpu_parity.py).
@@ -116,6 +123,7 @@ struct V2Args {
      * buffer, y / out [32][ys].  stage: 0 = per-lane loads (any strides / several tensors / periodic), 1 = the contiguous [32][d_c]
      * tile copied by the DMA path IS the feature tile (nfs = d_c), 2 = DMA of the raw tile + an elementwise cos / sin pass */
     int nfs, ys, stage, y_dma, out_lin;
+    int p_floats;                     /* floats of the s_p region in front of the y tile */
 #if BGK_V2_SAVE
     float* z0; float* z1;             /* scaled pre-activations [B, 128] */
     float* params; int64_t ldp;       /* spline parameters [B, P] in the reference's column order, or (src_col == NULL) element-major [B][d][3 K + 1] */
@@ -232,6 +240,92 @@ struct NoLive {
     template <int HK, int NH> __device__ __forceinline__ void hook() {}
 };
 
+/* ---- the same GEMM issued TILE-major: all 25 events of one tile (8 k-steps x 3 products, then its bias), then the next tile -------
+ * Every accumulator sees its products in the order of Live (k-step ascending, lo*hi, hi*lo, hi*hi, bias last), so the sums are the
+ * same bits; only the interleaving between tiles differs (no effect on speed: profiles/README.md r04, event order).  The tiles
+ * come in the order in which the registers of the PREVIOUS chunk die in the register-resident spline (chunk_piped_reg): the two
+ * slab tiles 1, 3 at once, tile 0 behind spline slot 0, tile 2 behind slot 1 -- so the chunk in flight and the chunk being
+ * evaluated share one set of 64 accumulator registers.  Load step L = 9 i + s: k-step s (s = 8: the bias block) of the i-th tile. */
+template <int NT>
+struct LiveTM {
+    static constexpr int LPT = KS + 1;            /* load steps per tile */
+    static constexpr int NLS = LPT * NT;
+    static constexpr int EPT = 3 * KS + 1;        /* events per tile */
+    static constexpr int NEV = EPT * NT;
+    static constexpr int tile_of(int i) { return NT == 4 ? (i == 0 ? 1 : (i == 1 ? 3 : (i == 2 ? 0 : 2))) : (i == 0 ? 1 : 0); }
+    f32x16 (&out)[4];
+    const BFrag& b;
+    const uint4* W;
+    unsigned voff;
+    TFrag (&ring)[RD];
+    __amdgpu_buffer_rsrc_t rs;
+
+    template <int BLK>
+    __device__ __forceinline__ u32x4 blk() {
+        return __builtin_amdgcn_raw_buffer_load_b128(rs, voff + ((BLK * 1024) & 4095), (BLK * 1024) & ~4095, 0);
+    }
+    template <int L>
+    __device__ __forceinline__ void load() {
+        if constexpr (L < NLS) {
+            constexpr int s = L % LPT, m = tile_of(L / LPT);
+            if constexpr (s < KS) {
+                ring[L % RD].hi = blk<(s * 4 + m) * 2>();
+                ring[L % RD].lo = blk<(s * 4 + m) * 2 + 1>();
+            } else {
+                ring[L % RD].hi = blk<KS * 4 * 2 + m>();
+            }
+        }
+    }
+    template <int L0, int L1>
+    __device__ __forceinline__ void loads() {
+        if constexpr (L0 < L1) { load<L0>(); loads<L0 + 1, L1>(); }
+    }
+    __device__ __forceinline__ void start() {
+        __builtin_amdgcn_sched_barrier(0);
+        rs = __builtin_amdgcn_make_buffer_rsrc((void*)W, 0, 0x7fffffff, 0x00020000);
+        loads<0, RD>();
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    template <int E>
+    __device__ __forceinline__ void event() {
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (E < NEV) {
+            constexpr int i = E / EPT, e = E % EPT, m = tile_of(i);
+            if constexpr (e < 3 * KS) {
+                constexpr int s = e / 3, p = e % 3, L = i * LPT + s;
+                const TFrag& f = ring[L % RD];
+                const h16x8 a = __builtin_bit_cast(h16x8, p == 0 ? f.lo : f.hi);
+                const h16x8 bb = p == 1 ? b.lo[s] : b.hi[s];
+                if constexpr (s == 0 && p == 0) {
+                    const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                    out[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bb, z, 0, 0, 0);
+                } else {
+                    out[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bb, out[m], 0, 0, 0);
+                }
+                if constexpr (p == 2) load<L + RD>();
+            } else {
+                constexpr int L = i * LPT + KS;
+                const h16x8 one2 = {(_Float16)1.0f, (_Float16)1.0f, 0, 0, 0, 0, 0, 0};
+                out[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, ring[L % RD].hi), one2, out[m], 0, 0, 0);
+                load<L + RD>();
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    template <int E0, int E1>
+    __device__ __forceinline__ void events() {
+        if constexpr (E0 < E1) {
+            event<E0>();
+            events<E0 + 1, E1>();
+        }
+    }
+    template <int HK, int NH>
+    __device__ __forceinline__ void hook() {
+        constexpr int e0 = (HK * NEV) / NH, e1 = ((HK + 1) * NEV) / NH;
+        if constexpr (e0 < e1) events<e0, e1>();
+    }
+};
+
 /* hook adapters: map the hook index of a code region (activation of one tile: 8 hooks; spline slot: EH hooks) to the
  * hook space of the overlapped GEMM */
 template <class G, int BASE, int NH>
@@ -300,8 +394,9 @@ __device__ __forceinline__ void act_split_tile(H hk, const f32x16& t, float c, B
 }
 
 /* ---- spline element, hardware-transcendental / regrouped form ------------------------------------------------------
- * pa / pb / ps: the element's 8 unnormalised searched-set / other-set / slope rows in the LDS chunk (row stride ST), UNSCALED
- * accumulator values (true parameter = value * c2; kL = c2 log2 e, kz = c2 beta log2 e fold the factor).  ps[8 ST] is the
+ * va / vb: the element's 8 unnormalised searched-set / other-set values (read from the LDS chunk, or accumulator registers of the
+ * lane: spline_slot / spline_slot_reg); ps: its slope rows in LDS (row stride pst); all UNSCALED
+ * accumulator values (true parameter = value * c2; kL = c2 log2 e, kz = c2 beta log2 e fold the factor).  ps[8 pst] is the
  * non-circular extra slope row.  Follows nflows' rational_quadratic_spline like bgk_rqs_element. */
 struct SpK { float kL, kz, c2; };
 
@@ -328,18 +423,13 @@ template <> struct ScSrc<false> {
 };
 
 template <int INV, class H>
-__device__ __forceinline__ float rqs_fast(H hk, float x, const float* pa, const float* pb, const float* ps, bool circ,
+__device__ __forceinline__ float rqs_fast(H hk, float x, const float (&va)[KB], const float (&vb)[KB], const float* ps, int pst, bool circ,
                                           const V2Args& a, const SpK& k, float* lad, int* bin, int* oob) {
     /* the spline constants: (re)read from the kernel argument block by scalar loads inside the element (inverse instance: fewer
      * live SGPRs win there), or kept in SGPRs for the whole tile (forward instance: ~470 fewer s_load + s_waitcnt per tile; A/B
      * on one box: forward -2 % with registers, inverse +2 %) */
     const ScSrc<(BGK_V2_KARG == 2 ? INV != 0 : BGK_V2_KARG != 0)> scs(a);
 #define SC scs.get()
-    float va[KB], vb[KB];
-#pragma unroll
-    for (int i = 0; i < KB; ++i) va[i] = pa[i * ST];
-#pragma unroll
-    for (int i = 0; i < KB; ++i) vb[i] = pb[i * ST];
     *oob = (x < SC.left) | (x > SC.right);
     x = __builtin_amdgcn_fmed3f(x, SC.left, SC.right);
     /* ---- searched set: softmax numerators, running sums, the 7 interior knots, comparison masks ---- */
@@ -403,7 +493,7 @@ __device__ __forceinline__ float rqs_fast(H hk, float x, const float* pa, const 
     hk.template at<11>();
     /* the two slopes of the bin (dynamic LDS rows; circular dims wrap the last knot's slope to row 0) */
     const int j1 = circ ? ((idx + 1) & 7) : (idx + 1);
-    const float s_lo = ps[idx * ST], s_hi = ps[j1 * ST];
+    const float s_lo = ps[idx * pst], s_hi = ps[j1 * pst];
     const float A_i = hi - lo;
     /* ---- other set: only knot[idx], knot[idx + 1] ---- */
     float mB = __builtin_fmaxf(__builtin_fmaxf(vb[0], vb[1]), vb[2]);
@@ -539,7 +629,14 @@ __device__ __forceinline__ void spline_slot(G& g, const V2Args& a, const SpK& k,
     float lad;
     const float x = s_y[j * a.ys + dim];
     Hooks<G, IT * EH, NHK> hk{g};
-    const float o = rqs_fast<INV>(hk, x, INV ? pw : ph, INV ? ph : pw, ps, circ, a, k, &lad, &bin, &oob);
+    const float* pa = INV ? pw : ph;
+    const float* pb = INV ? ph : pw;
+    float va[KB], vb[KB];
+#pragma unroll
+    for (int i = 0; i < KB; ++i) va[i] = pa[i * ST];
+#pragma unroll
+    for (int i = 0; i < KB; ++i) vb[i] = pb[i * ST];
+    const float o = rqs_fast<INV>(hk, x, va, vb, ps, ST, circ, a, k, &lad, &bin, &oob);
     s_y[valid ? j * a.ys + dim : 32 * a.ys + j] = o;         /* (32 spare floats behind the tile take the results of invalid slots) */
     oob_local += (valid && j < rows) ? oob : 0;
     bins[IT] = bin;
@@ -614,6 +711,78 @@ __device__ __forceinline__ void chunk_piped(const V2Args& a, const SpK& k, float
     spline_slot<INV, 0, 3 * EH>(g, a, k, s_p, s_y, c, DPC, hh, j, rows, run, oob_local, bins);
     spline_slot<INV, 1, 3 * EH>(g, a, k, s_p, s_y, c, DPC, hh, j, rows, run, oob_local, bins);
     spline_slot<INV, 2, 3 * EH>(g, a, k, s_p, s_y, c, DPC, hh, j, rows, run, oob_local, bins);
+}
+
+/* ---- register-resident spline parameters (inference instance; operand rows in order 2 of bgk_pack_rqs_columns_v) --------------
+ * The rows of the output layer are permuted at pack time so that the accumulators ARE the spline's operands: register r of tile
+ * 2 IT holds, in the lower half-wave, width r (r < 8) / height r - 8 of dim 2 IT of the chunk and in the upper half-wave the same
+ * of dim 2 IT + 1 -- the element that spline slot IT of that lane evaluates.  Only what is indexed at run time or belongs to the
+ * half-wave-less fifth dim goes through LDS: tiles 1 and 3 are a slab of 64 rows [row][sample] -- rows 9 q .. 9 q + 8 the slope
+ * rows of dim q (the two slopes of the bin found are dynamic reads, 2 ds_read + 3 VALU per element against ~14 VALU of two 8-way
+ * select chains), rows 45 .. 52 / 53 .. 60 the widths / heights of dim 4.  32 ds_write + 16 (+ 16 for slot 2) ds_read per lane and
+ * chunk instead of 64 + 48, and the slab is 8 KiB per wave instead of 16.5. */
+constexpr int SLAB = 64 * 32;         /* floats */
+constexpr int SLAB_SLOPES = KB + 1;   /* slab rows per dim */
+constexpr int SLAB_D4 = 5 * SLAB_SLOPES;
+__device__ __forceinline__ void slab_to_lds(const f32x16 (&h)[4], float* s_p, int hh, int j) {
+#pragma unroll
+    for (int mm = 0; mm < 2; ++mm)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s_p[drow(mm, r, hh) * 32 + j] = h[1 + 2 * mm][r];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+template <int INV, int IT, int NHK, class G>
+__device__ __forceinline__ void spline_slot_reg(G& g, const V2Args& a, const SpK& k, const f32x16& t, const float* s_p, float* s_y, int c, int nd,
+                                                int hh, int j, int rows, float& run, int& oob_local, int (&bins)[3]) {
+    const int q = 2 * IT + hh;
+    const bool valid = q < nd;
+    const int qq = valid ? q : 0;
+    const int dim = c * DPC + qq;
+    const float* ps = s_p + (qq * SLAB_SLOPES) * 32 + j;
+    const bool circ = (a.circ_mask >> dim) & 1ull;
+    int bin, oob;
+    float lad;
+    const float x = s_y[j * a.ys + dim];
+    Hooks<G, IT * EH, NHK> hk{g};
+    float va[KB], vb[KB];
+    if constexpr (IT < 2) {
+#pragma unroll
+        for (int i = 0; i < KB; ++i) { va[i] = INV ? t[i] : t[KB + i]; vb[i] = INV ? t[KB + i] : t[i]; }
+    } else {
+        const float* pw = s_p + SLAB_D4 * 32 + j;
+        const float* pa = INV ? pw : pw + KB * 32;
+        const float* pb = INV ? pw + KB * 32 : pw;
+#pragma unroll
+        for (int i = 0; i < KB; ++i) va[i] = pa[i * 32];
+#pragma unroll
+        for (int i = 0; i < KB; ++i) vb[i] = pb[i * 32];
+    }
+    const float o = rqs_fast<INV>(hk, x, va, vb, ps, 32, circ, a, k, &lad, &bin, &oob);
+    s_y[valid ? j * a.ys + dim : 32 * a.ys + j] = o;         /* (32 spare floats behind the tile take the results of invalid slots) */
+    oob_local += (valid && j < rows) ? oob : 0;
+    bins[IT] = bin;
+    lad = valid ? lad : 0.0f;
+    float l0 = lad, l1 = lad;                                 /* both halves add the dims in ascending order (see spline_slot) */
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(l0), "+v"(l1));
+    run += l0;
+    run += l1;
+}
+
+/* chunk c: slab tiles -> LDS, then the spline of this chunk threaded through the next chunk's tile-major GEMM, which refills h in
+ * the order its registers die (LiveTM) */
+template <int INV, int NT>
+__device__ __forceinline__ void chunk_piped_reg(const V2Args& a, const SpK& k, float* s_p, float* s_y, int c, int hh, int j, int rows,
+                                                float& run, int& oob_local, int (&bins)[3], f32x16 (&h)[4], const BFrag& bf,
+                                                TFrag (&ring)[RD], unsigned voff) {
+    LiveTM<NT> g{h, bf, a.A2 + (size_t)(c + 1) * GBLK * 64, voff, ring};
+    g.start();
+    slab_to_lds(h, s_p, hh, j);
+    __builtin_amdgcn_sched_barrier(0);
+    spline_slot_reg<INV, 0, 3 * EH>(g, a, k, h[0], s_p, s_y, c, DPC, hh, j, rows, run, oob_local, bins);
+    spline_slot_reg<INV, 1, 3 * EH>(g, a, k, h[2], s_p, s_y, c, DPC, hh, j, rows, run, oob_local, bins);
+    spline_slot_reg<INV, 2, 3 * EH>(g, a, k, h[2], s_p, s_y, c, DPC, hh, j, rows, run, oob_local, bins);
 }
 
 /* linear DMA copy of a wave's contiguous, 16-byte aligned tile of n floats (a multiple of 4) into LDS; only the first `valid`
@@ -804,16 +973,18 @@ __device__ __forceinline__ void l0_step(f32x16 (&h)[4], const L0Frag& fr, const 
 /* SAVEP (training variant only): the spline parameters are written out.  The instance without it is the default training forward since
  * the backward recomputes them: with the write-out compiled in (and skipped at run time) its loop-invariant row pointers and LDS
  * addresses cost 18 spilled registers, one of them reloaded -- behind a vmcnt(0) -- in front of every chunk's transposition. */
-template <int ACT, int INV, bool SAVEP = true>
+template <int ACT, int INV, bool SAVEP = true, bool REGP = false>      /* REGP: register-resident spline parameters (operand row order 2) */
 __global__ __launch_bounds__(FTHREADS, 2) void coupling_rqs_dense_h2v2_kernel(V2Args a) {
+    static_assert(!REGP || (!BGK_V2_SAVE && !BGK_V2_BF16), "row order 2 belongs to the split-f16 inference instance");
     if (a.cs_dev) { a.c0 = a.cs_dev[1]; a.c1 = a.cs_dev[3]; a.c2 = a.cs_dev[5]; }   /* wave-uniform scalar loads */
     /* MODE.FP16_OVFL: f16 conversions saturate at +-65504 instead of producing inf (whose lo part would be inf - inf), so the
      * activation code carries no clamp instructions */
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int wave = threadIdx.x >> 6;
+    /* (REGP: the wave index as a scalar -- the LDS base then lives in an SGPR instead of a VGPR carried through the chunk loop) */
+    const int wave = REGP ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
     float* s_p = smem + (size_t)wave * a.lds_per_wave;   /* parameter chunk [128][ST]; first the conditioner feature tile [32][nfs] */
-    float* s_y = s_p + 128 * ST;                          /* y / out tile [32][ys] + 32 spare floats */
+    float* s_y = s_p + (REGP ? a.p_floats : 128 * ST);    /* y / out tile [32][ys] + 32 spare floats (REGP: s_p = the slab [64][32], or the larger feature tile) */
     const int d = a.d;
     const int64_t n_tiles = (a.B + 31) / 32;
     const int64_t tile = (int64_t)blockIdx.x * FW + wave;
@@ -932,6 +1103,20 @@ __global__ __launch_bounds__(FTHREADS, 2) void coupling_rqs_dense_h2v2_kernel(V2
     for (int c = 0; c < a.n_chunks; ++c) {
         int bins[3] = {0, 0, 0};
         const int nd = (d - c * DPC) < DPC ? (d - c * DPC) : DPC;
+        if constexpr (REGP) {
+            /* the three cases below on the register-resident forms */
+            if (c + 2 < a.n_chunks || (c + 2 == a.n_chunks && a.last_tiles > 2)) {
+                chunk_piped_reg<INV, 4>(a, k, s_p, s_y, c, hh, j, rows, run, oob_local, bins, h, bf, ring, voff);
+            } else if (c + 2 == a.n_chunks) {
+                chunk_piped_reg<INV, 2>(a, k, s_p, s_y, c, hh, j, rows, run, oob_local, bins, h, bf, ring, voff);
+            } else {
+                NoLive none;
+                slab_to_lds(h, s_p, hh, j);
+                spline_slot_reg<INV, 0, 1>(none, a, k, h[0], s_p, s_y, c, nd, hh, j, rows, run, oob_local, bins);
+                if (nd > 2) spline_slot_reg<INV, 1, 1>(none, a, k, h[2], s_p, s_y, c, nd, hh, j, rows, run, oob_local, bins);
+                if (nd > 4) spline_slot_reg<INV, 2, 1>(none, a, k, h[2], s_p, s_y, c, nd, hh, j, rows, run, oob_local, bins);
+            }
+        } else
         if (c + 2 < a.n_chunks || (c + 2 == a.n_chunks && a.last_tiles > 2)) {
             chunk_piped<INV, 4, SAVEP>(a, k, s_p, s_y, c, hh, j, rows, run, oob_local, bins, h, bf, ring, voff, b0);
         } else if (c + 2 == a.n_chunks) {
@@ -960,13 +1145,21 @@ __global__ __launch_bounds__(FTHREADS, 2) void coupling_rqs_dense_h2v2_kernel(V2
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
-    if (hh == 0 && j < rows) {
-        if (a.accumulate) a.dlogp[b0 + j] += run; else a.dlogp[b0 + j] = run;
+    int lane_e = lane;
+    if constexpr (REGP) {
+        /* the lane index again, from the exec mask count instead of a register carried across the chunk loop: that loop runs at the
+         * full 256-register budget, and the one value it had to spill was this one (reloaded behind a vmcnt(0)) */
+        int zero = 0;
+        asm volatile("" : "+v"(zero));
+        lane_e = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)zero));
     }
-    store_tile32(out_t, ldo32, s_y, ys, d, a.magic_d, rows, lane, a.out_lin);
+    if ((lane_e >> 5) == 0 && (lane_e & 31) < rows) {
+        if (a.accumulate) a.dlogp[b0 + (lane_e & 31)] += run; else a.dlogp[b0 + (lane_e & 31)] = run;
+    }
+    store_tile32(out_t, ldo32, s_y, ys, d, a.magic_d, rows, lane_e, a.out_lin);
     if (a.oob_count && __builtin_amdgcn_ballot_w64(oob_local != 0)) {     /* rare: inputs outside the spline domain */
         for (int off = 32; off > 0; off >>= 1) oob_local += __shfl_xor(oob_local, off);
-        if (lane == 0) atomicAdd(a.oob_count, oob_local);
+        if (lane_e == 0) atomicAdd(a.oob_count, oob_local);
     }
     V2_TS(5 + a.n_chunks);
   }
@@ -1673,8 +1866,15 @@ int bgk_launch_rqs_dense_h2v2(const char* what, const float* cond, int64_t ldc, 
                               double left, double right, double bottom, double top,
                               double min_bin_width, double min_bin_height, double min_derivative, int32_t identity_init,
                               float* out, int64_t ldo, float* dlogp, int32_t accumulate, int32_t* bin_idx, int32_t* oob_count,
-                              void* stream, const BgkCondSegs* segs) {
+                              void* stream, const BgkCondSegs* segs, int32_t row_order) {
     V2Args a;
+#if BGK_V2_SAVE || BGK_V2_BF16
+    BGK_CHECK_ARG(row_order == 1, "%s: output-layer row order %d (this instance takes order 1)", what, row_order);
+    constexpr bool regp = false;
+#else
+    BGK_CHECK_ARG(row_order == 1 || row_order == 2, "%s: output-layer row order %d (1 | 2)", what, row_order);
+    const bool regp = row_order == 2;
+#endif
     const int n_in = periodic ? 2 * d_c : d_c;
     BGK_CHECK_ARG(make_cond_segs(a.cs, cond, ldc, d_c, segs), "%s: bad conditioning segments", what);
     a.d_c = d_c; a.periodic = periodic;
@@ -1696,7 +1896,12 @@ int bgk_launch_rqs_dense_h2v2(const char* what, const float* cond, int64_t ldc, 
     const TilePlan tp = plan_tiles(a.cs, d_c, periodic, y, ldy, out, ldo, d, 128 * ST);
     a.nfs = tp.nfs; a.ys = tp.ys; a.stage = tp.stage; a.y_dma = tp.y_dma; a.out_lin = tp.out_lin;
     BGK_CHECK_ARG(32 * a.nfs + 16 <= 128 * ST, "%s: %d conditioner input features do not fit the LDS tile", what, n_in);
-    a.lds_per_wave = ((128 * ST + 32 * a.ys + 32 + 3) / 4) * 4;
+    a.p_floats = 128 * ST;
+    if (regp) {       /* the slab [64][32]; before the first chunk the feature tile (+ the raw tile of the periodic DMA form) where that is larger */
+        const int feat = 32 * a.nfs + (a.stage == 2 ? 32 * d_c : 0) + 16;
+        a.p_floats = ((feat > SLAB ? feat : SLAB) + 3) / 4 * 4;
+    }
+    a.lds_per_wave = ((a.p_floats + 32 * a.ys + 32 + 3) / 4) * 4;
 #if BGK_V2_SAVE
     a.z0 = z0; a.z1 = z1; a.params = params; a.ldp = ldp; a.src_col = src_col;
 #endif
@@ -1710,8 +1915,11 @@ int bgk_launch_rqs_dense_h2v2(const char* what, const float* cond, int64_t ldc, 
 #if BGK_V2_SAVE
 #define BGK_LAUNCH(A, I) do { if (params) hipLaunchKernelGGL((coupling_rqs_dense_h2v2_kernel<A, I, true>), dim3(grid), dim3(FTHREADS), shmem, st, a); \
                               else hipLaunchKernelGGL((coupling_rqs_dense_h2v2_kernel<A, I, false>), dim3(grid), dim3(FTHREADS), shmem, st, a); } while (0)
-#else
+#elif BGK_V2_BF16
 #define BGK_LAUNCH(A, I) hipLaunchKernelGGL((coupling_rqs_dense_h2v2_kernel<A, I>), dim3(grid), dim3(FTHREADS), shmem, st, a)
+#else
+#define BGK_LAUNCH(A, I) do { if (regp) hipLaunchKernelGGL((coupling_rqs_dense_h2v2_kernel<A, I, true, true>), dim3(grid), dim3(FTHREADS), shmem, st, a); \
+                              else hipLaunchKernelGGL((coupling_rqs_dense_h2v2_kernel<A, I>), dim3(grid), dim3(FTHREADS), shmem, st, a); } while (0)
 #endif
     if (act == 1) { if (inverse) BGK_LAUNCH(1, 1); else BGK_LAUNCH(1, 0); }
     else if (act == 2) { if (inverse) BGK_LAUNCH(2, 1); else BGK_LAUNCH(2, 0); }

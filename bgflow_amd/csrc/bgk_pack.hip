@@ -185,6 +185,53 @@ void launch_pack(const PackLayer& L0, const PackLayer& L1, const PackLayer& L2, 
 
 }  // namespace
 
+/* Row order 2 of the spline layers' output operand (8 bins; bgk_fused2.hip, register-resident spline parameters): a permutation of
+ * the 128 rows of every chunk of bgk_pack_rqs_columns' order 1 (dim q of the chunk = rows 25 q .. 25 q + 24: 8 widths, 8 heights,
+ * 8 slopes, the non-circular extra slope).  Position 32 m + t of a chunk is accumulator register r of tile m in the half-wave hh
+ * with t = (r & 3) + 8 (r >> 2) + 4 hh:
+ *   tile 0 / tile 2: register r of half hh = width r (r < 8) / height r - 8 of dim hh / dim 2 + hh  (spline slots 0 / 1)
+ *   tiles 1, 3: slab row sigma = 32 (m >> 1) + t:  9 q + i = slope row i of dim q,  45 + e = width / height e of dim 4
+ * A chunk with one or two dims lives in tiles 0 and 1, like order 1's 25 / 50 rows (the kernels' dead-tile rule).
+ * perm128 (may be NULL): position -> row of order 1 within the chunk, -1 = unused. */
+namespace {
+void rqs_row_perm2(int32_t* perm) {
+    for (int i = 0; i < 128; ++i) perm[i] = -1;
+    for (int q = 0; q < 5; ++q)
+        for (int e = 0; e < 25; ++e) {
+            int m, t;
+            if (q < 4 && e < 16) {
+                m = 2 * (q >> 1);
+                t = (e & 3) + 8 * (e >> 2) + 4 * (q & 1);
+            } else {
+                const int sigma = e >= 16 ? 9 * q + (e - 16) : 45 + e;
+                m = 1 + 2 * (sigma >> 5);
+                t = sigma & 31;
+            }
+            perm[32 * m + t] = 25 * q + e;
+        }
+}
+}  // namespace
+
+extern "C" int32_t bgk_pack_rqs_columns_v(int32_t d, int32_t K, const int32_t* nc_slot_host, int32_t row_order, int32_t* src_col, int32_t* perm128) {
+    if (row_order == 1) {
+        if (perm128) for (int i = 0; i < 128; ++i) perm128[i] = i;
+        return bgk_pack_rqs_columns(d, K, nc_slot_host, src_col);
+    }
+    if (row_order != 2 || K != 8 || d <= 0) return BGK_EINVAL;
+    int32_t perm[128];
+    rqs_row_perm2(perm);
+    if (perm128) for (int i = 0; i < 128; ++i) perm128[i] = perm[i];
+    const int ncp = bgk_pack_rqs_columns(d, K, nullptr, nullptr);
+    if (src_col) {
+        int32_t* tmp = new int32_t[ncp];
+        bgk_pack_rqs_columns(d, K, nc_slot_host, tmp);
+        for (int c = 0; c < ncp / 128; ++c)
+            for (int i = 0; i < 128; ++i) src_col[c * 128 + i] = perm[i] >= 0 ? tmp[c * 128 + perm[i]] : -1;
+        delete[] tmp;
+    }
+    return ncp;
+}
+
 extern "C" int bgk_pack_dense_h2(const float* W0, const float* b0, int32_t n_in, int32_t H,
                                  const float* W1, const float* b1,
                                  const float* W2, const float* b2, int32_t rows2,

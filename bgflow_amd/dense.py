@@ -810,9 +810,11 @@ def _fused_affine_anydepth(transformer, plan, x, y2, ldy, B, d, out, ldo, dlogp,
     return out, dlogp[:, None]
 
 
-def pack_dense_for_fused_h2(linears, nc_slot_host, d, n_bins):
+def pack_dense_for_fused_h2(linears, nc_slot_host, d, n_bins, row_order=1):
     """Pack DenseNet([n_in, 128, 128, P]) for bgk_coupling_rqs_dense_h2.
-    Returns (A0, A1, A2 f16 device tensors, (c0, c1, c2) unscale factors)."""
+    Returns (A0, A1, A2 f16 device tensors, (c0, c1, c2) unscale factors).  ``row_order``: order of the output layer's rows
+    (bgk_pack_rqs_columns_v): 1 = what every kernel reads; 2 = the permutation the split-f16 inference kernel reads with
+    operand_dtype 2 (8 bins; widths / heights of a lane's element in that lane's accumulator registers)."""
     l0, l1, l2 = linears
     W0, b0 = l0.weight.detach().float(), l0.bias.detach().float()
     W1, b1 = l1.weight.detach().float(), l1.bias.detach().float()
@@ -825,11 +827,8 @@ def pack_dense_for_fused_h2(linears, nc_slot_host, d, n_bins):
     W0e[:, n_in] = b0                                   # column of the constant-1 feature
     A0 = _pack_h2(W0e * 2.0 ** e0, None, _h2_k_natural(S0))
     A1 = _pack_h2(W1 * 2.0 ** e1, b1 * 2.0 ** e1, _h2_k_hidden())
-    ncp = _lib.lib().bgk_pack_rqs_columns(d, n_bins, None, None)
-    src = np.empty(ncp, dtype=np.int32)
-    slots = np.ascontiguousarray(nc_slot_host, dtype=np.int32)
-    _lib.lib().bgk_pack_rqs_columns(d, n_bins, slots.ctypes.data, src.ctypes.data)
-    src_t = torch.as_tensor(src.astype(np.int64), device=W2.device)
+    src_t = _src_col_table(d, n_bins, nc_slot_host, W2.device, row_order).to(torch.int64)
+    ncp = src_t.numel()
     W2r = torch.where(src_t[:, None] >= 0, W2[src_t.clamp_min(0)], torch.zeros((), dtype=W2.dtype, device=W2.device)) * 2.0 ** e2
     b2r = torch.where(src_t >= 0, b2[src_t.clamp_min(0)], torch.zeros((), dtype=b2.dtype, device=b2.device)) * 2.0 ** e2
     A2 = torch.cat([_pack_h2(W2r[c * 128:(c + 1) * 128], b2r[c * 128:(c + 1) * 128], _h2_k_hidden())
@@ -1004,12 +1003,39 @@ def repack_training_plans(param_ids=None):
     return done
 
 
-def _src_col_table(d, n_bins, nc_slot_host, device):
-    ncp = _lib.lib().bgk_pack_rqs_columns(d, n_bins, None, None)
+def _src_col_table(d, n_bins, nc_slot_host, device, row_order=1):
+    """packed row -> source row of the output layer (-1 = padding) in row order ``row_order`` (bgk_pack_rqs_columns_v)"""
+    ncp = _lib.lib().bgk_pack_rqs_columns_v(d, n_bins, None, row_order, None, None)
+    if ncp <= 0:
+        raise ValueError(f"no row order {row_order} for {n_bins} bins")
     src = np.empty(ncp, dtype=np.int32)
     slots = np.ascontiguousarray(nc_slot_host, dtype=np.int32)
-    _lib.lib().bgk_pack_rqs_columns(d, n_bins, slots.ctypes.data, src.ctypes.data)
+    _lib.lib().bgk_pack_rqs_columns_v(d, n_bins, slots.ctypes.data, row_order, src.ctypes.data, None)
     return torch.as_tensor(src, device=device)
+
+
+def rqs_row_perm(row_order):
+    """[128] int32: position within a 128-row chunk of row order ``row_order`` -> row of order 1 within the chunk (-1 = unused)"""
+    perm = np.empty(128, dtype=np.int32)
+    if _lib.lib().bgk_pack_rqs_columns_v(1, 8, None, row_order, None, perm.ctypes.data) <= 0:
+        raise ValueError(f"no row order {row_order}")
+    return perm
+
+
+REGISTER_PARAMS = True     # split-f16 inference (8 bins, width 128) on operands in row order 2; False: the order-1 operands (same bits)
+
+
+def _regparam_operands(plan):
+    """The operands of the split-f16 inference kernel with the output layer in row order 2, packed on demand and keyed on the same
+    parameter state as the plan's order-1 operands (which the training forward, its backward and the other kernels keep reading;
+    repack_training_plans refreshes only those).  Returns (A0, A1, A2, cs)."""
+    if plan.get("regp_version") != plan["version"]:
+        if "src_col_dev2" not in plan:
+            plan["src_col_dev2"] = _src_col_table(plan["y_dim"], plan["n_bins"], plan["regp_slots"], plan["device"], 2)
+        plan["regp_bufs"] = pack_dense_for_fused_h2_device(plan["regp_linears"], plan["src_col_dev2"], plan["src_col_dev2"].numel() // 128,
+                                                           plan.get("regp_bufs"))
+        plan["regp_version"] = plan["version"]
+    return plan["regp_bufs"]
 
 
 def _gemm_mode(transformer):
@@ -1092,6 +1118,9 @@ def _fused_plan(transformer, y_dim, nc_slot_host):
             A0, A1, A2, cs = pack_dense_for_fused_h2_device((l0, l1, l2), cache["src_col_dev"], n_chunks, cache.get("bufs"),
                                                             bf16=(mode == "bf16"))
             cache.update(common, bufs=(A0, A1, A2, cs), packed=(A0, A1, A2, (1.0, 1.0, 1.0)), cs=cs)
+            if mode == "f16x2" and n_bins == 8:
+                # inference reads its own operand set with the output layer in row order 2 (_regparam_operands, packed when first used)
+                cache.update(regp_linears=(l0, l1, l2), regp_slots=np.array(nc_slot_host, dtype=np.int32))
         else:
             pack = pack_dense_for_fused if mode == "f32" else pack_dense_for_fused_h2
             cache.update(common, packed=pack((l0, l1, l2), nc_slot_host, y_dim, n_bins), cs=None)
@@ -1176,15 +1205,21 @@ def fused_spline_coupling(transformer, x, y, nc_slot_host, inverse, oob_counter,
         else:
             c0, c1, c2 = plan["packed"][3]
             ops = (_lib.ptr(W0p), _lib.ptr(W1p), _lib.ptr(W2p), c0, c1, c2, _lib.ptr(plan.get("cs")), int(plan["mode"] == "bf16"))
+            ops_try = [ops]
+            if REGISTER_PARAMS and "regp_linears" in plan and plan["hidden"] == 128:
+                # first choice; BGK_EUNSUPPORTED where the second-generation kernel does not run (option 1 = 1): the order-1 operands then
+                R0, R1, R2, rcs = _regparam_operands(plan)
+                ops_try.insert(0, (_lib.ptr(R0), _lib.ptr(R1), _lib.ptr(R2), c0, c1, c2, _lib.ptr(rcs), 2))
             st = -2
-            if len(parts) > 1:
-                ptrs, lds, widths, n, keep = _lib.cond_segments(parts)
-                st = _lib.lib().bgk_coupling_rqs_dense_h2_mc(ptrs, lds, widths, n, int(plan["periodic"]), *ops, *tail)
+            for ops in ops_try:
+                if len(parts) > 1:
+                    ptrs, lds, widths, n, keep = _lib.cond_segments(parts)
+                    st = _lib.lib().bgk_coupling_rqs_dense_h2_mc(ptrs, lds, widths, n, int(plan["periodic"]), *ops, *tail)
                 if st == -2:
-                    parts = [x.cat()]
-            if st == -2:
-                x2, ldc = _lib.rowmajor(parts[0])
-                st = _lib.lib().bgk_coupling_rqs_dense_h2(_lib.ptr(x2), ldc, plan["d_c"], int(plan["periodic"]), *ops, *tail)
+                    x2, ldc = _lib.rowmajor(x.cat() if len(parts) > 1 else parts[0])
+                    st = _lib.lib().bgk_coupling_rqs_dense_h2(_lib.ptr(x2), ldc, plan["d_c"], int(plan["periodic"]), *ops, *tail)
+                if st != -2:
+                    break
     if st == -2:
         return _reject(transformer, "shape outside the fused spline kernels' envelope: " + _lib.lib().bgk_last_error().decode(errors="replace"))
     _lib.check(st, "bgk_coupling_rqs_dense")

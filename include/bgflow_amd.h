@@ -338,6 +338,8 @@ int bgk_coupling_rqs_dense(const float* cond, int64_t ldc, int32_t d_c, int32_t 
  * operands were packed on the device by bgk_pack_dense_h2, cs_dev = its scale table (c0..c2 are then ignored).
  * operand_dtype 0: split-f16 (above); 1: single bf16 operands (bf16 parameter storage + bf16 GEMM inputs, f32
  * accumulate; knots, bin search and log-det stay f32) -- the reduced-precision variant of BASELINE config 5.
+ * operand_dtype 2: split-f16 operands whose output layer A2p is in row order 2 of bgk_pack_rqs_columns_v (8 bins, H0 = H1 = 128,
+ * inference): the spline's widths and heights stay in the accumulator registers; same results as operand_dtype 0, bit for bit.
  * H0 = H1 = 128: the envelope of every variant.  H0 = H1 = 256 (conditioner_factory.py:76-80 takes any `hidden`; 129 .. 255 units
  * zero-padded by the packer): split-f16 inference (operand_dtype 0) with operands from bgflow_amd/dense.py::pack_dense_for_fused_w256
  * -- one wave per SIMD on the unified 512-register file (bgk_fused.hip::coupling_rqs_dense_w256_kernel); other widths: BGK_EUNSUPPORTED. */
@@ -851,6 +853,13 @@ int bgk_whiten(const float* x, int64_t ldx, const float* T, const float* pre, co
  * layout, P = 3*K*d + n_nc) of every packed column, -1 for padding.  HOST function:
  * src_col is a host int32[NCp] buffer (pass NULL to query NCp only). */
 int32_t bgk_pack_rqs_columns(int32_t d, int32_t K, const int32_t* nc_slot_host, int32_t* src_col);
+
+/* The same table in row order `row_order`: 1 = bgk_pack_rqs_columns' order; 2 (K = 8 only) = every 128-row chunk permuted so that
+ * the split-f16 inference kernel finds the widths and heights of the element a lane evaluates in that lane's own accumulator
+ * registers (layout: csrc/bgk_pack.hip).  Operands packed from the order-2 table are passed to bgk_coupling_rqs_dense_h2 / _mc with
+ * operand_dtype = 2; every other entry point takes order 1.  perm128 (host int32[128], may be NULL): position within a chunk -> row
+ * of order 1 within the chunk, -1 = unused.  HOST function; returns NCp, BGK_EINVAL for an order this K has no layout for. */
+int32_t bgk_pack_rqs_columns_v(int32_t d, int32_t K, const int32_t* nc_slot_host, int32_t row_order, int32_t* src_col, int32_t* perm128);
 
 #pragma GCC visibility pop
 
