@@ -17,7 +17,8 @@ from .modulo import *        # noqa: F401,F403
 from .bg import *            # noqa: F401,F403
 from .factory import *       # noqa: F401,F403
 from .training import *      # noqa: F401,F403
-from . import configs, dp, factory, training, utils      # noqa: F401
+from .clipped import *       # noqa: F401,F403
+from . import clipped, configs, dp, factory, training, utils      # noqa: F401
 
 __version__ = "0.1.0"
 

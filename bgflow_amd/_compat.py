@@ -38,6 +38,7 @@ _MAP = {
     "distribution.energy": "distributions",
     "distribution.energy.base": "distributions",
     "distribution.energy.double_well": "distributions",
+    "distribution.energy.clipped": "clipped",
     "distribution.sampling": "distributions",
     "distribution.sampling.base": "distributions",
     "distribution.sampling.dataset": "training",
@@ -50,6 +51,7 @@ _MAP = {
     "factory.distribution_factory": "factory",
     "factory.icmarginals": "factory",
     "utils.types": "utils",
+    "utils.train": "clipped",
 }
 
 

@@ -12,8 +12,14 @@
  * Roofline: HBM, 4 (sum_f d_f + 1) B per sample forward, 4 (2 sum_f d_f + 1) B backward.  Rows of a tile are staged coalesced
  * through LDS (odd stride) in column chunks of 96 (any width fits), one lane per row adds its terms in ascending column order
  * (deterministic).  Rows that are multiples of 4 wide at 16-byte aligned addresses take the float4 kernels (energy_rows4_kernel, round 6:
- * L lanes per row, fixed xor tree); BGK_ENERGY_STAGED=1 keeps the staging kernels for every shape (the A/B). */
-#include "bgk_common.h"
+ * L lanes per row, fixed xor tree); BGK_ENERGY_STAGED=1 keeps the staging kernels for every shape (the A/B).
+ *
+ * The robust-training wrappers folded in (bgk_energy_fields_cut / _cut_backward; LinLogCutEnergy and GradientClippedEnergy,
+ * bgflow/distribution/energy/clipped.py:8-38, around a delegate described by fields): u = linlogcut(sum_f e_f + c_in) / T + c_out, the
+ * uncut sum saved (one float per sample) for the backward, which multiplies the row gradient by the cut's derivative and clips the
+ * FINAL gradient g_row (de / dx) / T of every field in groups of norm_dim elements before it is stored (what the reference's tensor
+ * hook sees).  Same kernels, the additions behind uniform branches: without them the arithmetic is the one above, bit for bit. */
+#include "bgk_clip.h"
 
 namespace {
 
@@ -31,6 +37,7 @@ struct EField {
 struct EArgs {
     EField f[NE_MAXF]; int n; int64_t B;
     float inv_t, c_in, c_out; float* u;
+    int cut; float high, max_e; float* v;                       /* lin-log cut of the field sum at T = 1; v [B]: the uncut sum, or NULL */
     const float* dlogp; int drop_nonfinite; float* partial;     /* partial [gridDim.x][2] or NULL */
 };
 typedef const __attribute__((address_space(4))) EArgs* eargs_t;   /* run-time indexed field table: scalar loads from the argument block */
@@ -85,7 +92,9 @@ __global__ __launch_bounds__(NE_THREADS) void energy_fields_kernel(EArgs a) {
             e += acc0 + 0.5f * acc;
         }
         if (tid < rows) {
-            const float u = (e + a.c_in) * a.inv_t + a.c_out;
+            const float v = e + a.c_in;
+            if (a.v) a.v[b0 + tid] = v;
+            const float u = (a.cut ? bgk_linlogcut(v, a.high, a.max_e) : v) * a.inv_t + a.c_out;
             a.u[b0 + tid] = u;
             if (a.partial) {
                 const float loss = u - a.dlogp[b0 + tid];
@@ -139,7 +148,9 @@ __global__ __launch_bounds__(NE_THREADS) void energy_rows4_kernel(EArgs a, int L
             e += part;
         }
         if (l == 0) {
-            const float u = (e + a.c_in) * a.inv_t + a.c_out;
+            const float v = e + a.c_in;
+            if (a.v) a.v[row] = v;
+            const float u = (a.cut ? bgk_linlogcut(v, a.high, a.max_e) : v) * a.inv_t + a.c_out;
             a.u[row] = u;
             if (a.partial) {
                 const float loss = u - a.dlogp[row];
@@ -176,11 +187,12 @@ __global__ __launch_bounds__(64) void energy_partial_reduce_kernel(const float* 
     }
 }
 
-struct EBwdField { const float* x; int64_t ldx; const float* p; float* g_x; int64_t ldg; int d, kind; float a, b, c; };
+struct EBwdField { const float* x; int64_t ldx; const float* p; float* g_x; int64_t ldg; int d, kind; float a, b, c; int nd; };   /* nd: clip group, 0 = none */
 struct EBwdArgs {
     EBwdField f[NE_MAXF]; int n; int64_t B; float inv_t;
     const float* g_u;                   /* [B] upstream gradient of u, or NULL: then g_u[b] = g_scalar[0] * mask[b] (loss-sum form) */
     const float* g_scalar; const float* u; const float* dlogp; int drop_nonfinite; float* g_dlogp;
+    const float* v; int cut; float high, max_e, clip;      /* v [B]: uncut field sums (cut != 0) */
 };
 typedef const __attribute__((address_space(4))) EBwdArgs* ebargs_t;
 
@@ -191,6 +203,10 @@ __global__ __launch_bounds__(NE_THREADS) void energy_fields_bwd_kernel(EBwdArgs 
         if (a.g_u) return a.g_u[r];
         const bool ok = !a.drop_nonfinite || __builtin_isfinite(a.u[r] - a.dlogp[r]);
         return ok ? gs : 0.0f;
+    };
+    auto x_grad = [&](int64_t r) -> float {      /* gradient of the row's field sum: through the cut and the temperature division */
+        const float g = row_grad(r);
+        return (a.cut ? g * bgk_linlogcut_grad(a.v[r], a.high, a.max_e) : g);
     };
     if (a.g_dlogp)                      /* d(sum_i (u_i - dlogp_i)) / d dlogp_i = -1 for the kept samples */
         for (int64_t r = (int64_t)blockIdx.x * NE_THREADS + threadIdx.x; r < a.B; r += (int64_t)gridDim.x * NE_THREADS)
@@ -204,14 +220,30 @@ __global__ __launch_bounds__(NE_THREADS) void energy_fields_bwd_kernel(EBwdArgs 
         const int64_t ldx = ka->f[fi].ldx, ldg = ka->f[fi].ldg;
         const float ca = ka->f[fi].a, cb = ka->f[fi].b, cc = ka->f[fi].c;
         const int64_t total = a.B * d;
+        const int nd = ka->f[fi].nd;
+        auto de_of = [&](int64_t r, int col) -> float {
+            const float v = x[r * ldx + col];
+            if (kind == 0) return v - (mean ? mean[col] : 0.0f);
+            return col == 0 ? ca + 2.0f * cb * v + 4.0f * cc * (v * v * v) : v;
+        };
+        if (nd > 0) {                   /* clipped field: a lane owns one group of nd elements at a time */
+            const int gpr = d / nd;
+            for (int64_t i = (int64_t)blockIdx.x * NE_THREADS + threadIdx.x; i < a.B * gpr; i += (int64_t)gridDim.x * NE_THREADS) {
+                const int64_t r = i / gpr;
+                const int c0 = (int)(i - r * gpr) * nd;
+                const float gr = x_grad(r);
+                if (nd == 1) { g_x[r * ldg + c0] = bgk_clip_value(bgk_clip_clean(gr * de_of(r, c0) * a.inv_t), a.clip); continue; }
+                float ss = 0.0f;
+                for (int j = 0; j < nd; ++j) { const float g = bgk_clip_clean(gr * de_of(r, c0 + j) * a.inv_t); ss += g * g; }
+                const float f = bgk_clip_factor(ss, a.clip);
+                for (int j = 0; j < nd; ++j) g_x[r * ldg + c0 + j] = bgk_clip_clean(gr * de_of(r, c0 + j) * a.inv_t) * f;
+            }
+            continue;
+        }
         for (int64_t i = (int64_t)blockIdx.x * NE_THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * NE_THREADS) {
             const int64_t r = i / d;
             const int col = (int)(i - r * d);
-            const float v = x[r * ldx + col];
-            float de;
-            if (kind == 0) de = v - (mean ? mean[col] : 0.0f);
-            else de = col == 0 ? ca + 2.0f * cb * v + 4.0f * cc * (v * v * v) : v;
-            g_x[r * ldg + col] = row_grad(r) * de * a.inv_t;
+            g_x[r * ldg + col] = x_grad(r) * de_of(r, col) * a.inv_t;
         }
     }
 }
@@ -226,6 +258,7 @@ __global__ __launch_bounds__(NE_THREADS) void energy_rows4_bwd_kernel(EBwdArgs a
         if (a.g_u) gr = a.g_u[row];
         else gr = (!a.drop_nonfinite || __builtin_isfinite(a.u[row] - a.dlogp[row])) ? gs : 0.0f;
         if (a.g_dlogp && l == 0) a.g_dlogp[row] = -gr;
+        if (a.cut) gr *= bgk_linlogcut_grad(a.v[row], a.high, a.max_e);
         for (int fi = 0; fi < a.n; ++fi) {
             const int kind = ka->f[fi].kind, d = ka->f[fi].d;
             float* g_x = ka->f[fi].g_x;
@@ -240,8 +273,10 @@ __global__ __launch_bounds__(NE_THREADS) void energy_rows4_bwd_kernel(EBwdArgs a
                 de = v;
                 if (l == 0) de.x = ka->f[fi].a + 2.0f * ka->f[fi].b * v.x + 4.0f * ka->f[fi].c * (v.x * v.x * v.x);
             }
-            *reinterpret_cast<float4*>(g_x + row * ka->f[fi].ldg + 4 * l) =
-                make_float4(gr * de.x * a.inv_t, gr * de.y * a.inv_t, gr * de.z * a.inv_t, gr * de.w * a.inv_t);
+            float4 o = make_float4(gr * de.x * a.inv_t, gr * de.y * a.inv_t, gr * de.z * a.inv_t, gr * de.w * a.inv_t);
+            const int nd = ka->f[fi].nd;
+            if (nd) o = bgk_clip_quad(o, nd, a.clip);          /* nd in {1, 2, 4}: whole groups inside the lane's float4 */
+            *reinterpret_cast<float4*>(g_x + row * ka->f[fi].ldg + 4 * l) = o;
         }
     }
 }
@@ -279,22 +314,26 @@ int fill_fields(const char* what, EField* f, int32_t n_fields, const float* cons
 
 }  // namespace
 
-extern "C" int bgk_energy_fields(const float* const* x, const int64_t* ldx, const int32_t* d, const int32_t* kind,
-                                 const float* const* param, const float* coef, int32_t n_fields, int64_t B,
-                                 double temperature, double c_in, double c_out, float* u,
-                                 const float* dlogp, int32_t drop_nonfinite, float* partial, int32_t nblk, double* loss_sums,
-                                 void* stream) {
-    BGK_CHECK_ARG((u || B == 0) && B >= 0 && temperature > 0.0, "bgk_energy_fields: bad arguments");
-    BGK_CHECK_ARG(!loss_sums || (dlogp && partial && nblk >= 1), "bgk_energy_fields: the loss sums need dlogp and a [nblk, 2] workspace");
+struct ECut { int cut; double high, max_e; };
+
+static int energy_fields_impl(const char* what, const float* const* x, const int64_t* ldx, const int32_t* d, const int32_t* kind,
+                              const float* const* param, const float* coef, int32_t n_fields, int64_t B,
+                              double temperature, double c_in, double c_out, ECut cut, float* u, float* u_uncut,
+                              const float* dlogp, int32_t drop_nonfinite, float* partial, int32_t nblk, double* loss_sums,
+                              void* stream) {
+    BGK_CHECK_ARG((u || B == 0) && B >= 0 && temperature > 0.0, "%s: bad arguments", what);
+    BGK_CHECK_ARG(!loss_sums || (dlogp && partial && nblk >= 1), "%s: the loss sums need dlogp and a [nblk, 2] workspace", what);
+    BGK_CHECK_ARG(!cut.cut || (cut.high == cut.high && cut.max_e == cut.max_e), "%s: the cut's high / max energy must be numbers", what);
     hipStream_t s = (hipStream_t)stream;
     if (B == 0) {               /* an empty batch (its tensors have no storage: null pointers): the loss sums are zero */
         if (loss_sums) { hipError_t e = hipMemsetAsync(loss_sums, 0, 2 * sizeof(double), s); if (e != hipSuccess) return (int)e; }
         return 0;
     }
     EArgs a{};
-    const int st = fill_fields("bgk_energy_fields", a.f, n_fields, x, ldx, d, kind, param, coef);
+    const int st = fill_fields(what, a.f, n_fields, x, ldx, d, kind, param, coef);
     if (st) return st;
     a.n = n_fields; a.B = B; a.inv_t = (float)(1.0 / temperature); a.c_in = (float)c_in; a.c_out = (float)c_out; a.u = u;
+    a.cut = cut.cut; a.high = (float)cut.high; a.max_e = (float)cut.max_e; a.v = u_uncut;
     a.dlogp = loss_sums ? dlogp : nullptr; a.drop_nonfinite = drop_nonfinite; a.partial = loss_sums ? partial : nullptr;
     const int L = getenv("BGK_ENERGY_STAGED") ? 0 : rows4_lanes(a.f, n_fields, (const float* const*)nullptr, (const int64_t*)nullptr);
     const int64_t n_tiles = L ? (B + NE_THREADS / L - 1) / (NE_THREADS / L) : (B + NE_ROWS - 1) / NE_ROWS;
@@ -303,7 +342,26 @@ extern "C" int bgk_energy_fields(const float* const* x, const int64_t* ldx, cons
     if (L) hipLaunchKernelGGL(energy_rows4_kernel, dim3(grid), dim3(NE_THREADS), 0, s, a, L);
     else hipLaunchKernelGGL(energy_fields_kernel, dim3(grid), dim3(NE_THREADS), 0, s, a);
     if (loss_sums) hipLaunchKernelGGL(energy_partial_reduce_kernel, dim3(1), dim3(64), 0, s, partial, grid, loss_sums);
-    return bgk_launch_status("bgk_energy_fields");
+    return bgk_launch_status(what);
+}
+
+extern "C" int bgk_energy_fields(const float* const* x, const int64_t* ldx, const int32_t* d, const int32_t* kind,
+                                 const float* const* param, const float* coef, int32_t n_fields, int64_t B,
+                                 double temperature, double c_in, double c_out, float* u,
+                                 const float* dlogp, int32_t drop_nonfinite, float* partial, int32_t nblk, double* loss_sums,
+                                 void* stream) {
+    return energy_fields_impl("bgk_energy_fields", x, ldx, d, kind, param, coef, n_fields, B, temperature, c_in, c_out, ECut{0, 0.0, 0.0}, u,
+                              nullptr, dlogp, drop_nonfinite, partial, nblk, loss_sums, stream);
+}
+
+extern "C" int bgk_energy_fields_cut(const float* const* x, const int64_t* ldx, const int32_t* d, const int32_t* kind,
+                                     const float* const* param, const float* coef, int32_t n_fields, int64_t B,
+                                     double temperature, double c_in, double c_out, int32_t cut, double high_energy, double max_energy,
+                                     float* u, float* u_uncut,
+                                     const float* dlogp, int32_t drop_nonfinite, float* partial, int32_t nblk, double* loss_sums,
+                                     void* stream) {
+    return energy_fields_impl("bgk_energy_fields_cut", x, ldx, d, kind, param, coef, n_fields, B, temperature, c_in, c_out,
+                              ECut{cut != 0, high_energy, max_energy}, u, u_uncut, dlogp, drop_nonfinite, partial, nblk, loss_sums, stream);
 }
 
 /* [sum, count] partials -> loss_sums [2] (f64, fixed order): shared with the KL epilogue of the training tail (bgk_tail.hip) */
@@ -312,37 +370,66 @@ int bgk_loss_partial_reduce(const float* partial, int n_partials, double* loss_s
     return bgk_launch_status("bgk_loss_partial_reduce");
 }
 
+static int energy_fields_backward_impl(const char* what, const float* const* x, const int64_t* ldx, const int32_t* d, const int32_t* kind,
+                                       const float* const* param, const float* coef, int32_t n_fields, int64_t B,
+                                       double temperature, ECut cut, const float* u_uncut, double clip, const int32_t* norm_dim,
+                                       const float* g_u,
+                                       const float* g_scalar, const float* u, const float* dlogp, int32_t drop_nonfinite, float* g_dlogp,
+                                       float* const* g_x, const int64_t* ldg, void* stream) {
+    BGK_CHECK_ARG(B >= 0 && temperature > 0.0 && g_x && ldg, "%s: bad arguments", what);
+    BGK_CHECK_ARG(g_u || (g_scalar && u && dlogp), "%s: need g_u [B] or (g_scalar, u, dlogp)", what);
+    BGK_CHECK_ARG(!cut.cut || (cut.high == cut.high && cut.max_e == cut.max_e), "%s: the cut's high / max energy must be numbers", what);
+    BGK_CHECK_ARG(!norm_dim || (clip == clip && clip >= 0.0), "%s: clip must be a non-negative number", what);
+    if (B == 0) return 0;
+    BGK_CHECK_ARG(!cut.cut || u_uncut, "%s: the cut's derivative needs the uncut energies", what);
+    EField tmp[NE_MAXF];
+    const int st = fill_fields(what, tmp, n_fields, x, ldx, d, kind, param, coef);
+    if (st) return st;
+    EBwdArgs a{};
+    int64_t total = 0;
+    bool quads = true;                  /* every clipped field's groups fit a lane's float4 */
+    for (int i = 0; i < n_fields; ++i) {
+        BGK_CHECK_ARG(!g_x[i] || ldg[i] >= d[i], "%s: field %d: gradient row stride", what, i);
+        const int nd = norm_dim ? norm_dim[i] : 0;
+        BGK_CHECK_ARG(nd == 0 || (nd >= 1 && d[i] % nd == 0), "%s: field %d: norm_dim %d does not divide the width %d (0 = unclipped)", what, i, nd, d[i]);
+        a.f[i] = EBwdField{tmp[i].x, tmp[i].ldx, tmp[i].p, g_x[i], ldg[i], tmp[i].d, tmp[i].kind, tmp[i].a, tmp[i].b, tmp[i].c, nd};
+        quads = quads && (nd == 0 || nd == 1 || nd == 2 || nd == 4);
+        total += (int64_t)d[i] * B;
+    }
+    a.n = n_fields; a.B = B; a.inv_t = (float)(1.0 / temperature);
+    a.g_u = g_u; a.g_scalar = g_scalar; a.u = u; a.dlogp = dlogp; a.drop_nonfinite = drop_nonfinite; a.g_dlogp = g_dlogp;
+    a.v = u_uncut; a.cut = cut.cut; a.high = (float)cut.high; a.max_e = (float)cut.max_e; a.clip = (float)clip;
+    const int L = (getenv("BGK_ENERGY_STAGED") || !quads) ? 0 : rows4_lanes(tmp, n_fields, (const float* const*)g_x, ldg);
+    if (L) {
+        const int64_t blocks = (B + NE_THREADS / L - 1) / (NE_THREADS / L);
+        const int grid = (int)(blocks < 256 * 16 ? blocks : 256 * 16);
+        hipLaunchKernelGGL(energy_rows4_bwd_kernel, dim3(grid), dim3(NE_THREADS), 0, (hipStream_t)stream, a, L);
+        return bgk_launch_status(what);
+    }
+    const int64_t blocks = (total + NE_THREADS * 4 - 1) / (NE_THREADS * 4);
+    const int grid = (int)(blocks < 256 * 16 ? (blocks < 1 ? 1 : blocks) : 256 * 16);
+    hipLaunchKernelGGL(energy_fields_bwd_kernel, dim3(grid), dim3(NE_THREADS), 0, (hipStream_t)stream, a);
+    return bgk_launch_status(what);
+}
+
 extern "C" int bgk_energy_fields_backward(const float* const* x, const int64_t* ldx, const int32_t* d, const int32_t* kind,
                                           const float* const* param, const float* coef, int32_t n_fields, int64_t B,
                                           double temperature, const float* g_u,
                                           const float* g_scalar, const float* u, const float* dlogp, int32_t drop_nonfinite, float* g_dlogp,
                                           float* const* g_x, const int64_t* ldg, void* stream) {
-    BGK_CHECK_ARG(B >= 0 && temperature > 0.0 && g_x && ldg, "bgk_energy_fields_backward: bad arguments");
-    BGK_CHECK_ARG(g_u || (g_scalar && u && dlogp), "bgk_energy_fields_backward: need g_u [B] or (g_scalar, u, dlogp)");
-    if (B == 0) return 0;
-    EField tmp[NE_MAXF];
-    const int st = fill_fields("bgk_energy_fields_backward", tmp, n_fields, x, ldx, d, kind, param, coef);
-    if (st) return st;
-    EBwdArgs a{};
-    int64_t total = 0;
-    for (int i = 0; i < n_fields; ++i) {
-        BGK_CHECK_ARG(!g_x[i] || ldg[i] >= d[i], "bgk_energy_fields_backward: field %d: gradient row stride", i);
-        a.f[i] = EBwdField{tmp[i].x, tmp[i].ldx, tmp[i].p, g_x[i], ldg[i], tmp[i].d, tmp[i].kind, tmp[i].a, tmp[i].b, tmp[i].c};
-        total += (int64_t)d[i] * B;
-    }
-    a.n = n_fields; a.B = B; a.inv_t = (float)(1.0 / temperature);
-    a.g_u = g_u; a.g_scalar = g_scalar; a.u = u; a.dlogp = dlogp; a.drop_nonfinite = drop_nonfinite; a.g_dlogp = g_dlogp;
-    const int L = getenv("BGK_ENERGY_STAGED") ? 0 : rows4_lanes(tmp, n_fields, (const float* const*)g_x, ldg);
-    if (L) {
-        const int64_t blocks = (B + NE_THREADS / L - 1) / (NE_THREADS / L);
-        const int grid = (int)(blocks < 256 * 16 ? blocks : 256 * 16);
-        hipLaunchKernelGGL(energy_rows4_bwd_kernel, dim3(grid), dim3(NE_THREADS), 0, (hipStream_t)stream, a, L);
-        return bgk_launch_status("bgk_energy_fields_backward");
-    }
-    const int64_t blocks = (total + NE_THREADS * 4 - 1) / (NE_THREADS * 4);
-    const int grid = (int)(blocks < 256 * 16 ? (blocks < 1 ? 1 : blocks) : 256 * 16);
-    hipLaunchKernelGGL(energy_fields_bwd_kernel, dim3(grid), dim3(NE_THREADS), 0, (hipStream_t)stream, a);
-    return bgk_launch_status("bgk_energy_fields_backward");
+    return energy_fields_backward_impl("bgk_energy_fields_backward", x, ldx, d, kind, param, coef, n_fields, B, temperature, ECut{0, 0.0, 0.0},
+                                       nullptr, 0.0, nullptr, g_u, g_scalar, u, dlogp, drop_nonfinite, g_dlogp, g_x, ldg, stream);
+}
+
+extern "C" int bgk_energy_fields_cut_backward(const float* const* x, const int64_t* ldx, const int32_t* d, const int32_t* kind,
+                                              const float* const* param, const float* coef, int32_t n_fields, int64_t B,
+                                              double temperature, int32_t cut, double high_energy, double max_energy, const float* u_uncut,
+                                              double clip, const int32_t* norm_dim, const float* g_u,
+                                              const float* g_scalar, const float* u, const float* dlogp, int32_t drop_nonfinite,
+                                              float* g_dlogp, float* const* g_x, const int64_t* ldg, void* stream) {
+    return energy_fields_backward_impl("bgk_energy_fields_cut_backward", x, ldx, d, kind, param, coef, n_fields, B, temperature,
+                                       ECut{cut != 0, high_energy, max_energy}, u_uncut, clip, norm_dim, g_u, g_scalar, u, dlogp, drop_nonfinite,
+                                       g_dlogp, g_x, ldg, stream);
 }
 
 /* the single-field forms of round 2 (ABI kept) */

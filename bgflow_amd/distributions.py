@@ -192,11 +192,151 @@ class _KLSumsFn(torch.autograd.Function):
                 *[t if t is not None else (torch.zeros_like(x) if nd else None) for t, x, nd in zip(gx, xs, need)])
 
 
+class _CutEnergyFieldsFn(torch.autograd.Function):
+    """``_EnergyFieldsFn`` with the robust-training wrappers folded in (bgk_energy_fields_cut / _cut_backward):
+    u = cut(sum_f e_f(x_f) + c_in) / T + c_out; the backward applies the cut's derivative and clips every field's final gradient.
+    wrap = (cut, clip): cut = (high, max) or None, clip = (threshold, norm_dim) or None"""
+
+    @staticmethod
+    def forward(ctx, specs, temperature, c_in, c_out, wrap, *xs):
+        from . import _lib
+        args, keep = _fields_args(specs, xs)
+        B, dev = xs[0].shape[0], xs[0].device
+        u = torch.empty(B, dtype=torch.float32, device=dev)
+        cut = wrap[0]
+        v = torch.empty(B, dtype=torch.float32, device=dev) if cut else None
+        with torch.cuda.device(dev):
+            st = _lib.lib().bgk_energy_fields_cut(*args, B, float(temperature), float(c_in), float(c_out), int(cut is not None),
+                                                  *(cut or (0.0, 0.0)), _lib.ptr(u), _lib.ptr(v), None, 0, None, 0, None, _lib.stream_ptr(dev))
+        _lib.check(st, "bgk_energy_fields_cut")
+        ctx.save_for_backward(*([] if v is None else [v]), *[t for t, _ in keep[0]])
+        ctx.cfg = (specs, float(temperature), wrap)
+        return u[:, None]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_u):
+        specs, temperature, wrap = ctx.cfg
+        saved = list(ctx.saved_tensors)
+        v = saved.pop(0) if wrap[0] else None
+        g = g_u.reshape(-1).to(torch.float32).contiguous()
+        gx = _cut_fields_backward(specs, temperature, wrap, v, saved, ctx.needs_input_grad[5:], g, None, None, None, False, None)
+        return (None, None, None, None, None, *gx)
+
+
+def _cut_fields_backward(specs, temperature, wrap, v, xs, need, g_u, g_scalar, u, dl, drop, g_dl):
+    """one launch of bgk_energy_fields_cut_backward (+ bgk_clip_gradient per field for a whole-tensor norm); returns the gradients of xs"""
+    import ctypes
+    from . import _lib
+    args, keep = _fields_args(specs, xs)
+    B, dev, n = xs[0].shape[0], xs[0].device, len(xs)
+    cut, clip = wrap
+    gx = [torch.empty_like(x, memory_format=torch.contiguous_format) if nd and sp[0] != 2 else None for x, nd, sp in zip(xs, need, specs)]
+    G = (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in gx])
+    LG = (ctypes.c_int64 * n)(*[0 if t is None else t.shape[1] for t in gx])
+    whole = clip is not None and clip[1] == -1
+    ND = None if clip is None or whole else (ctypes.c_int32 * n)(*[0 if sp[0] == 2 else clip[1] for sp in specs])
+    with torch.cuda.device(dev):
+        st = _lib.lib().bgk_energy_fields_cut_backward(*args, B, temperature, int(cut is not None), *(cut or (0.0, 0.0)), _lib.ptr(v),
+                                                       0.0 if clip is None else clip[0], ND, _lib.ptr(g_u), _lib.ptr(g_scalar), _lib.ptr(u),
+                                                       _lib.ptr(dl), int(drop), _lib.ptr(g_dl), G, LG, _lib.stream_ptr(dev))
+    _lib.check(st, "bgk_energy_fields_cut_backward")
+    if whole:
+        from .clipped import clip_launch
+        for t in gx:
+            if t is not None:
+                clip_launch(t, clip[0], -1, out=t)
+    return [t if t is not None else (torch.zeros_like(x) if nd else None) for t, x, nd in zip(gx, xs, need)]
+
+
+class _CutKLSumsFn(torch.autograd.Function):
+    """``_KLSumsFn`` for a wrapped target: the loss partial sums are formed on the cut energy inside bgk_energy_fields_cut"""
+
+    @staticmethod
+    def forward(ctx, specs, temperature, c_in, c_out, wrap, drop_nonfinite, dlogp, *xs):
+        from . import _lib
+        args, keep = _fields_args(specs, xs)
+        B, dev = xs[0].shape[0], xs[0].device
+        u = torch.empty(B, dtype=torch.float32, device=dev)
+        cut = wrap[0]
+        v = torch.empty(B, dtype=torch.float32, device=dev) if cut else None
+        dl = dlogp.detach().reshape(-1).to(torch.float32).contiguous()
+        nblk = 2048
+        partial = torch.empty((nblk, 2), dtype=torch.float32, device=dev)
+        sums = torch.empty(2, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            st = _lib.lib().bgk_energy_fields_cut(*args, B, float(temperature), float(c_in), float(c_out), int(cut is not None),
+                                                  *(cut or (0.0, 0.0)), _lib.ptr(u), _lib.ptr(v), _lib.ptr(dl), int(bool(drop_nonfinite)),
+                                                  _lib.ptr(partial), nblk, _lib.ptr(sums), _lib.stream_ptr(dev))
+        _lib.check(st, "bgk_energy_fields_cut")
+        ctx.save_for_backward(u, dl, *([] if v is None else [v]), *[t for t, _ in keep[0]])
+        ctx.cfg = (specs, float(temperature), wrap, bool(drop_nonfinite), dlogp.shape)
+        u2 = u[:, None]
+        ctx.mark_non_differentiable(u2)
+        return sums, u2
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_sums, _g_u):
+        specs, temperature, wrap, drop, dl_shape = ctx.cfg
+        u, dl, *saved = ctx.saved_tensors
+        v = saved.pop(0) if wrap[0] else None
+        gs = g_sums[0:1].to(torch.float32).contiguous()
+        g_dl = torch.empty(u.shape[0], dtype=torch.float32, device=u.device) if ctx.needs_input_grad[6] else None
+        gx = _cut_fields_backward(specs, temperature, wrap, v, saved, ctx.needs_input_grad[7:], None, gs, u, dl, drop, g_dl)
+        return (None, None, None, None, None, None, None if g_dl is None else g_dl.reshape(dl_shape), *gx)
+
+
+def _own_methods(obj, cls):
+    """``obj`` evaluates its energy with the code of ``cls`` (no subclass override of ``energy`` / ``_energy``)"""
+    return all(getattr(type(obj), name, None) is getattr(cls, name) for name in ("energy", "_energy"))
+
+
+def _wrapper_plan(dist, temperature):
+    """plan of a chain of at most one LinLogCutEnergy and at most one GradientClippedEnergy (either order) around a distribution with
+    kernel fields: (specs, dims, c_in, 0.0, T, (cut, clip)), or None.  The wrappers evaluate their delegate WITHOUT the temperature
+    and divide the (cut) result by it (energy/base.py:124-146), so the delegate's plan is taken at T = 1 and BOTH its constants sit
+    inside the cut and the division: u = cut(sum_f e_f + c_in(1) + c_out(1)) / T -- the value of the wrapper chain."""
+    from . import clipped
+    if not (isinstance(temperature, (int, float)) and temperature > 0):
+        return None
+    cut = clip = None
+    node = dist
+    while isinstance(node, (clipped.LinLogCutEnergy, clipped.GradientClippedEnergy)):
+        if isinstance(node, clipped.LinLogCutEnergy):
+            if cut is not None or not _own_methods(node, clipped.LinLogCutEnergy):
+                return None
+            if not all(isinstance(t, (int, float)) for t in (node.high_energy, node.max_energy)):
+                return None
+            cut = (float(node.high_energy), float(node.max_energy))
+        else:
+            c = node.clipping
+            if clip is not None or not _own_methods(node, clipped.GradientClippedEnergy) or type(c) is not clipped.ClipGradient:
+                return None
+            if c._clip_host is None or not isinstance(c.norm_dim, int):
+                return None
+            clip = (c._clip_host, int(c.norm_dim))
+        node = node.delegate
+    base = _kernel_plan(node, 1.0)
+    if base is None or len(base) != 5:
+        return None
+    specs, dims, c_in, c_out, _ = base
+    if clip is not None and clip[1] != -1 and (clip[1] < 1 or any(d % clip[1] for d in dims)):
+        return None                      # (the wrappers' own code raises the ValueError that names the limit)
+    return specs, dims, c_in + c_out, 0.0, float(temperature), (cut, clip)
+
+
 def _kernel_plan(dist, temperature):
     """``dist._kernel_fields(temperature)`` -- unless a subclass overrides ``energy`` / ``_energy`` of the class that describes the
-    kernel fields: such an override (a custom target, a clipped or regularised energy) must run through its own code"""
+    kernel fields: such an override (a custom target, a clipped or regularised energy) must run through its own code.  The package's
+    own wrappers (clipped.LinLogCutEnergy / GradientClippedEnergy) around such a distribution give a plan of SIX entries, the last
+    one the wrappers' settings (``_wrapper_plan``); callers that cannot fold them in treat a plan of another length than 5 as None."""
     describe = getattr(dist, "_kernel_fields", None)
     if describe is None:
+        if hasattr(dist, "delegate"):
+            from . import clipped
+            if isinstance(dist, (clipped.LinLogCutEnergy, clipped.GradientClippedEnergy)):
+                return _wrapper_plan(dist, temperature)
         return None
     owner = next(c for c in type(dist).__mro__ if "_kernel_fields" in c.__dict__)
     for name in ("energy", "_energy"):
@@ -211,22 +351,27 @@ def kernel_energy(dist, xs, temperature=1.0):
     plan = _kernel_plan(dist, temperature)
     if plan is None:
         return None
-    specs, dims, c_in, c_out, t_eff = plan
+    specs, dims, c_in, c_out, t_eff, *wrap = plan
     if not (_fields_ok(xs, dims) and isinstance(temperature, (int, float)) and temperature > 0):
         return None
+    if wrap:
+        return _CutEnergyFieldsFn.apply(specs, t_eff, c_in, c_out, wrap[0], *xs)
     return _EnergyFieldsFn.apply(specs, t_eff, c_in, c_out, *xs)
 
 
 def kl_loss_sums(target, xs, dlogp, temperature=1.0, drop_nonfinite=False):
     """(sums, u): sums = f64 [2] = [sum_b (u_target(x_b) - dlogp_b), samples kept] with autograd to x and dlogp, formed inside the
-    target-energy kernel (no per-sample loss tensor, no isfinite / where / sum launches); None if the target has no kernel fields"""
+    target-energy kernel (no per-sample loss tensor, no isfinite / where / sum launches); None if the target has no kernel fields.
+    A target wrapped in clipped.LinLogCutEnergy / GradientClippedEnergy takes the same path on bgk_energy_fields_cut."""
     plan = _kernel_plan(target, temperature)
     if plan is None:
         return None
-    specs, dims, c_in, c_out, t_eff = plan
+    specs, dims, c_in, c_out, t_eff, *wrap = plan
     if not (_fields_ok(xs, dims) and isinstance(temperature, (int, float)) and temperature > 0 and torch.is_tensor(dlogp)
             and dlogp.is_cuda and dlogp.numel() == xs[0].shape[0]):
         return None
+    if wrap:
+        return _CutKLSumsFn.apply(specs, t_eff, c_in, c_out, wrap[0], bool(drop_nonfinite), dlogp, *xs)
     return _KLSumsFn.apply(specs, t_eff, c_in, c_out, bool(drop_nonfinite), dlogp, *xs)
 
 
@@ -608,7 +753,7 @@ class ProductDistribution(Energy, Sampler, _FusedSampling):
         specs, dims, c_in = [], [], 0.0
         for c in self._components:
             plan = _kernel_plan(c, 1.0)
-            if plan is None or len(plan[0]) != 1:
+            if plan is None or len(plan) != 5 or len(plan[0]) != 1:       # (a wrapped component runs through its own code)
                 return None
             specs.append(plan[0][0]); dims.append(plan[1][0])
             c_in += plan[2] + plan[3]                       # the component's constants belong inside the division by T

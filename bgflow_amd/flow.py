@@ -172,7 +172,7 @@ class SequentialFlow(Flow):
         if not isinstance(tail, _FusedGenerationTail):
             return None
         plan = _kernel_plan(target, temperature)
-        if plan is None:
+        if plan is None or len(plan) != 5:        # (a target wrapped in a cut / a gradient clip: the tail's launch, then the energy launch)
             return None
         specs, dims, c_in, c_out, t_eff = plan
         ic = tail._ic

@@ -131,10 +131,20 @@ def _bump_versions(params):
 
 
 class FlatAdam(torch.optim.Optimizer):
-    """Adam (torch.optim.Adam semantics: lr, betas, eps, L2 weight_decay) over one flat f32 bucket on a HIP device."""
+    """Adam (torch.optim.Adam semantics: lr, betas, eps, L2 weight_decay) over one flat f32 bucket on a HIP device.
 
-    def __init__(self, params, lr=5e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    ``max_grad_norm`` (None: off): ``step()`` clips the total 2-norm of the gradient like
+    ``torch.nn.utils.clip_grad_norm_(params, max_grad_norm)`` in front of the update -- the norm of the whole bucket in one pass
+    (bgk_grad_norm_flag, after ``allreduce_gradients()``: the global gradient under data parallelism), the coefficient
+    min(1, max / (norm + 1e-6)) formed and applied inside the Adam launch (bgk_adam_step_clipped), no host read.  The bucket itself
+    stays unscaled.  Deviation from torch: a non-finite norm (an inf or NaN gradient) skips the step and counts it, like a NaN
+    gradient does without clipping -- torch would write NaN into every parameter."""
+
+    def __init__(self, params, lr=5e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
         params = [p for p in params]
+        if max_grad_norm is not None and not (float(max_grad_norm) >= 0.0):
+            raise ValueError("FlatAdam: max_grad_norm is None or a non-negative number")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         ps = [p for g in self.param_groups for p in g["params"] if p.requires_grad]
         assert ps and all(p.is_cuda and p.dtype == torch.float32 for p in ps), "FlatAdam: f32 parameters on a HIP device"
@@ -149,6 +159,8 @@ class FlatAdam(torch.optim.Optimizer):
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
         self._flag = torch.zeros(1, dtype=torch.int32, device=dev)
         self._skipped = torch.zeros(1, dtype=torch.int32, device=dev)
+        if self.max_grad_norm is not None:      # [1024 block partials, sum of squares] of bgk_grad_norm_flag
+            self._norm_ws = torch.zeros(1025, dtype=torch.float64, device=dev)
         self._step = 0
         self.generation = 0          # number of updates this optimizer has written through the bucket
         off = 0
@@ -205,14 +217,21 @@ class FlatAdam(torch.optim.Optimizer):
         self._step += 1
         lib = _lib.lib()
         dev = self.flat.device
+        flag = _lib.ptr(self._flag) if skip_on_nan else None
+        adam = (_lib.ptr(self.flat), _lib.ptr(self.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), self.flat.numel(), float(g["lr"]),
+                float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self._step, flag, _lib.ptr(self._skipped))
         with torch.cuda.device(dev):
-            if skip_on_nan:
-                _lib.check(lib.bgk_grad_nan_flag(_lib.ptr(self.grad), self.grad.numel(), _lib.ptr(self._flag), _lib.stream_ptr(dev)),
-                           "bgk_grad_nan_flag")
-            _lib.check(lib.bgk_adam_step(_lib.ptr(self.flat), _lib.ptr(self.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
-                                         self.flat.numel(), float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-                                         float(g["weight_decay"]), self._step, _lib.ptr(self._flag) if skip_on_nan else None,
-                                         _lib.ptr(self._skipped), _lib.stream_ptr(dev)), "bgk_adam_step")
+            if self.max_grad_norm is not None:
+                # the scan that gives the norm gives the flag too (a non-finite norm sets it); skip_on_nan=False ignores it
+                ws = self._norm_ws
+                _lib.check(lib.bgk_grad_norm_flag(_lib.ptr(self.grad), self.grad.numel(), _lib.ptr(self._flag), _lib.ptr(ws), 1024,
+                                                  _lib.ptr(ws[1024:]), _lib.stream_ptr(dev)), "bgk_grad_norm_flag")
+                _lib.check(lib.bgk_adam_step_clipped(*adam, _lib.ptr(ws[1024:]), self.max_grad_norm, _lib.stream_ptr(dev)), "bgk_adam_step_clipped")
+            else:
+                if skip_on_nan:
+                    _lib.check(lib.bgk_grad_nan_flag(_lib.ptr(self.grad), self.grad.numel(), _lib.ptr(self._flag), _lib.stream_ptr(dev)),
+                               "bgk_grad_nan_flag")
+                _lib.check(lib.bgk_adam_step(*adam, _lib.stream_ptr(dev)), "bgk_adam_step")
         # the kernel wrote through the bucket, which torch's version counters do not see: bump them by hand -- caches keyed on
         # ``_version`` (UniformDistribution._const_host, user code) and autograd's saved-tensor check (a backward through a graph
         # retained across this step raises instead of silently using the new weights) then see the update like any in-place op --
@@ -226,6 +245,13 @@ class FlatAdam(torch.optim.Optimizer):
         dense.repack_training_plans(self._param_ids)
         dense.repack_affine_training_plans(self._param_ids)
 
+    def last_grad_norm(self):
+        """total 2-norm of the gradient the last ``step()`` saw (before clipping), as a device scalar: formed from the kernel's sum of
+        squares only when asked for, and no host sync unless the caller reads it.  Needs ``max_grad_norm``."""
+        if self.max_grad_norm is None:
+            raise RuntimeError("FlatAdam.last_grad_norm: the norm is only formed with max_grad_norm set")
+        return self._norm_ws[1024].sqrt().to(torch.float32)
+
     def skipped_steps(self):
         """number of optimizer steps skipped because a gradient was NaN (host sync)"""
         return int(self._skipped.item())
@@ -235,7 +261,7 @@ class FlatAdam(torch.optim.Optimizer):
         ``Optimizer.state``: one tensor per moment, not one per parameter)"""
         sd = super().state_dict()
         sd["flat_adam"] = dict(exp_avg=self.exp_avg.detach().clone(), exp_avg_sq=self.exp_avg_sq.detach().clone(),
-                               step=int(self._step), skipped=int(self._skipped.item()))
+                               step=int(self._step), skipped=int(self._skipped.item()), max_grad_norm=self.max_grad_norm)
         return sd
 
     def load_state_dict(self, state_dict):
@@ -250,6 +276,10 @@ class FlatAdam(torch.optim.Optimizer):
         self.exp_avg_sq.copy_(extra["exp_avg_sq"].to(self.exp_avg_sq.device))
         self._step = int(extra["step"])
         self._skipped.fill_(int(extra["skipped"]))
+        if "max_grad_norm" in extra and extra["max_grad_norm"] != self.max_grad_norm:     # (checkpoints written before the option: keep ours)
+            if (extra["max_grad_norm"] is None) != (self.max_grad_norm is None):
+                raise ValueError("FlatAdam.load_state_dict: the checkpoint and this optimizer disagree on whether max_grad_norm is set")
+            self.max_grad_norm = float(extra["max_grad_norm"])
 
 
 class KLTrainer(object):

@@ -605,6 +605,16 @@ int bgk_dense_backward_dx(const float* g, int64_t ldg, int32_t P, const float* z
 int bgk_grad_nan_flag(const float* g, int64_t n, int32_t* flag, void* stream);
 int bgk_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                   float weight_decay, int64_t step, const int32_t* skip_flag, int32_t* skipped_count, void* stream);
+/* Norm clipping of the bucket's gradient (replaces torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type=2) in front of the
+ * optimizer step of trainers.py:198-201; the reference itself has no norm clipping of parameter gradients):
+ * bgk_grad_norm_flag is bgk_grad_nan_flag that also writes grad_sumsq[0] = sum_i g_i^2 (double; block partials into
+ * partial[nblk] doubles, every sum in a fixed order) and sets the flag for a non-finite sum too; n == 0 writes 0.
+ * bgk_adam_step_clipped is bgk_adam_step on coef * g with coef = min(1, max_norm / (sqrt(grad_sumsq[0]) + 1e-6)) formed on the
+ * device; g itself is not modified. */
+int bgk_grad_norm_flag(const float* g, int64_t n, int32_t* flag, double* partial, int32_t nblk, double* grad_sumsq, void* stream);
+int bgk_adam_step_clipped(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, int64_t step, const int32_t* skip_flag, int32_t* skipped_count,
+                          const double* grad_sumsq, float max_norm, void* stream);
 
 /* Energy of the isotropic, optionally shifted normal distribution (bgflow/distribution/normal.py:61-72, NormalDistribution._energy
  * without `cov`; the target end of the KL integrand u(F(z)) - log|det J|, bgflow/bg.py:13-17, for the synthetic Gaussian targets,
@@ -639,6 +649,38 @@ int bgk_energy_fields_backward(const float* const* x, const int64_t* ldx, const 
                                double temperature, const float* g_u,
                                const float* g_scalar, const float* u, const float* dlogp, int32_t drop_nonfinite, float* g_dlogp,
                                float* const* g_x, const int64_t* ldg, void* stream);
+
+/* The same two launches with the robust-training wrappers folded in: LinLogCutEnergy and GradientClippedEnergy
+ * (bgflow/distribution/energy/clipped.py:8-38) around a delegate described by fields.
+ * bgk_energy_fields_cut: u[b] = cut(sum_f e_f(x_f[b]) + c_in) / temperature + c_out, cut = linlogcut(., high_energy, max_energy)
+ *   (bgflow/utils/train.py:60-62) if `cut` != 0, else the identity.  The wrappers evaluate their delegate at T = 1 and divide the
+ *   result by the temperature (energy/base.py:124-146), so the caller passes the delegate's constants of T = 1, both inside (c_in),
+ *   and c_out = 0.  u_uncut [B] (may be NULL) receives sum_f e_f + c_in, which the backward needs.  Loss sums as above (on the cut u).
+ * bgk_energy_fields_cut_backward: g_x_f = clip_f( g_row cut'(u_uncut[b]) (de_f / dx) / temperature ), cut' = 1 below high_energy,
+ *   1 / (1 + u_uncut - high_energy) above, 0 where the clamp is active; clip_f = ClipGradient.clip_tensor (train.py:107-118) with the
+ *   scalar `clip` over groups of norm_dim[f] consecutive elements of a row (HOST array; norm_dim[f] must divide d[f]; 0 = this field
+ *   is not clipped, norm_dim == NULL = none is).  A whole-tensor norm (norm_dim -1) is bgk_clip_gradient on the unclipped result. */
+int bgk_energy_fields_cut(const float* const* x, const int64_t* ldx, const int32_t* d, const int32_t* kind,
+                          const float* const* param, const float* coef, int32_t n_fields, int64_t B,
+                          double temperature, double c_in, double c_out, int32_t cut, double high_energy, double max_energy,
+                          float* u, float* u_uncut,
+                          const float* dlogp, int32_t drop_nonfinite, float* partial, int32_t nblk, double* loss_sums, void* stream);
+int bgk_energy_fields_cut_backward(const float* const* x, const int64_t* ldx, const int32_t* d, const int32_t* kind,
+                                   const float* const* param, const float* coef, int32_t n_fields, int64_t B,
+                                   double temperature, int32_t cut, double high_energy, double max_energy, const float* u_uncut,
+                                   double clip, const int32_t* norm_dim, const float* g_u,
+                                   const float* g_scalar, const float* u, const float* dlogp, int32_t drop_nonfinite,
+                                   float* g_dlogp, float* const* g_x, const int64_t* ldg, void* stream);
+
+/* ClipGradient.clip_tensor (bgflow/utils/train.py:107-118) of a gradient g [B, D] (row stride ldg) into out (row stride ldo; out == g
+ * allowed): NaN -> 0 and +-inf -> +-FLT_MAX (torch.nan_to_num), then every group of norm_dim consecutive elements of a row is scaled by
+ * min(clip / |group|_2, 1).  norm_dim must divide D; norm_dim = -1 is ONE norm over the whole tensor (two launches; workspace: nblk + 1
+ * doubles, block partial sums of squares reduced in a fixed order; workspace[nblk] receives the norm).  An f32 sum of squares that
+ * overflows gives the factor 0, like the reference.  `clip` is a scalar (the reference's tensor-valued clip is not provided).
+ * bgk_linlogcut: out[i] = linlogcut(v[i], high, max_val) (train.py:60-62), or, with g != NULL, g[i] * d linlogcut / d v (v[i]). */
+int bgk_clip_gradient(const float* g, int64_t ldg, int64_t B, int32_t D, double clip, int32_t norm_dim,
+                      float* out, int64_t ldo, double* workspace, int32_t nblk, void* stream);
+int bgk_linlogcut(const float* v, const float* g, int64_t n, double high, double max_val, float* out, void* stream);
 
 /* Prior sampling in one launch from a counter-based generator (Philox4x32-10; counter = (global row, field, 4-column block, offset),
  * key = seed: independent of launch geometry and of the sharding of a batch, row0 = first global row of this launch), replacing
