@@ -14,6 +14,7 @@ from .ic import *            # noqa: F401,F403
 from .distributions import * # noqa: F401,F403
 from .cdf import *           # noqa: F401,F403
 from .modulo import *        # noqa: F401,F403
+from .moments import *       # noqa: F401,F403
 from .bg import *            # noqa: F401,F403
 from .factory import *       # noqa: F401,F403
 from .training import *      # noqa: F401,F403

@@ -116,6 +116,8 @@ _SIGNATURES = {
     "bgk_pack_dense_h2_t_many": (ctypes.c_int, [i32] + [vp] * 9 + [vp]),
     "bgk_column_sum": (ctypes.c_int, [vp, i64, i64, i32, vp, i32, vp, vp]),
     "bgk_absmax": (ctypes.c_int, [vp, i64, i64, i32, vp, vp]),
+    "bgk_column_moments_update": (ctypes.c_int, [vp, i64, i64, i32, vp, i32, vp, vp]),
+    "bgk_column_moments_finalize": (ctypes.c_int, [vp, i32, i64, vp, vp]),
     "bgk_whiten": (ctypes.c_int, [vp, i64, vp, vp, vp, i32, i32, i64, vp, i64, vp]),
     "bgk_normal_energy": (ctypes.c_int, [vp, i64, vp, i32, i64, f64, f64, vp, vp]),
     "bgk_normal_energy_backward": (ctypes.c_int, [vp, i64, vp, i32, i64, f64, vp, vp, i64, vp]),

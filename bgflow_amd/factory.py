@@ -3,11 +3,11 @@
 Pure host-side Python -- no kernels.  It emits exactly the blocks of bgflow_amd.flow / transformer / dense / ic / cdf that the
 hot path accelerates, with the reference builder's block order, tensor slots and parameter names
 (factory/generator_builder.py:108-459, tensor_info.py:17-371, conditioner_factory.py:23-80,230-251,
-transformer_factory.py:15-43, distribution_factory.py:10-57, icmarginals.py:14-77), so a script written against
+transformer_factory.py:15-43, distribution_factory.py:10-57, icmarginals.py:14-163), so a script written against
 ``bgflow.BoltzmannGeneratorBuilder`` runs unchanged and checkpoints line up.  Covered: dense conditioners, spline and affine
-transformers, split / merge / set-constant / arbitrary layers, the default IC marginals, Relative / Mixed / Global coordinate
-transforms, constraint merging, chirality / torsion-multiplicity / torsion-shift helpers.  Not covered (out of the hot path's
-scope, raise NotImplementedError): GNN conditioners.
+transformers, split / merge / set-constant / arbitrary layers, the default and the data-informed IC marginals, Relative / Mixed /
+Global coordinate transforms, constraint merging, chirality / torsion-multiplicity / torsion-shift helpers.  Not covered (out of the
+hot path's scope, raise NotImplementedError): GNN conditioners.
 """
 import warnings
 from collections import OrderedDict, namedtuple
@@ -23,6 +23,7 @@ from .distributions import (NormalDistribution, ProductDistribution, SloppyUnifo
 from .flow import CouplingFlow, Flow, InverseFlow, MergeFlow, SequentialFlow, SetConstantFlow, SplitFlow, WrapFlow
 from .ic import GlobalInternalCoordinateTransformation
 from .modulo import CircularShiftFlow, IncreaseMultiplicityFlow, TorchTransform
+from .moments import ColumnMoments
 from .transformer import AffineTransformer, ConditionalSplineTransformer
 
 __all__ = ["TensorInfo", "ShapeDictionary", "BONDS", "ANGLES", "TORSIONS", "FIXED", "ORIGIN", "ROTATION", "AUGMENTED", "TARGET",
@@ -253,7 +254,8 @@ class _NormalMarginal(torch.nn.Module):
 
 
 class InternalCoordinateMarginals(dict):
-    """Default marginal distributions whose inverse CDFs map the unit cube onto the IC domains (icmarginals.py:14-77)."""
+    """Marginal distributions whose inverse CDFs map the unit cube onto the IC domains: field-uniform defaults, or per-channel ones
+    fitted to data / a force field (icmarginals.py:14-163)."""
 
     def __init__(self, current_dims, ctx, bond_mu=1.0, bond_sigma=1.0, bond_lower=1e-5, bond_upper=np.inf,
                  angle_mu=0.5, angle_sigma=1.0, angle_lower=1e-5, angle_upper=1.0, torsion_lower=0.0, torsion_upper=1.0,
@@ -274,6 +276,67 @@ class InternalCoordinateMarginals(dict):
             self[fixed] = _NormalMarginal(torch.zeros(current_dims[fixed], **ctx), full(fixed, fixed_scale))
         if augmented in current_dims:
             self[augmented] = _NormalMarginal(torch.zeros(current_dims[augmented], **ctx), full(augmented, 1.0))
+
+    def inform_with_force_field(self, system, coordinate_transform, temperature, bonds=BONDS, angles=ANGLES, torsions=None):
+        """Marginals estimated from the force field's bond / angle / torsion terms by bgmol (icmarginals.py:82-104)."""
+        import bgmol
+        if bonds in self.current_dims:
+            self[bonds] = bgmol.bond_marginal_estimate(system, coordinate_transform, temperature, **self.ctx)
+        if angles in self.current_dims:
+            self[angles] = bgmol.angle_marginal_estimate(system, coordinate_transform, temperature, **self.ctx)
+        if torsions in self.current_dims:
+            cdf = bgmol.torsion_marginal_cdf_estimate(system, coordinate_transform, temperature, **self.ctx)
+            self[torsions] = InverseFlow(cdf)
+
+    def inform_with_data(self, data, coordinate_transform, bond_lower=0.01, bond_upper=1, angle_lower=0.01, angle_upper=1.0,
+                         torsion_lower=0.0, torsion_upper=1.0, constrained_bond_indices=None, bonds=BONDS, angles=ANGLES,
+                         torsions=None, broadening=1, *, batch_size=None):
+        """Truncated-normal marginals with the per-channel mean and (``broadening`` x) standard deviation of the data's internal
+        coordinates (icmarginals.py:106-163).  The statistics are one pass of ``ColumnMoments`` per field (bgk_column_moments_update
+        on HIP tensors; f64 sums) instead of min / max / mean / std passes; the six range checks read ONE host copy of the
+        finalized statistics.  ``batch_size`` (keyword only, not in the reference): the frames go through ``coordinate_transform``
+        in chunks of that many rows and the statistics stream, for data sets whose ICs do not fit in memory at once."""
+        fields = [(bonds, bond_lower, bond_upper), (angles, angle_lower, angle_upper), (torsions, torsion_lower, torsion_upper)]
+        n_frames = len(data)
+        step = max(1, n_frames if batch_size is None else int(batch_size))
+        moments, dtype = None, None
+        with torch.no_grad():
+            for start in range(0, max(n_frames, 1), step):
+                values = coordinate_transform.forward(data[start:start + step])[:3]
+                if moments is None:
+                    moments = [ColumnMoments(v.shape[-1], v.device) if f in self.current_dims else None
+                               for (f, _, _), v in zip(fields, values)]
+                    dtype = values[0].dtype
+                for m, v in zip(moments, values):
+                    if m is not None:
+                        m.update(v.reshape(-1, v.shape[-1]))
+            stats = [None if m is None else m.result() for m in moments]
+            present = [s for s in stats if s is not None]
+            if not present:
+                return
+            host = torch.stack([torch.stack([s.min.min(), s.max.max()]) for s in present]).cpu().numpy()    # the one host read
+        ctx = {"device": self.ctx.get("device"), "dtype": self.ctx.get("dtype") or dtype}
+        at = 0
+        for k, ((field, lower, upper), s) in enumerate(zip(fields, stats)):
+            if s is None:
+                continue
+            lowest, highest = host[at]
+            at += 1
+            name = ("bond", "angle", "torsion")[k]
+            if k < 2:       # bonds and angles: strict; all columns, constrained bonds included (the reference asserts first)
+                assert lower < lowest, f"Set a smaller {name}_lower"
+                assert upper > highest, f"Set a larger {name}_upper"
+            else:
+                assert lower <= lowest, f"Set a smaller {name}_lower"
+                assert upper >= highest, f"Set a larger {name}_upper"
+            mu, sigma = s.mean, s.std
+            if k == 0 and constrained_bond_indices is not None:
+                keep = torch.as_tensor(np.array([i for i in range(len(mu)) if i not in constrained_bond_indices], dtype=np.int64),
+                                       device=mu.device)
+                mu, sigma = mu[keep], sigma[keep]
+            self[field] = TruncatedNormalDistribution(mu=mu.to(**ctx), sigma=(broadening * sigma).to(**ctx),
+                                                      lower_bound=torch.as_tensor(lower, **ctx),
+                                                      upper_bound=torch.as_tensor(upper, **ctx))
 
 
 # ---- the builder ----------------------------------------------------------------------------------------------------

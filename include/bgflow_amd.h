@@ -843,6 +843,21 @@ int bgk_column_sum(const float* x, int64_t ldx, int64_t B, int32_t P, float* par
  * kernel of this library (those publish their own maximum: the g_absmax / gz_absmax arguments below). */
 int bgk_absmax(const float* x, int64_t ldx, int64_t B, int32_t P, float* out, void* stream);
 
+/* Column statistics of a tall row-major f32 matrix x [B, P] (row stride ldx >= P, so a column slice of a wider buffer works) in one
+ * pass: replaces `values.min/max/mean/std(axis=0)` of `factory/icmarginals.py:126-157`.  The running state is a caller-owned f64
+ * buffer state [P, 6] = {n, K, S1, S2, min, max} per column -- S1 = sum(x - K), S2 = sum((x - K)^2), K a value of the column --
+ * zero-filled before the first chunk; bgk_column_moments_update merges one chunk into it (under the state's K; min / max are
+ * merged), so a data set larger than memory is reduced chunk by chunk.  partial: workspace of nblk * P * 6 doubles (nblk row
+ * blocks; the partition and every merge order are fixed: two calls on the same input with the same nblk give the same bits; no
+ * atomics).  B == 0: a no-op.  f64 accumulation; every element of x is read once.
+ * bgk_column_moments_finalize writes out [5, P] = count, mean, unbiased std (divisor n - 1: NaN for n = 1, exactly 0 for a constant
+ * column), min, max in f64.  n_rows: the number of rows the caller has merged into the state (the state's own n stays on the
+ * device); n_rows == 0 is an error (BGK_EINVAL, text in bgk_last_error).  A NaN in the data reaches the statistics of its own
+ * column only (min and max included, as torch.min / torch.max). */
+int bgk_column_moments_update(const float* x, int64_t ldx, int64_t B, int32_t P, double* partial, int32_t nblk,
+                              double* state, void* stream);
+int bgk_column_moments_finalize(const double* state, int32_t P, int64_t n_rows, double* out, void* stream);
+
 /* One Linear layer (+ bias + activation) of a conditioner network on its own: y = act(x W^T + b).
  * Replaces one `Linear (, activation)` pair of DenseNet._layers (nn/dense.py:30-48) for the networks the one-launch coupling kernels do
  * not take (conditioner_factory.py:76-80 allows any `hidden` tuple: other depths, layers wider than 256; README.md:72-79's [1, 4, 1]
