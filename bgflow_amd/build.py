@@ -12,6 +12,8 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+from ._abi import HEADER, abi_signatures       # the one parse of include/bgflow_amd.h
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
@@ -36,14 +38,9 @@ TU_FLAGS = {"bgk_fused2.hip": ["-fno-slp-vectorize"], "bgk_fused2_train.hip": ["
 INCLUDES_SOURCE = {"bgk_fused2_train.hip": ["bgk_fused2.hip"], "bgk_fused2_bf16.hip": ["bgk_fused2.hip"], "bgk_fused2_afftrain.hip": ["bgk_fused2.hip"]}     # translation units that #include another .hip
 
 
-HEADER = os.path.join(HERE, "..", "include", "bgflow_amd.h")
-
-
 def abi_symbols(header=HEADER):
     """names of the C-ABI prototypes declared in include/bgflow_amd.h -- the library's export list"""
-    import re
-    text = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    return sorted(set(re.findall(r"^[A-Za-z_][\w \t\*]*?\b(bgk_\w+)\s*\(", text, flags=re.M)))
+    return sorted(abi_signatures(header))
 
 
 def _export_map():

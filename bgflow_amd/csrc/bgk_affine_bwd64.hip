@@ -52,21 +52,6 @@ struct Bwd64Args {
 };
 constexpr int FWB = 12 + 18 + 9;   /* forward operand blocks in LDS (RECOMP): A0 (<= 3 k-steps x 2 tiles x {hi, lo}), A1 (4 x 2 x 2 + 2 bias), A2 (4 x 1 x 2 + 1) */
 
-/* tanh of the scale network's OUTPUT (log sigma): the form of the forward kernels (bgk_affine_fwd64.hip::f64_tanh_out) */
-__device__ __forceinline__ float q_tanh_out(float x) {
-    const float ax = __builtin_fabsf(x);
-    const float dn = 1.0f + __builtin_amdgcn_exp2f(ax * 2.88539008177792681f);
-    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, bgk_rcp_sat(dn), 1.0f), x);
-    const float z = x * x;
-    float p = -5.70498872745e-3f;
-    p = __builtin_fmaf(p, z, 2.06390887954e-2f);
-    p = __builtin_fmaf(p, z, -5.37397155531e-2f);
-    p = __builtin_fmaf(p, z, 1.33314422036e-1f);
-    p = __builtin_fmaf(p, z, -3.33332819422e-1f);
-    const float small = __builtin_fmaf(p * z, x, x);
-    return ax >= 0.625f ? big : small;
-}
-
 /* d = g * act'(z), h = act(z) for a pair (hardware exp / rcp; the forms of bgk_dense_backward_dx) */
 __device__ __forceinline__ void q_act_grad2(int act, bgk_f2 z, bgk_f2 g, bgk_f2& gz, bgk_f2& h) {
     if (act == 1) {
@@ -402,7 +387,7 @@ __global__ __launch_bounds__(QW * 64, BGK_BWD64_OCC) void affine_net_bwd64_kerne
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const bool in = (r & 3) + 8 * (r >> 2) + 4 * hh < d;
-                const float th = q_tanh_out(sraw[r]);
+                const float th = bgk_tanh_out(sraw[r]);
                 const float ex = __builtin_amdgcn_exp2f((INVERSE ? -th : th) * alpha * 1.44269504088896341f);
                 gy[r] = gv[r] * ex;
                 /* forward: out = y e^s + mu, dlogp = sum s;  inverse: out = (y - mu) e^-s, dlogp = - sum s, and (y - mu) e^-s IS the output (yv) */

@@ -35,21 +35,6 @@ struct Fwd64Args {
     int vec_y, vec_o;                       /* rows of y / out start on 16-byte boundaries (float4 accesses) */
 };
 
-/* tanh of the OUTPUT layer (log sigma): the form of the other fused affine kernels (bgk_fused2.hip::aff_tanh_out) */
-__device__ __forceinline__ float f64_tanh_out(float x) {
-    const float ax = __builtin_fabsf(x);
-    const float dn = 1.0f + __builtin_amdgcn_exp2f(ax * 2.88539008177792681f);
-    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, bgk_rcp_sat(dn), 1.0f), x);
-    const float z = x * x;
-    float p = -5.70498872745e-3f;
-    p = __builtin_fmaf(p, z, 2.06390887954e-2f);
-    p = __builtin_fmaf(p, z, -5.37397155531e-2f);
-    p = __builtin_fmaf(p, z, 1.33314422036e-1f);
-    p = __builtin_fmaf(p, z, -3.33332819422e-1f);
-    const float small = __builtin_fmaf(p * z, x, x);
-    return ax >= 0.625f ? big : small;
-}
-
 /* NT tiles held in accumulator layout -> dst[b0 + r][32 m ..] (row pitch `pitch` floats) as complete 128-byte lines, half a tile at a
  * time through the wave's LDS slab [16][32] (16-byte pieces XOR-swizzled by the row); buffer stores: rows past the batch are out of range */
 typedef unsigned f64_u32x4 __attribute__((ext_vector_type(4)));
@@ -203,7 +188,7 @@ __global__ __launch_bounds__(FWW * 64, 1) void coupling_affine_fwd64_train_kerne
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int dim = (r & 3) + 8 * (r >> 2) + 4 * hh;
-            const float l = (has_scale && dim < d) ? f64_tanh_out(sr[r]) * alpha : 0.0f;
+            const float l = (has_scale && dim < d) ? bgk_tanh_out(sr[r]) * alpha : 0.0f;
             sr[r] = l;
             lsum += l;
         }

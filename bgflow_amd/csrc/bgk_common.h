@@ -9,6 +9,7 @@
 #include "../../include/bgflow_amd.h"
 #include "bgk_detmath.h"
 #include "bgk_detmath_pk.h"
+#include "bgk_fused2.h"      /* BgkSplineBox */
 
 #define BGK_WAVE 64
 
@@ -42,16 +43,14 @@ struct BgkRqsCfg {
     float beta;
 };
 
-static inline BgkRqsCfg bgk_make_rqs_cfg(double left, double right, double bottom, double top,
-                                         double min_w, double min_h, double min_d,
-                                         int identity_init, int K) {
+static inline BgkRqsCfg bgk_make_rqs_cfg(const BgkSplineBox& b, int K) {
     BgkRqsCfg c;
-    c.left = (float)left; c.right = (float)right; c.bottom = (float)bottom; c.top = (float)top;
-    c.xspan = (float)(right - left); c.yspan = (float)(top - bottom);
-    c.min_w = (float)min_w; c.min_h = (float)min_h; c.min_d = (float)min_d;
-    c.w_scale = (float)(1.0 - min_w * K);
-    c.h_scale = (float)(1.0 - min_h * K);
-    c.beta = (float)(identity_init ? (0.6931471805599453 / (1.0 - min_d)) : 1.0);
+    c.left = (float)b.left; c.right = (float)b.right; c.bottom = (float)b.bottom; c.top = (float)b.top;
+    c.xspan = (float)(b.right - b.left); c.yspan = (float)(b.top - b.bottom);
+    c.min_w = (float)b.min_bin_width; c.min_h = (float)b.min_bin_height; c.min_d = (float)b.min_derivative;
+    c.w_scale = (float)(1.0 - b.min_bin_width * K);
+    c.h_scale = (float)(1.0 - b.min_bin_height * K);
+    c.beta = (float)(b.identity_init ? (0.6931471805599453 / (1.0 - b.min_derivative)) : 1.0);
     return c;
 }
 

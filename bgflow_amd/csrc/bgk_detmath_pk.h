@@ -167,4 +167,20 @@ __device__ __forceinline__ float bgk_rcp_sat(float d) {
     return __builtin_fmaf(__builtin_fminf(__builtin_fmaf(-d, r, 1.0f), 1.0f), r, r);
 }
 
+/* tanh of an affine coupling's OUTPUT layer (log sigma), one definition for every affine kernel: hardware exp2 + bgk_rcp_sat above 0.625
+ * (abs error ~1e-7; +-1 where exp2 overflows), odd polynomial below (same coefficients as bgk_tanhf2) */
+__device__ __forceinline__ float bgk_tanh_out(float x) {
+    const float ax = __builtin_fabsf(x);
+    const float dn = 1.0f + __builtin_amdgcn_exp2f(ax * 2.88539008177792681f);
+    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, bgk_rcp_sat(dn), 1.0f), x);
+    const float z = x * x;
+    float p = -5.70498872745e-3f;
+    p = __builtin_fmaf(p, z, 2.06390887954e-2f);
+    p = __builtin_fmaf(p, z, -5.37397155531e-2f);
+    p = __builtin_fmaf(p, z, 1.33314422036e-1f);
+    p = __builtin_fmaf(p, z, -3.33332819422e-1f);
+    const float small = __builtin_fmaf(p * z, x, x);
+    return ax >= 0.625f ? big : small;
+}
+
 #endif /* BGK_DETMATH_PK_H */

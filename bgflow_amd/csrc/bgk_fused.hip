@@ -1429,6 +1429,24 @@ extern "C" int32_t bgk_pack_rqs_columns(int32_t d, int32_t K, const int32_t* nc_
     return ncp;
 }
 
+namespace {
+/* the part of FusedArgs that every spline launcher of this file fills the same way, from the call record; the dims of a 128-column
+ * parameter chunk follow from the bin count (3 K + 1 packed parameters per dim).  W0 / W1 / W2 / T0: the exact-f32 kernel's operands */
+void fill_fused_args(FusedArgs& a, const BgkRqsDenseCall& c, int K, int lds_per_wave) {
+    a.cond = c.cond; a.ldc = c.ldc; a.d_c = c.d_c; a.periodic = c.periodic;
+    a.W0 = nullptr; a.W1 = nullptr; a.W2 = nullptr; a.T0 = 0;
+    const int ppd_k = 3 * K + 1, dpc_k = 128 / ppd_k;
+    a.n_chunks = (c.d + dpc_k - 1) / dpc_k;
+    a.last_tiles = ((c.d - (a.n_chunks - 1) * dpc_k) * ppd_k + 31) / 32;
+    a.act = c.act; a.y = c.y; a.ldy = c.ldy; a.B = c.B; a.d = c.d; a.inverse = c.inverse;
+    a.circ_mask = c.circ_mask;
+    a.out = c.out; a.ldo = c.ldo; a.dlogp = c.dlogp; a.accumulate = c.accumulate;
+    a.bin_idx = c.bin_idx; a.oob_count = c.oob_count;
+    a.lds_per_wave = lds_per_wave;
+    a.cfg = bgk_make_rqs_cfg(c.box, K);
+}
+}  // namespace
+
 extern "C" int bgk_coupling_rqs_dense(const float* cond, int64_t ldc, int32_t d_c, int32_t periodic,
                                       const float* W0p, const float* W1p, const float* W2p,
                                       int32_t H0, int32_t H1, int32_t act, const float* y,
@@ -1440,6 +1458,8 @@ extern "C" int bgk_coupling_rqs_dense(const float* cond, int64_t ldc, int32_t d_
                                       int64_t ldo, float* dlogp, int32_t accumulate,
                                       int32_t* bin_idx, int32_t* oob_count, void* stream) {
     if (B == 0) return 0;       /* an empty batch: nothing to do (its tensors have no storage, hence null pointers) */
+    const BgkSplineBox box{.left = left, .right = right, .bottom = bottom, .top = top, .min_bin_width = min_bin_width,
+                           .min_bin_height = min_bin_height, .min_derivative = min_derivative, .identity_init = identity_init};
     BGK_CHECK_ARG(cond && W0p && W1p && W2p && y && out && dlogp, "bgk_coupling_rqs_dense: null pointer");
     BGK_CHECK_ARG(B >= 0 && d > 0 && d_c > 0, "bgk_coupling_rqs_dense: bad sizes");
     if (H0 != HID || H1 != HID || K != KB || d > 64 || act < 1 || act > 3) {
@@ -1454,19 +1474,16 @@ extern "C" int bgk_coupling_rqs_dense(const float* cond, int64_t ldc, int32_t d_
     }
     BGK_CHECK_ARG(min_bin_width * K <= 1.0 && min_bin_height * K <= 1.0,
                   "Minimal bin width/height too large for the number of bins");
-    if (B == 0) return 0;
+    BgkRqsDenseCall c{};
+    c.what = "bgk_coupling_rqs_dense";
+    c.cond = cond; c.ldc = ldc; c.d_c = d_c; c.periodic = periodic;
+    c.act = act; c.y = y; c.ldy = ldy; c.B = B; c.d = d; c.circ_mask = circ_mask; c.inverse = inverse; c.box = box;
+    c.out = out; c.ldo = ldo; c.dlogp = dlogp; c.accumulate = accumulate; c.bin_idx = bin_idx; c.oob_count = oob_count; c.stream = stream;
     FusedArgs a;
-    a.cond = cond; a.ldc = ldc; a.d_c = d_c; a.periodic = periodic;
+    fill_fused_args(a, c, KB, LDS_P + (d + 1) * SROW);   /* + dummy row for discarded spline slots */
     a.W0 = reinterpret_cast<const float4*>(W0p); a.T0 = ((n_in + 1) / 2 + 3) & ~3;   /* padded to x4 by the packer */
     a.W1 = reinterpret_cast<const float4*>(W1p);
-    a.W2 = reinterpret_cast<const float4*>(W2p); a.n_chunks = (d + DPC - 1) / DPC;
-    a.last_tiles = ((d - (a.n_chunks - 1) * DPC) * PPD + 31) / 32;
-    a.act = act; a.y = y; a.ldy = ldy; a.B = B; a.d = d; a.inverse = inverse;
-    a.circ_mask = circ_mask;
-    a.out = out; a.ldo = ldo; a.dlogp = dlogp; a.accumulate = accumulate;
-    a.bin_idx = bin_idx; a.oob_count = oob_count;
-    a.lds_per_wave = LDS_P + (d + 1) * SROW;   /* + dummy row for discarded spline slots */
-    a.cfg = bgk_make_rqs_cfg(left, right, bottom, top, min_bin_width, min_bin_height, min_derivative, identity_init, K);
+    a.W2 = reinterpret_cast<const float4*>(W2p);
     size_t shmem = sizeof(float) * (size_t)FW * a.lds_per_wave;
     int64_t n_wg = ((B + 31) / 32 + FW - 1) / FW;
     BGK_CHECK_ARG(n_wg < (int64_t)0x7fffffff, "bgk_coupling_rqs_dense: batch too large for one launch");
@@ -1481,23 +1498,20 @@ extern "C" int bgk_coupling_rqs_dense(const float* cond, int64_t ldc, int32_t d_
 }
 
 namespace {
-int launch_h2(const char* what, const float* cond, int64_t ldc, int32_t d_c, int32_t periodic,
-              const void* A0p, const void* A1p, const void* A2p, float c0, float c1, float c2, const float* cs_dev,
-              int32_t operand_dtype, int32_t H0, int32_t H1, int32_t act, const float* y, int64_t ldy, int64_t B, int32_t d, int32_t K,
-              uint64_t circ_mask, int32_t inverse, double left, double right, double bottom, double top,
-              double min_bin_width, double min_bin_height, double min_derivative, int32_t identity_init,
-              float* out, int64_t ldo, float* dlogp, int32_t accumulate, int32_t* bin_idx, int32_t* oob_count,
-              float* z0, float* z1, float* params, int64_t ldp, const int32_t* src_col, void* stream, const BgkCondSegs* segs = nullptr,
-              int params_layout = 0) {
-    if (segs && segs->n >= 1) { cond = segs->ptr[0]; ldc = segs->ld[0]; }
+/* operand_dtype: 0 = split-f16, 1 = bf16, 2 = split-f16 with the output layer in row order 2; params_layout: of c.params (training forward) */
+int launch_h2(const BgkRqsDenseCall& c, int32_t operand_dtype, int32_t H0, int32_t H1, int32_t K, int params_layout = 0) {
+    const char* what = c.what;
+    const BgkCondSegs* segs = c.segs;
+    const int d = c.d, d_c = c.d_c, act = c.act, inverse = c.inverse;
+    const int64_t B = c.B;
     /* operand_dtype 2: split-f16 operands whose output layer is in row order 2 (bgk_pack_rqs_columns_v) -- the second-generation inference kernel only */
     const int row_order = operand_dtype == 2 ? 2 : 1;
     if (operand_dtype == 2) operand_dtype = 0;
-    BGK_CHECK_ARG(cond && A0p && A1p && A2p && y && out && dlogp, "%s: null pointer", what);
+    BGK_CHECK_ARG(c.cond && c.A0p && c.A1p && c.A2p && c.y && c.out && c.dlogp, "%s: null pointer", what);
     BGK_CHECK_ARG(B >= 0 && d > 0 && d_c > 0, "%s: bad sizes", what);
     const bool other_k = (K == 4 || K == 12 || K == 16 || K == 32) && operand_dtype == 0;     /* K != 8: split-f16 only (inference and training forward) */
     const bool wide = H0 == 32 * W_T && H1 == 32 * W_T;      /* hidden width 256 (129 .. 255 zero-padded by the packer): split-f16 inference */
-    if (wide && (operand_dtype != 0 || row_order != 1 || z0 || z1 || params || (segs && segs->n > 1))) {
+    if (wide && (operand_dtype != 0 || row_order != 1 || c.z0 || c.z1 || c.params || (segs && segs->n > 1))) {
         bgk_set_error("%s: hidden width 256 runs fused in split-f16 inference from one conditioning tensor only", what);
         return BGK_EUNSUPPORTED;
     }
@@ -1506,39 +1520,33 @@ int launch_h2(const char* what, const float* cond, int64_t ldc, int32_t d_c, int
                       "(got H0=%d H1=%d K=%d d=%d act=%d)", what, H0, H1, K, d, act);
         return BGK_EUNSUPPORTED;
     }
-    const int n_in = periodic ? 2 * d_c : d_c;
+    const int n_in = c.periodic ? 2 * d_c : d_c;
     const int S0 = (n_in + 1 + 15) / 16;
     if (16 * S0 * SROW > LDS_P) {        /* outside the envelope, not an error: the caller runs the conditioner layer by layer */
         bgk_set_error("%s: conditioner input of %d features does not fit the layer-0 tile (at most 111)", what, n_in);
         return BGK_EUNSUPPORTED;
     }
-    BGK_CHECK_ARG(min_bin_width * K <= 1.0 && min_bin_height * K <= 1.0,
+    BGK_CHECK_ARG(c.box.min_bin_width * K <= 1.0 && c.box.min_bin_height * K <= 1.0,
                   "Minimal bin width/height too large for the number of bins");
     if (B == 0) return 0;
+    /* the operands and the save part of FusedArgsH2 */
+    const auto fill_h2 = [&](FusedArgsH2& ah) {
+        ah.A0 = reinterpret_cast<const uint4*>(c.A0p); ah.S0 = S0;
+        ah.A1 = reinterpret_cast<const uint4*>(c.A1p);
+        ah.A2 = reinterpret_cast<const uint4*>(c.A2p);
+        ah.c0 = c.c0; ah.c1 = c.c1; ah.c2 = c.c2; ah.cs_dev = c.cs_dev;
+        ah.z0 = c.z0; ah.z1 = c.z1; ah.params = c.params; ah.ldp = c.ldp; ah.src_col = c.src_col;
+    };
     if (wide) {
         FusedArgsH2 ah;
         FusedArgs& a = ah.f;
-        a.cond = cond; a.ldc = ldc; a.d_c = d_c; a.periodic = periodic;
-        a.W0 = nullptr; a.W1 = nullptr; a.W2 = nullptr; a.T0 = 0;
-        const int ppd_k = 3 * K + 1, dpc_k = 128 / ppd_k;
-        a.n_chunks = (d + dpc_k - 1) / dpc_k;
-        a.last_tiles = ((d - (a.n_chunks - 1) * dpc_k) * ppd_k + 31) / 32;
-        a.act = act; a.y = y; a.ldy = ldy; a.B = B; a.d = d; a.inverse = inverse;
-        a.circ_mask = circ_mask;
-        a.out = out; a.ldo = ldo; a.dlogp = dlogp; a.accumulate = accumulate;
-        a.bin_idx = bin_idx; a.oob_count = oob_count;
-        a.lds_per_wave = 128 * 32 + (d + 1) * SROW;
-        a.cfg = bgk_make_rqs_cfg(left, right, bottom, top, min_bin_width, min_bin_height, min_derivative, identity_init, K);
-        ah.A0 = reinterpret_cast<const uint4*>(A0p); ah.S0 = S0;
-        ah.A1 = reinterpret_cast<const uint4*>(A1p);
-        ah.A2 = reinterpret_cast<const uint4*>(A2p);
-        ah.c0 = c0; ah.c1 = c1; ah.c2 = c2; ah.cs_dev = cs_dev;
-        ah.z0 = nullptr; ah.z1 = nullptr; ah.params = nullptr; ah.ldp = 0; ah.src_col = nullptr;
+        fill_fused_args(a, c, K, 128 * 32 + (d + 1) * SROW);
+        fill_h2(ah);                     /* (no save part here: checked above) */
         const size_t shmem = sizeof(float) * (size_t)FW * a.lds_per_wave;
         const int64_t n_wg = ((B + 31) / 32 + FW - 1) / FW;
         BGK_CHECK_ARG(n_wg < (int64_t)0x7fffffff, "%s: batch too large for one launch", what);
         const int grid = (int)n_wg;
-        hipStream_t st = (hipStream_t)stream;
+        hipStream_t st = (hipStream_t)c.stream;
 #define BGK_LAUNCHW(I, KK) hipLaunchKernelGGL((coupling_rqs_dense_w256_kernel<I, KK>), dim3(grid), dim3(FTHREADS), shmem, st, ah)
 #define BGK_LAUNCHW2(KK) do { if (inverse) BGK_LAUNCHW(1, KK); else BGK_LAUNCHW(0, KK); } while (0)
         if (K == 8) BGK_LAUNCHW2(8); else if (K == 4) BGK_LAUNCHW2(4); else if (K == 12) BGK_LAUNCHW2(12);
@@ -1548,51 +1556,34 @@ int launch_h2(const char* what, const float* cond, int64_t ldc, int32_t d_c, int
         return bgk_launch_status(what);
     }
     /* second-generation kernels: their staging index math uses 24-bit multiplies (row strides below 2^24 floats) */
-    const bool v2_ok = bgk_h2_variant == 2 && K == KB && ldc < (1 << 24) && ldy < (1 << 24) && ldo < (1 << 24);
-    if (row_order == 2 && !(v2_ok && z0 == nullptr)) {
+    const bool v2_ok = bgk_h2_variant == 2 && K == KB && c.ldc < (1 << 24) && c.ldy < (1 << 24) && c.ldo < (1 << 24);
+    const bool save = c.z0 != nullptr;
+    if (row_order == 2 && !(v2_ok && !save)) {
         bgk_set_error("%s: output-layer row order 2 is read by the second-generation inference kernel only (8 bins, hidden width 128)", what);
         return BGK_EUNSUPPORTED;
     }
     if (segs && segs->n > 1 && !v2_ok) return BGK_EUNSUPPORTED;     /* several conditioning tensors: second-generation kernels only */
-    if (params_layout == 1 && !(v2_ok && z0 != nullptr && operand_dtype == 0 && params && z1)) return BGK_EUNSUPPORTED;   /* element-major parameters: second-generation kernel only */
-    if (params_layout == 2 && !(v2_ok && z0 != nullptr && operand_dtype == 0 && z1)) return BGK_EUNSUPPORTED;             /* no parameter write-out: likewise */
-    if (v2_ok && z0 != nullptr && operand_dtype == 0 && (src_col || params_layout >= 1) && (params || params_layout == 2) && z1)   /* training forward */
-        return bgk_launch_rqs_dense_h2v2_train(what, z0, z1, params_layout == 2 ? nullptr : params, ldp, params_layout >= 1 ? nullptr : src_col, cond, ldc, d_c, periodic, A0p, A1p, A2p, c0, c1, c2, cs_dev,
-                                               act, y, ldy, B, d, circ_mask, inverse, left, right, bottom, top, min_bin_width,
-                                               min_bin_height, min_derivative, identity_init, out, ldo, dlogp, accumulate, bin_idx,
-                                               oob_count, stream, segs);
-    if (v2_ok && z0 == nullptr && operand_dtype == 1)   /* reduced-precision bf16 mode on the second-generation kernel */
-        return bgk_launch_rqs_dense_h2v2_bf16(what, cond, ldc, d_c, periodic, A0p, A1p, A2p, c0, c1, c2, cs_dev, act, y, ldy, B, d, circ_mask,
-                                              inverse, left, right, bottom, top, min_bin_width, min_bin_height, min_derivative,
-                                              identity_init, out, ldo, dlogp, accumulate, bin_idx, oob_count, stream, segs);
-    if (v2_ok && z0 == nullptr && operand_dtype == 0)   /* split-f16 inference: the second-generation kernel */
-        return bgk_launch_rqs_dense_h2v2(what, cond, ldc, d_c, periodic, A0p, A1p, A2p, c0, c1, c2, cs_dev, act, y, ldy, B, d, circ_mask,
-                                         inverse, left, right, bottom, top, min_bin_width, min_bin_height, min_derivative,
-                                         identity_init, out, ldo, dlogp, accumulate, bin_idx, oob_count, stream, segs, row_order);
+    if (params_layout == 1 && !(v2_ok && save && operand_dtype == 0 && c.params && c.z1)) return BGK_EUNSUPPORTED;   /* element-major parameters: second-generation kernel only */
+    if (params_layout == 2 && !(v2_ok && save && operand_dtype == 0 && c.z1)) return BGK_EUNSUPPORTED;               /* no parameter write-out: likewise */
+    if (v2_ok && (operand_dtype == 0 || (operand_dtype == 1 && !save))) {     /* the second-generation kernels */
+        BgkRqsDenseCall v = c;
+        v.row_order = row_order;
+        if (!save) return operand_dtype == 1 ? bgk_launch_rqs_dense_h2v2_bf16(v) : bgk_launch_rqs_dense_h2v2(v);   /* bf16 mode | split-f16 inference */
+        if ((c.src_col || params_layout >= 1) && (c.params || params_layout == 2) && c.z1) {                     /* training forward */
+            if (params_layout == 2) v.params = nullptr;
+            if (params_layout >= 1) v.src_col = nullptr;
+            return bgk_launch_rqs_dense_h2v2_train(v);
+        }
+    }
     FusedArgsH2 ah;
     FusedArgs& a = ah.f;
-    a.cond = cond; a.ldc = ldc; a.d_c = d_c; a.periodic = periodic;
-    a.W0 = nullptr; a.W1 = nullptr; a.W2 = nullptr; a.T0 = 0;
-    const int ppd_k = 3 * K + 1, dpc_k = 128 / ppd_k;
-    a.n_chunks = (d + dpc_k - 1) / dpc_k;
-    a.last_tiles = ((d - (a.n_chunks - 1) * dpc_k) * ppd_k + 31) / 32;
-    a.act = act; a.y = y; a.ldy = ldy; a.B = B; a.d = d; a.inverse = inverse;
-    a.circ_mask = circ_mask;
-    a.out = out; a.ldo = ldo; a.dlogp = dlogp; a.accumulate = accumulate;
-    a.bin_idx = bin_idx; a.oob_count = oob_count;
-    const bool save = z0 != nullptr;
-    a.lds_per_wave = 128 * (save ? 33 : 32) + (d + 1) * SROW;
-    a.cfg = bgk_make_rqs_cfg(left, right, bottom, top, min_bin_width, min_bin_height, min_derivative, identity_init, K);
-    ah.A0 = reinterpret_cast<const uint4*>(A0p); ah.S0 = S0;
-    ah.A1 = reinterpret_cast<const uint4*>(A1p);
-    ah.A2 = reinterpret_cast<const uint4*>(A2p);
-    ah.c0 = c0; ah.c1 = c1; ah.c2 = c2; ah.cs_dev = cs_dev;
-    ah.z0 = z0; ah.z1 = z1; ah.params = params; ah.ldp = ldp; ah.src_col = src_col;
+    fill_fused_args(a, c, K, 128 * (save ? 33 : 32) + (d + 1) * SROW);
+    fill_h2(ah);
     size_t shmem = sizeof(float) * (size_t)FW * a.lds_per_wave;
     int64_t n_wg = ((B + 31) / 32 + FW - 1) / FW;
     BGK_CHECK_ARG(n_wg < (int64_t)0x7fffffff, "%s: batch too large for one launch", what);
     int grid = (int)n_wg;
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)c.stream;
     BGK_CHECK_ARG(operand_dtype == 0 || (operand_dtype == 1 && !save), "%s: operand_dtype %d (0 = split-f16, 1 = bf16; the training "
                   "forward is split-f16 only)", what, operand_dtype);
 #define BGK_LAUNCH(A, I, S, F) hipLaunchKernelGGL((coupling_rqs_dense_h2_kernel<A, I, S, F>), dim3(grid), dim3(FTHREADS), shmem, st, ah)
@@ -1628,6 +1619,8 @@ extern "C" int bgk_coupling_rqs_dense_deep(const float* cond, int64_t ldc, int32
                                            float* out, int64_t ldo, float* dlogp, int32_t accumulate,
                                            int32_t* bin_idx, int32_t* oob_count, void* stream) {
     if (B == 0) return 0;       /* an empty batch: nothing to do (its tensors have no storage, hence null pointers) */
+    const BgkSplineBox box{.left = left, .right = right, .bottom = bottom, .top = top, .min_bin_width = min_bin_width,
+                           .min_bin_height = min_bin_height, .min_derivative = min_derivative, .identity_init = identity_init};
     const char* what = "bgk_coupling_rqs_dense_deep";
     BGK_CHECK_ARG(cond && A0p && A2p && y && out && dlogp, "%s: null pointer", what);
     BGK_CHECK_ARG(B > 0 && d > 0 && d_c > 0, "%s: bad sizes", what);
@@ -1644,20 +1637,14 @@ extern "C" int bgk_coupling_rqs_dense_deep(const float* cond, int64_t ldc, int32
         return BGK_EUNSUPPORTED;
     }
     BGK_CHECK_ARG(min_bin_width * K <= 1.0 && min_bin_height * K <= 1.0, "Minimal bin width/height too large for the number of bins");
+    BgkRqsDenseCall c{};
+    c.what = what;
+    c.cond = cond; c.ldc = ldc; c.d_c = d_c; c.periodic = periodic;
+    c.act = act; c.y = y; c.ldy = ldy; c.B = B; c.d = d; c.circ_mask = circ_mask; c.inverse = inverse; c.box = box;
+    c.out = out; c.ldo = ldo; c.dlogp = dlogp; c.accumulate = accumulate; c.bin_idx = bin_idx; c.oob_count = oob_count; c.stream = stream;
     DeepArgs da;
     FusedArgsH2& ah = da.h;
-    FusedArgs& a = ah.f;
-    a.cond = cond; a.ldc = ldc; a.d_c = d_c; a.periodic = periodic;
-    a.W0 = nullptr; a.W1 = nullptr; a.W2 = nullptr; a.T0 = 0;
-    const int ppd_k = 3 * K + 1, dpc_k = 128 / ppd_k;
-    a.n_chunks = (d + dpc_k - 1) / dpc_k;
-    a.last_tiles = ((d - (a.n_chunks - 1) * dpc_k) * ppd_k + 31) / 32;
-    a.act = act; a.y = y; a.ldy = ldy; a.B = B; a.d = d; a.inverse = inverse;
-    a.circ_mask = circ_mask;
-    a.out = out; a.ldo = ldo; a.dlogp = dlogp; a.accumulate = accumulate;
-    a.bin_idx = bin_idx; a.oob_count = oob_count;
-    a.lds_per_wave = 128 * 32 + (d + 1) * SROW;
-    a.cfg = bgk_make_rqs_cfg(left, right, bottom, top, min_bin_width, min_bin_height, min_derivative, identity_init, K);
+    fill_fused_args(ah.f, c, K, 128 * 32 + (d + 1) * SROW);
     ah.A0 = reinterpret_cast<const uint4*>(A0p); ah.S0 = S0;
     ah.A1 = reinterpret_cast<const uint4*>(A1p);
     ah.A2 = reinterpret_cast<const uint4*>(A2p);
@@ -1665,7 +1652,7 @@ extern "C" int bgk_coupling_rqs_dense_deep(const float* cond, int64_t ldc, int32
     ah.z0 = nullptr; ah.z1 = nullptr; ah.params = nullptr; ah.ldp = 0; ah.src_col = nullptr;
     da.n_hh = n_hidden - 1;
     for (int l = 0; l < DEEP_MAX_HH; ++l) da.c1s[l] = l < da.n_hh ? c1s[l] : 1.0f;
-    const size_t shmem = sizeof(float) * (size_t)FW * a.lds_per_wave;
+    const size_t shmem = sizeof(float) * (size_t)FW * ah.f.lds_per_wave;
     const int64_t n_wg = ((B + 31) / 32 + FW - 1) / FW;
     BGK_CHECK_ARG(n_wg < (int64_t)0x7fffffff, "%s: batch too large for one launch", what);
     const int grid = (int)n_wg;
@@ -1691,10 +1678,15 @@ extern "C" int bgk_coupling_rqs_dense_h2(const float* cond, int64_t ldc, int32_t
                                          int64_t ldo, float* dlogp, int32_t accumulate,
                                          int32_t* bin_idx, int32_t* oob_count, void* stream) {
     if (B == 0) return 0;       /* an empty batch: nothing to do (its tensors have no storage, hence null pointers) */
-    return launch_h2("bgk_coupling_rqs_dense_h2", cond, ldc, d_c, periodic, A0p, A1p, A2p, c0, c1, c2, cs_dev, operand_dtype, H0, H1, act, y, ldy, B, d, K,
-                     circ_mask, inverse, left, right, bottom, top, min_bin_width, min_bin_height, min_derivative,
-                     identity_init, out, ldo, dlogp, accumulate, bin_idx, oob_count,
-                     nullptr, nullptr, nullptr, 0, nullptr, stream);
+    const BgkSplineBox box{.left = left, .right = right, .bottom = bottom, .top = top, .min_bin_width = min_bin_width,
+                           .min_bin_height = min_bin_height, .min_derivative = min_derivative, .identity_init = identity_init};
+    BgkRqsDenseCall c{};
+    c.what = "bgk_coupling_rqs_dense_h2";
+    c.cond = cond; c.ldc = ldc; c.d_c = d_c; c.periodic = periodic;
+    c.A0p = A0p; c.A1p = A1p; c.A2p = A2p; c.c0 = c0; c.c1 = c1; c.c2 = c2; c.cs_dev = cs_dev;
+    c.act = act; c.y = y; c.ldy = ldy; c.B = B; c.d = d; c.circ_mask = circ_mask; c.inverse = inverse; c.box = box;
+    c.out = out; c.ldo = ldo; c.dlogp = dlogp; c.accumulate = accumulate; c.bin_idx = bin_idx; c.oob_count = oob_count; c.stream = stream;
+    return launch_h2(c, operand_dtype, H0, H1, K);
 }
 
 extern "C" int bgk_coupling_rqs_dense_h2_mc(const float* const* cond, const int64_t* ldc, const int32_t* width, int32_t n_cond, int32_t periodic,
@@ -1714,10 +1706,15 @@ extern "C" int bgk_coupling_rqs_dense_h2_mc(const float* const* cond, const int6
     int d_c = 0;
     for (int i = 0; i < n_cond; ++i) { segs.ptr[i] = cond[i]; segs.ld[i] = ldc[i]; segs.w[i] = width[i]; d_c += width[i]; }
     segs.n = n_cond;
-    return launch_h2("bgk_coupling_rqs_dense_h2_mc", cond[0], ldc[0], d_c, periodic, A0p, A1p, A2p, c0, c1, c2, cs_dev, operand_dtype, H0, H1, act, y, ldy,
-                     B, d, K, circ_mask, inverse, left, right, bottom, top, min_bin_width, min_bin_height, min_derivative,
-                     identity_init, out, ldo, dlogp, accumulate, bin_idx, oob_count,
-                     nullptr, nullptr, nullptr, 0, nullptr, stream, &segs);
+    const BgkSplineBox box{.left = left, .right = right, .bottom = bottom, .top = top, .min_bin_width = min_bin_width,
+                           .min_bin_height = min_bin_height, .min_derivative = min_derivative, .identity_init = identity_init};
+    BgkRqsDenseCall c{};
+    c.what = "bgk_coupling_rqs_dense_h2_mc";
+    c.cond = cond[0]; c.ldc = ldc[0]; c.d_c = d_c; c.periodic = periodic; c.segs = &segs;
+    c.A0p = A0p; c.A1p = A1p; c.A2p = A2p; c.c0 = c0; c.c1 = c1; c.c2 = c2; c.cs_dev = cs_dev;
+    c.act = act; c.y = y; c.ldy = ldy; c.B = B; c.d = d; c.circ_mask = circ_mask; c.inverse = inverse; c.box = box;
+    c.out = out; c.ldo = ldo; c.dlogp = dlogp; c.accumulate = accumulate; c.bin_idx = bin_idx; c.oob_count = oob_count; c.stream = stream;
+    return launch_h2(c, operand_dtype, H0, H1, K);
 }
 
 extern "C" int bgk_coupling_rqs_dense_h2_train(const float* cond, int64_t ldc, int32_t d_c, int32_t periodic,
@@ -1738,9 +1735,16 @@ extern "C" int bgk_coupling_rqs_dense_h2_train(const float* cond, int64_t ldc, i
     BGK_CHECK_ARG(z0 && z1 && (params || params_layout == 2) && (src_col_dev || params_layout >= 1), "bgk_coupling_rqs_dense_h2_train: null save buffer");
     const int n_nc = d - __builtin_popcountll(circ_mask & (d >= 64 ? ~0ull : ((1ull << d) - 1)));
     BGK_CHECK_ARG(params_layout == 2 || ldp >= (params_layout == 1 ? (3 * K + 1) * d + 3 : 3 * K * d + n_nc), "bgk_coupling_rqs_dense_h2_train: params row stride %lld too small", (long long)ldp);
-    return launch_h2("bgk_coupling_rqs_dense_h2_train", cond, ldc, d_c, periodic, A0p, A1p, A2p, c0, c1, c2, cs_dev, 0, H0, H1, act, y, ldy, B, d,
-                     K, circ_mask, inverse, left, right, bottom, top, min_bin_width, min_bin_height, min_derivative,
-                     identity_init, out, ldo, dlogp, accumulate, nullptr, oob_count, z0, z1, params, ldp, src_col_dev, stream, nullptr, params_layout);
+    const BgkSplineBox box{.left = left, .right = right, .bottom = bottom, .top = top, .min_bin_width = min_bin_width,
+                           .min_bin_height = min_bin_height, .min_derivative = min_derivative, .identity_init = identity_init};
+    BgkRqsDenseCall c{};
+    c.what = "bgk_coupling_rqs_dense_h2_train";
+    c.cond = cond; c.ldc = ldc; c.d_c = d_c; c.periodic = periodic;
+    c.A0p = A0p; c.A1p = A1p; c.A2p = A2p; c.c0 = c0; c.c1 = c1; c.c2 = c2; c.cs_dev = cs_dev;
+    c.act = act; c.y = y; c.ldy = ldy; c.B = B; c.d = d; c.circ_mask = circ_mask; c.inverse = inverse; c.box = box;
+    c.out = out; c.ldo = ldo; c.dlogp = dlogp; c.accumulate = accumulate; c.bin_idx = nullptr; c.oob_count = oob_count; c.stream = stream;
+    c.z0 = z0; c.z1 = z1; c.params = params; c.ldp = ldp; c.src_col = src_col_dev;
+    return launch_h2(c, 0, H0, H1, K, params_layout);
 }
 
 /* Backward of the spline transformer of a layer whose training forward ran with params_layout = 2 (no parameter write-out): the
@@ -1766,7 +1770,12 @@ extern "C" int bgk_coupling_rqs_dense_h2_backward(const float* z1, const void* A
     BGK_CHECK_ARG(P == 3 * K * d + n_nc && ldgp >= P && ldy >= d && ldgo >= d && ldgy >= d, "%s: bad widths / row strides", what);
     BGK_CHECK_ARG(((uintptr_t)z1 & 15) == 0, "%s: z1 must be 16-byte aligned", what);
     BGK_CHECK_ARG(min_bin_width * K <= 1.0 && min_bin_height * K <= 1.0, "Minimal bin width/height too large for the number of bins");
-    return bgk_launch_rqs_bwd_recompute(what, z1, A2p, c2, cs_dev, act, y, ldy, B, d, circ_mask, inverse, left, right, bottom, top,
-                                        min_bin_width, min_bin_height, min_derivative, identity_init, g_out, ldgo, g_dlogp, g_y, ldgy,
-                                        g_params, ldgp, g_absmax, stream);
+    BgkRqsBwdCall c{};
+    c.what = what; c.z1 = z1; c.A2p = A2p; c.c2 = c2; c.cs_dev = cs_dev; c.act = act;
+    c.y = y; c.ldy = ldy; c.B = B; c.d = d; c.circ_mask = circ_mask; c.inverse = inverse;
+    c.box = BgkSplineBox{.left = left, .right = right, .bottom = bottom, .top = top, .min_bin_width = min_bin_width,
+                         .min_bin_height = min_bin_height, .min_derivative = min_derivative, .identity_init = identity_init};
+    c.g_out = g_out; c.ldgo = ldgo; c.g_dlogp = g_dlogp; c.g_y = g_y; c.ldgy = ldgy; c.g_params = g_params; c.ldgp = ldgp;
+    c.g_absmax = g_absmax; c.stream = stream;
+    return bgk_launch_rqs_bwd_recompute(c);
 }

@@ -405,10 +405,6 @@ __device__ __forceinline__ float fdiv_hw(float n, float d) {
     const float q = n * r;
     return __builtin_fmaf(__builtin_fmaf(-d, q, n), r, q);
 }
-__device__ __forceinline__ float rcp_nr(float d) {
-    const float r = __builtin_amdgcn_rcpf(d);
-    return __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
-}
 
 template <bool KARG> struct ScSrc;
 template <> struct ScSrc<true> {
@@ -454,7 +450,7 @@ __device__ __forceinline__ float rqs_fast(H hk, float x, const float (&va)[KB], 
     hk.template at<3>();
     E[3] += E[2]; E[4] += E[3]; E[5] += E[4]; E[6] += E[5]; E[7] += E[6];
     hk.template at<4>();
-    const float gA = SC.sa.gnum * rcp_nr(E[7]);
+    const float gA = SC.sa.gnum * bgk_rcp_refined(E[7]);
     float kn[7];
     kn[0] = __builtin_fmaf(E[0], gA, SC.sa.kc[0]);
     kn[1] = __builtin_fmaf(E[1], gA, SC.sa.kc[1]);
@@ -1370,22 +1366,6 @@ __device__ __forceinline__ void aff_layers(const AffV2Net& n, f32x16 (&X)[4], f3
 }
 #endif
 
-/* tanh for the OUTPUT layer (log sigma): hardware exp2 + Newton-refined rcp above 0.625 (abs error ~1e-7; +-1 where exp2 overflows),
- * odd polynomial below (the form of the other fused affine kernels, bgk_fused_affine.hip::r_tanh_out) */
-__device__ __forceinline__ float aff_tanh_out(float x) {
-    const float ax = __builtin_fabsf(x);
-    const float dn = 1.0f + __builtin_amdgcn_exp2f(ax * 2.88539008177792681f);
-    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, bgk_rcp_sat(dn), 1.0f), x);
-    const float z = x * x;
-    float p = -5.70498872745e-3f;
-    p = __builtin_fmaf(p, z, 2.06390887954e-2f);
-    p = __builtin_fmaf(p, z, -5.37397155531e-2f);
-    p = __builtin_fmaf(p, z, 1.33314422036e-1f);
-    p = __builtin_fmaf(p, z, -3.33332819422e-1f);
-    const float small = __builtin_fmaf(p * z, x, x);
-    return ax >= 0.625f ? big : small;
-}
-
 #ifndef BGK_V2_AFF_TS
 #define BGK_V2_AFF_TS 0               /* profiling build (tools/r06_aff_ts.py): lane 0 stamps s_memtime at the affine kernel's phase boundaries and writes the stamps over the tile's first output row */
 #endif
@@ -1501,7 +1481,7 @@ __global__ __launch_bounds__(FTHREADS, 2) void coupling_affine_dense_v2_kernel(A
     for (int m = 0; m < OT; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float l = (a.has_scale && drow(m, r, hh) < d) ? aff_tanh_out(acc[m][r] * a.scale.c2) * alpha : 0.0f;
+            const float l = (a.has_scale && drow(m, r, hh) < d) ? bgk_tanh_out(acc[m][r] * a.scale.c2) * alpha : 0.0f;
             acc[m][r] = l;
             lsum += l;
         }
@@ -1577,7 +1557,7 @@ typedef float rc_f4u __attribute__((ext_vector_type(4), aligned(4)));
 #define BGK_RC_TS 0
 #endif
 #ifndef BGK_RC_RD
-#define BGK_RC_RD 4           /* (6 / 8: no difference, call 52) */
+#define BGK_RC_RD 4           /* (6 and 8 measured no different) */
 #endif
 
 #if BGK_RC_TS
@@ -1821,31 +1801,28 @@ int bgk_h2_variant = 2;
 
 #if BGK_V2_SAVE
 int bgk_rc_vjp_variant = 2;      /* 2 (default): the element VJP's knots on the hardware forms (FAST); 1: the deterministic forms of bgk_rqs_backward */
-int bgk_launch_rqs_bwd_recompute(const char* what, const float* z1, const void* A2p, float c2, const float* cs_dev, int32_t act,
-                                 const float* y, int64_t ldy, int64_t B, int32_t d, uint64_t circ_mask, int32_t inverse,
-                                 double left, double right, double bottom, double top,
-                                 double min_bin_width, double min_bin_height, double min_derivative, int32_t identity_init,
-                                 const float* g_out, int64_t ldgo, const float* g_dlogp, float* g_y, int64_t ldgy,
-                                 float* g_params, int64_t ldgp, float* g_absmax, void* stream) {
+int bgk_launch_rqs_bwd_recompute(const BgkRqsBwdCall& c) {
+    const char* what = c.what;
+    const int d = c.d;
     RcArgs a;
-    a.z1 = z1; a.A2 = reinterpret_cast<const uint4*>(A2p); a.c2 = c2; a.cs_dev = cs_dev;
+    a.z1 = c.z1; a.A2 = reinterpret_cast<const uint4*>(c.A2p); a.c2 = c.c2; a.cs_dev = c.cs_dev;
     a.n_chunks = (d + DPC - 1) / DPC;
     a.last_tiles = ((d - (a.n_chunks - 1) * DPC) * PPD + 31) / 32;
-    a.y = y; a.ldy = ldy; a.B = B; a.d = d; a.nc_mask = ~circ_mask & (d >= 64 ? ~0ull : ((1ull << d) - 1ull)); a.inverse = inverse;
-    BGK_CHECK_ARG(ldy < (1 << 24) && ldgo < (1 << 24) && ldgy < (1 << 24) && ldgp < (1 << 24), "%s: row stride too large", what);
-    a.g_out = g_out; a.ldgo = ldgo; a.g_dlogp = g_dlogp; a.g_y = g_y; a.ldgy = ldgy; a.g_params = g_params; a.ldgp = ldgp;
-    a.g_absmax = g_absmax;
-    a.cfg = bgk_make_rqs_cfg(left, right, bottom, top, min_bin_width, min_bin_height, min_derivative, identity_init, KB);
+    a.y = c.y; a.ldy = c.ldy; a.B = c.B; a.d = d; a.nc_mask = ~c.circ_mask & (d >= 64 ? ~0ull : ((1ull << d) - 1ull)); a.inverse = c.inverse;
+    BGK_CHECK_ARG(c.ldy < (1 << 24) && c.ldgo < (1 << 24) && c.ldgy < (1 << 24) && c.ldgp < (1 << 24), "%s: row stride too large", what);
+    a.g_out = c.g_out; a.ldgo = c.ldgo; a.g_dlogp = c.g_dlogp; a.g_y = c.g_y; a.ldgy = c.ldgy; a.g_params = c.g_params; a.ldgp = c.ldgp;
+    a.g_absmax = c.g_absmax;
+    a.cfg = bgk_make_rqs_cfg(c.box, KB);
     a.lds_per_wave = ((128 * ST + 3) / 4) * 4;
     static_assert(128 * ST >= 32 * 128, "the chunk buffer holds the z1 tile");
     const size_t shmem = sizeof(float) * (size_t)FW * a.lds_per_wave;
-    const int64_t n_wg = ((B + 31) / 32 + FW - 1) / FW;
+    const int64_t n_wg = ((c.B + 31) / 32 + FW - 1) / FW;
     BGK_CHECK_ARG(n_wg < (int64_t)0x7fffffff, "%s: batch too large for one launch", what);
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)c.stream;
 #define BGK_LAUNCH(A, F) do { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(coupling_rqs_bwd_recompute_kernel<A, F>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
                               hipLaunchKernelGGL((coupling_rqs_bwd_recompute_kernel<A, F>), dim3((int)n_wg), dim3(FTHREADS), shmem, st, a); } while (0)
 #define BGK_LAUNCH_F(A) do { if (bgk_rc_vjp_variant == 1) BGK_LAUNCH(A, false); else BGK_LAUNCH(A, true); } while (0)
-    if (act == 1) BGK_LAUNCH_F(1); else if (act == 2) BGK_LAUNCH_F(2); else BGK_LAUNCH_F(3);
+    if (c.act == 1) BGK_LAUNCH_F(1); else if (c.act == 2) BGK_LAUNCH_F(2); else BGK_LAUNCH_F(3);
 #undef BGK_LAUNCH_F
 #undef BGK_LAUNCH
     return bgk_launch_status(what);
@@ -1854,46 +1831,42 @@ int bgk_launch_rqs_bwd_recompute(const char* what, const float* z1, const void* 
 
 #if !BGK_V2_AFFTRAIN      /* (the affine training unit holds the affine kernel only) */
 #if BGK_V2_SAVE
-int bgk_launch_rqs_dense_h2v2_train(const char* what, float* z0, float* z1, float* params, int64_t ldp, const int32_t* src_col,
-                                    const float* cond, int64_t ldc, int32_t d_c, int32_t periodic,
+int bgk_launch_rqs_dense_h2v2_train(const BgkRqsDenseCall& c) {
 #elif BGK_V2_BF16
-int bgk_launch_rqs_dense_h2v2_bf16(const char* what, const float* cond, int64_t ldc, int32_t d_c, int32_t periodic,
+int bgk_launch_rqs_dense_h2v2_bf16(const BgkRqsDenseCall& c) {
 #else
-int bgk_launch_rqs_dense_h2v2(const char* what, const float* cond, int64_t ldc, int32_t d_c, int32_t periodic,
+int bgk_launch_rqs_dense_h2v2(const BgkRqsDenseCall& c) {
 #endif
-                              const void* A0p, const void* A1p, const void* A2p, float c0, float c1, float c2, const float* cs_dev,
-                              int32_t act, const float* y, int64_t ldy, int64_t B, int32_t d, uint64_t circ_mask, int32_t inverse,
-                              double left, double right, double bottom, double top,
-                              double min_bin_width, double min_bin_height, double min_derivative, int32_t identity_init,
-                              float* out, int64_t ldo, float* dlogp, int32_t accumulate, int32_t* bin_idx, int32_t* oob_count,
-                              void* stream, const BgkCondSegs* segs, int32_t row_order) {
+    const char* what = c.what;
+    const int d = c.d, d_c = c.d_c, periodic = c.periodic, inverse = c.inverse;
+    const BgkSplineBox& box = c.box;
     V2Args a;
 #if BGK_V2_SAVE || BGK_V2_BF16
-    BGK_CHECK_ARG(row_order == 1, "%s: output-layer row order %d (this instance takes order 1)", what, row_order);
+    BGK_CHECK_ARG(c.row_order == 1, "%s: output-layer row order %d (this instance takes order 1)", what, c.row_order);
     constexpr bool regp = false;
 #else
-    BGK_CHECK_ARG(row_order == 1 || row_order == 2, "%s: output-layer row order %d (1 | 2)", what, row_order);
-    const bool regp = row_order == 2;
+    BGK_CHECK_ARG(c.row_order == 1 || c.row_order == 2, "%s: output-layer row order %d (1 | 2)", what, c.row_order);
+    const bool regp = c.row_order == 2;
 #endif
     const int n_in = periodic ? 2 * d_c : d_c;
-    BGK_CHECK_ARG(make_cond_segs(a.cs, cond, ldc, d_c, segs), "%s: bad conditioning segments", what);
+    BGK_CHECK_ARG(make_cond_segs(a.cs, c.cond, c.ldc, d_c, c.segs), "%s: bad conditioning segments", what);
     a.d_c = d_c; a.periodic = periodic;
-    a.y = y; a.ldy = ldy; a.out = out; a.ldo = ldo; a.d = d; a.magic_d = magic_div(d);
-    a.B = B; a.dlogp = dlogp; a.accumulate = accumulate; a.bin_idx = bin_idx; a.oob_count = oob_count;
-    a.A0 = reinterpret_cast<const uint4*>(A0p); a.A1 = reinterpret_cast<const uint4*>(A1p); a.A2 = reinterpret_cast<const uint4*>(A2p);
+    a.y = c.y; a.ldy = c.ldy; a.out = c.out; a.ldo = c.ldo; a.d = d; a.magic_d = magic_div(d);
+    a.B = c.B; a.dlogp = c.dlogp; a.accumulate = c.accumulate; a.bin_idx = c.bin_idx; a.oob_count = c.oob_count;
+    a.A0 = reinterpret_cast<const uint4*>(c.A0p); a.A1 = reinterpret_cast<const uint4*>(c.A1p); a.A2 = reinterpret_cast<const uint4*>(c.A2p);
     a.S0 = (n_in + 1 + 15) / 16;
     a.n_chunks = (d + DPC - 1) / DPC;
     a.last_tiles = ((d - (a.n_chunks - 1) * DPC) * PPD + 31) / 32;
-    a.c0 = c0; a.c1 = c1; a.c2 = c2; a.cs_dev = cs_dev;
-    a.circ_mask = circ_mask;
-    a.sc.left = (float)left; a.sc.right = (float)right;
+    a.c0 = c.c0; a.c1 = c.c1; a.c2 = c.c2; a.cs_dev = c.cs_dev;
+    a.circ_mask = c.circ_mask;
+    a.sc.left = (float)box.left; a.sc.right = (float)box.right;
     /* bgflow forward = nflows inverse: the heights are searched, the widths evaluated; bgflow inverse: the other way round */
-    const SetK sw = make_set(left, right, min_bin_width, KB), sh = make_set(bottom, top, min_bin_height, KB);
+    const SetK sw = make_set(box.left, box.right, box.min_bin_width, KB), sh = make_set(box.bottom, box.top, box.min_bin_height, KB);
     a.sc.sa = inverse ? sw : sh;
     a.sc.sb = inverse ? sh : sw;
-    const double beta = identity_init ? (0.6931471805599453 / (1.0 - min_derivative)) : 1.0;
-    a.sc.beta = (float)beta; a.sc.kout = (float)(0.6931471805599453 / (double)(float)beta); a.sc.min_d = (float)min_derivative;
-    const TilePlan tp = plan_tiles(a.cs, d_c, periodic, y, ldy, out, ldo, d, 128 * ST);
+    const double beta = box.identity_init ? (0.6931471805599453 / (1.0 - box.min_derivative)) : 1.0;
+    a.sc.beta = (float)beta; a.sc.kout = (float)(0.6931471805599453 / (double)(float)beta); a.sc.min_d = (float)box.min_derivative;
+    const TilePlan tp = plan_tiles(a.cs, d_c, periodic, c.y, c.ldy, c.out, c.ldo, d, 128 * ST);
     a.nfs = tp.nfs; a.ys = tp.ys; a.stage = tp.stage; a.y_dma = tp.y_dma; a.out_lin = tp.out_lin;
     BGK_CHECK_ARG(32 * a.nfs + 16 <= 128 * ST, "%s: %d conditioner input features do not fit the LDS tile", what, n_in);
     a.p_floats = 128 * ST;
@@ -1903,17 +1876,17 @@ int bgk_launch_rqs_dense_h2v2(const char* what, const float* cond, int64_t ldc, 
     }
     a.lds_per_wave = ((a.p_floats + 32 * a.ys + 32 + 3) / 4) * 4;
 #if BGK_V2_SAVE
-    a.z0 = z0; a.z1 = z1; a.params = params; a.ldp = ldp; a.src_col = src_col;
+    a.z0 = c.z0; a.z1 = c.z1; a.params = c.params; a.ldp = c.ldp; a.src_col = c.src_col;
 #endif
     const size_t shmem = sizeof(float) * (size_t)FW * a.lds_per_wave;
-    const int64_t n_wg = ((B + 31) / 32 + FW - 1) / FW;
+    const int64_t n_wg = ((c.B + 31) / 32 + FW - 1) / FW;
     BGK_CHECK_ARG(n_wg < (int64_t)0x7fffffff, "%s: batch too large for one launch", what);
     BGK_CHECK_ARG((int64_t)32 * (d > d_c ? d : d_c) < (1 << 16), "%s: tile index range", what);
-    BGK_CHECK_ARG(ldy < (1 << 24) && ldo < (1 << 24), "%s: row stride too large", what);
+    BGK_CHECK_ARG(c.ldy < (1 << 24) && c.ldo < (1 << 24), "%s: row stride too large", what);
     const int grid = (int)n_wg;
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)c.stream;
 #if BGK_V2_SAVE
-#define BGK_LAUNCH(A, I) do { if (params) hipLaunchKernelGGL((coupling_rqs_dense_h2v2_kernel<A, I, true>), dim3(grid), dim3(FTHREADS), shmem, st, a); \
+#define BGK_LAUNCH(A, I) do { if (c.params) hipLaunchKernelGGL((coupling_rqs_dense_h2v2_kernel<A, I, true>), dim3(grid), dim3(FTHREADS), shmem, st, a); \
                               else hipLaunchKernelGGL((coupling_rqs_dense_h2v2_kernel<A, I, false>), dim3(grid), dim3(FTHREADS), shmem, st, a); } while (0)
 #elif BGK_V2_BF16
 #define BGK_LAUNCH(A, I) hipLaunchKernelGGL((coupling_rqs_dense_h2v2_kernel<A, I>), dim3(grid), dim3(FTHREADS), shmem, st, a)
@@ -1921,8 +1894,8 @@ int bgk_launch_rqs_dense_h2v2(const char* what, const float* cond, int64_t ldc, 
 #define BGK_LAUNCH(A, I) do { if (regp) hipLaunchKernelGGL((coupling_rqs_dense_h2v2_kernel<A, I, true, true>), dim3(grid), dim3(FTHREADS), shmem, st, a); \
                               else hipLaunchKernelGGL((coupling_rqs_dense_h2v2_kernel<A, I>), dim3(grid), dim3(FTHREADS), shmem, st, a); } while (0)
 #endif
-    if (act == 1) { if (inverse) BGK_LAUNCH(1, 1); else BGK_LAUNCH(1, 0); }
-    else if (act == 2) { if (inverse) BGK_LAUNCH(2, 1); else BGK_LAUNCH(2, 0); }
+    if (c.act == 1) { if (inverse) BGK_LAUNCH(1, 1); else BGK_LAUNCH(1, 0); }
+    else if (c.act == 2) { if (inverse) BGK_LAUNCH(2, 1); else BGK_LAUNCH(2, 0); }
     else { if (inverse) BGK_LAUNCH(3, 1); else BGK_LAUNCH(3, 0); }
 #undef BGK_LAUNCH
     return bgk_launch_status(what);
@@ -1934,16 +1907,12 @@ int bgk_launch_rqs_dense_h2v2(const char* what, const float* cond, int64_t ldc, 
  * Returns BGK_EUNSUPPORTED (no error text) for any other combination: bgk_fused_affine.hip::affine_dense_launch then runs its
  * streaming kernel. */
 #if BGK_V2_AFFTRAIN
-int bgk_launch_affine_dense_v2_train(const BgkAffTrainSave* save,
-                               const float* cond, int64_t ldc, int32_t d_c, int32_t periodic,
+int bgk_launch_affine_dense_v2_train(const BgkAffTrainSave* save, const BgkAffDenseCall& c) {
 #else
-int bgk_launch_affine_dense_v2(const float* cond, int64_t ldc, int32_t d_c, int32_t periodic,
+int bgk_launch_affine_dense_v2(const BgkAffDenseCall& c) {
 #endif
-                               const void* sA0, const void* sA1, const void* sA1b, const void* sA2, float sc0, float sc1, float sc1b, float sc2, int32_t s_act,
-                               const void* tA0, const void* tA1, const void* tA1b, const void* tA2, float tc0, float tc1, float tc1b, float tc2, int32_t t_act,
-                               const float* log_alpha, int32_t preserve_volume, int32_t is_circular, int32_t inverse,
-                               const float* y, int64_t ldy, int64_t B, int32_t d,
-                               float* out, int64_t ldo, float* dlogp, int32_t accumulate, void* stream, const BgkCondSegs* segs) {
+    const BgkAffNetOps &s = c.shift, &t = c.scale;
+    const int d = c.d, d_c = c.d_c, periodic = c.periodic;
 #if BGK_V2_AFFTRAIN
     const char* what = "bgk_coupling_affine_dense_h2_train";
 #else
@@ -1951,18 +1920,18 @@ int bgk_launch_affine_dense_v2(const float* cond, int64_t ldc, int32_t d_c, int3
 #endif
     AffV2Args a;
     const int n_in = periodic ? 2 * d_c : d_c;
-    BGK_CHECK_ARG(make_cond_segs(a.cs, cond, ldc, d_c, segs), "%s: bad conditioning segments", what);
+    BGK_CHECK_ARG(make_cond_segs(a.cs, c.cond, c.ldc, d_c, c.segs), "%s: bad conditioning segments", what);
     a.d_c = d_c; a.periodic = periodic; a.S0 = (n_in + 1 + 15) / 16;
 #if BGK_V2_AFFTRAIN
-    a.shift = AffV2Net{(const uint4*)sA0, (const uint4*)sA1, (const uint4*)sA1b, (const uint4*)sA2, sc0, sc1, sc1b, sc2, save->s_cs, save->s_z0, save->s_z1};
-    a.scale = AffV2Net{(const uint4*)tA0, (const uint4*)tA1, (const uint4*)tA1b, (const uint4*)tA2, tc0, tc1, tc1b, tc2, save->t_cs, save->t_z0, save->t_z1};
+    a.shift = AffV2Net{(const uint4*)s.A0, (const uint4*)s.A1, (const uint4*)s.A1b, (const uint4*)s.A2, s.c0, s.c1, s.c1b, s.c2, save->s_cs, save->s_z0, save->s_z1};
+    a.scale = AffV2Net{(const uint4*)t.A0, (const uint4*)t.A1, (const uint4*)t.A1b, (const uint4*)t.A2, t.c0, t.c1, t.c1b, t.c2, save->t_cs, save->t_z0, save->t_z1};
     a.mu_out = save->mu; a.s_out = save->s_raw; a.ldms = save->ldms; a.zt = save->ldz == 64 ? 2 : 4;
 #else
-    a.shift = AffV2Net{(const uint4*)sA0, (const uint4*)sA1, (const uint4*)sA1b, (const uint4*)sA2, sc0, sc1, sc1b, sc2};
-    a.scale = AffV2Net{(const uint4*)tA0, (const uint4*)tA1, (const uint4*)tA1b, (const uint4*)tA2, tc0, tc1, tc1b, tc2};
+    a.shift = AffV2Net{(const uint4*)s.A0, (const uint4*)s.A1, (const uint4*)s.A1b, (const uint4*)s.A2, s.c0, s.c1, s.c1b, s.c2};
+    a.scale = AffV2Net{(const uint4*)t.A0, (const uint4*)t.A1, (const uint4*)t.A1b, (const uint4*)t.A2, t.c0, t.c1, t.c1b, t.c2};
 #endif
-    a.has_shift = sA0 != nullptr; a.has_scale = tA0 != nullptr;
-    const bool deep = a.has_shift ? sA1b != nullptr : tA1b != nullptr;
+    a.has_shift = s.A0 != nullptr; a.has_scale = t.A0 != nullptr;
+    const bool deep = a.has_shift ? s.A1b != nullptr : t.A1b != nullptr;
 #if BGK_V2_AFFTRAIN
     if (deep) return BGK_EUNSUPPORTED;
     BGK_CHECK_ARG((!a.has_shift || (save->s_z0 && save->s_z1 && save->mu)) && (!a.has_scale || (save->t_z0 && save->t_z1 && save->s_raw)),
@@ -1971,14 +1940,14 @@ int bgk_launch_affine_dense_v2(const float* cond, int64_t ldc, int32_t d_c, int3
     BGK_CHECK_ARG(save->ldms >= 32 * ((d + 31) / 32) && save->ldms % 4 == 0 && save->ldms < (1 << 20), "%s: ldms = %lld (a multiple of 4, >= 32 ceil(d / 32))",
                   what, (long long)save->ldms);
 #endif
-    if (a.has_shift && a.has_scale && (sA1b != nullptr) != (tA1b != nullptr)) return BGK_EUNSUPPORTED;
-    const int as = a.has_shift ? s_act : t_act, at = a.has_scale ? t_act : s_act;
+    if (a.has_shift && a.has_scale && (s.A1b != nullptr) != (t.A1b != nullptr)) return BGK_EUNSUPPORTED;
+    const int as = a.has_shift ? s.act : t.act, at = a.has_scale ? t.act : s.act;
     if (!((as == at && as >= 1 && as <= 3) || (as == 2 && at == 3))) return BGK_EUNSUPPORTED;
-    a.log_alpha = log_alpha; a.preserve_volume = preserve_volume; a.is_circular = is_circular; a.inverse = inverse;
-    a.y = y; a.ldy = ldy; a.B = B; a.d = d; a.out = out; a.ldo = ldo; a.dlogp = dlogp; a.accumulate = accumulate;
+    a.log_alpha = c.log_alpha; a.preserve_volume = c.preserve_volume; a.is_circular = c.is_circular; a.inverse = c.inverse;
+    a.y = c.y; a.ldy = c.ldy; a.B = c.B; a.d = d; a.out = c.out; a.ldo = c.ldo; a.dlogp = c.dlogp; a.accumulate = c.accumulate;
     a.magic_d = magic_div(d);
     const int OT = (d + 31) / 32;
-    TilePlan tp = plan_tiles(a.cs, d_c, periodic, y, ldy, out, ldo, d, 32 * 128);
+    TilePlan tp = plan_tiles(a.cs, d_c, periodic, c.y, c.ldy, c.out, c.ldo, d, 32 * 128);
     a.nfs = tp.nfs; a.ys = tp.ys; a.stage = tp.stage; a.y_dma = tp.y_dma; a.out_lin = tp.out_lin;
     const int tile_f = 32 * a.nfs + (a.stage == 2 ? 32 * d_c : 0) + 16, park_f = d * SROW;
     a.lds_tile = (((tile_f > park_f ? tile_f : park_f) + 3) / 4) * 4;
@@ -1988,15 +1957,15 @@ int bgk_launch_affine_dense_v2(const float* cond, int64_t ldc, int32_t d_c, int3
 #endif
     a.lds_per_wave = a.lds_tile + ((32 * a.ys + 3) / 4) * 4;
     const size_t shmem = sizeof(float) * (size_t)FW * a.lds_per_wave;
-    const int64_t n_wg = ((B + 31) / 32 + FW - 1) / FW;
+    const int64_t n_wg = ((c.B + 31) / 32 + FW - 1) / FW;
     BGK_CHECK_ARG(n_wg < (int64_t)0x7fffffff, "%s: batch too large for one launch", what);
-    BGK_CHECK_ARG(ldy < (1 << 24) && ldo < (1 << 24) && (int64_t)32 * d_c < 4096 && (int64_t)32 * d < 4096
+    BGK_CHECK_ARG(c.ldy < (1 << 24) && c.ldo < (1 << 24) && (int64_t)32 * d_c < 4096 && (int64_t)32 * d < 4096
                   && OT >= 1 && OT <= 3, "%s: outside the kernel's envelope", what);
     if (shmem > 160 * 1024) {
         bgk_set_error("%s: %d input features / %d dims do not fit the LDS tiles", what, n_in, d);
         return BGK_EUNSUPPORTED;
     }
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)c.stream;
 #define BGK_LAUNCH(S, T, O, D) do { if (shmem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(coupling_affine_dense_v2_kernel<S, T, O, D>), \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
                                     hipLaunchKernelGGL((coupling_affine_dense_v2_kernel<S, T, O, D>), dim3((int)n_wg), dim3(FTHREADS), shmem, st, a); } while (0)

@@ -29,8 +29,11 @@ extern "C" int bgk_coupling_affine_dense_h2_train(const float* const* cond, cons
     const int n_in = periodic ? 2 * d_c : d_c;
     if (n_in > 127) { bgk_set_error("%s: %d input features > 127", what, n_in); return BGK_EUNSUPPORTED; }
     const BgkAffTrainSave save{s_cs, s_z0, s_z1, t_cs, t_z0, t_z1, mu, s_raw, ldms, ldz};
-    return bgk_launch_affine_dense_v2_train(&save, cond[0], ldc[0], d_c, periodic,
-                                            sA0, sA1, nullptr, sA2, 1.0f, 1.0f, 1.0f, 1.0f, s_act,
-                                            tA0, tA1, nullptr, tA2, 1.0f, 1.0f, 1.0f, 1.0f, t_act,
-                                            log_alpha, preserve_volume, is_circular, inverse, y, ldy, B, d, out, ldo, dlogp, accumulate, stream, &segs);
+    BgkAffDenseCall c{};
+    c.cond = cond[0]; c.ldc = ldc[0]; c.d_c = d_c; c.periodic = periodic; c.segs = &segs;
+    c.shift = BgkAffNetOps{.A0 = sA0, .A1 = sA1, .A1b = nullptr, .A2 = sA2, .c0 = 1.0f, .c1 = 1.0f, .c1b = 1.0f, .c2 = 1.0f, .act = s_act};
+    c.scale = BgkAffNetOps{.A0 = tA0, .A1 = tA1, .A1b = nullptr, .A2 = tA2, .c0 = 1.0f, .c1 = 1.0f, .c1b = 1.0f, .c2 = 1.0f, .act = t_act};
+    c.log_alpha = log_alpha; c.preserve_volume = preserve_volume; c.is_circular = is_circular; c.inverse = inverse;
+    c.y = y; c.ldy = ldy; c.B = B; c.d = d; c.out = out; c.ldo = ldo; c.dlogp = dlogp; c.accumulate = accumulate; c.stream = stream;
+    return bgk_launch_affine_dense_v2_train(&save, c);
 }

@@ -168,22 +168,6 @@ __device__ __forceinline__ void r_act_split(RB<HT>& b, const h2_f32x16 (&in)[HT]
     else r_act_split_t<0, HT>(b, in, c);
 }
 
-/* tanh for the OUTPUT layer (log sigma): hardware exp2 + Newton-refined rcp above 0.625 (abs error ~1e-7; +-1 where exp2 overflows),
- * odd polynomial below (same coefficients as bgk_tanhf2) */
-__device__ __forceinline__ float r_tanh_out(float x) {
-    const float ax = __builtin_fabsf(x);
-    const float d = 1.0f + __builtin_amdgcn_exp2f(ax * 2.88539008177792681f);
-    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, bgk_rcp_sat(d), 1.0f), x);
-    const float z = x * x;
-    float p = -5.70498872745e-3f;
-    p = __builtin_fmaf(p, z, 2.06390887954e-2f);
-    p = __builtin_fmaf(p, z, -5.37397155531e-2f);
-    p = __builtin_fmaf(p, z, 1.33314422036e-1f);
-    p = __builtin_fmaf(p, z, -3.33332819422e-1f);
-    const float small = __builtin_fmaf(p * z, x, x);
-    return ax >= 0.625f ? big : small;
-}
-
 template <int HT, int OT>
 __device__ __forceinline__ void net_eval(h2_f32x16 (&res)[OT], const AffNet& n, const float* s_x, int S0, int lane) {
     h2_f32x16 h[HT];
@@ -237,8 +221,8 @@ __device__ __forceinline__ void aff_tail(const FusedAffArgs& a, h2_f32x16 (&mu)[
     for (int m = 0; m < OT; ++m)
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
-            const float l0 = (a.has_scale && h2_row(m, r, hh) < d) ? r_tanh_out(sr[m][r] * a.scale.c2) * alpha : 0.0f;
-            const float l1 = (a.has_scale && h2_row(m, r + 1, hh) < d) ? r_tanh_out(sr[m][r + 1] * a.scale.c2) * alpha : 0.0f;
+            const float l0 = (a.has_scale && h2_row(m, r, hh) < d) ? bgk_tanh_out(sr[m][r] * a.scale.c2) * alpha : 0.0f;
+            const float l1 = (a.has_scale && h2_row(m, r + 1, hh) < d) ? bgk_tanh_out(sr[m][r + 1] * a.scale.c2) * alpha : 0.0f;
             sr[m][r] = l0; sr[m][r + 1] = l1;
             lsum += l0;
             lsum += l1;
@@ -578,8 +562,8 @@ __global__ __launch_bounds__(RW * 64, 1) void coupling_affine_resident_kernel(Fu
         for (int m = 0; m < OT; ++m)
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
-                const float l0 = (a.has_scale && h2_row(m, r, hh) < d) ? r_tanh_out(sr[m][r] * a.scale.c2) * alpha : 0.0f;
-                const float l1 = (a.has_scale && h2_row(m, r + 1, hh) < d) ? r_tanh_out(sr[m][r + 1] * a.scale.c2) * alpha : 0.0f;
+                const float l0 = (a.has_scale && h2_row(m, r, hh) < d) ? bgk_tanh_out(sr[m][r] * a.scale.c2) * alpha : 0.0f;
+                const float l1 = (a.has_scale && h2_row(m, r + 1, hh) < d) ? bgk_tanh_out(sr[m][r + 1] * a.scale.c2) * alpha : 0.0f;
                 sr[m][r] = l0; sr[m][r + 1] = l1;
                 lsum += l0;
                 lsum += l1;
@@ -833,8 +817,8 @@ __global__ __launch_bounds__(RW * 64, 1) void coupling_affine_resident_dma_kerne
         float lsum = 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
-            const float l0 = (a.has_scale && h2_row(0, r, hh) < d) ? r_tanh_out(sr[0][r] * a.scale.c2) * alpha : 0.0f;
-            const float l1 = (a.has_scale && h2_row(0, r + 1, hh) < d) ? r_tanh_out(sr[0][r + 1] * a.scale.c2) * alpha : 0.0f;
+            const float l0 = (a.has_scale && h2_row(0, r, hh) < d) ? bgk_tanh_out(sr[0][r] * a.scale.c2) * alpha : 0.0f;
+            const float l1 = (a.has_scale && h2_row(0, r + 1, hh) < d) ? bgk_tanh_out(sr[0][r + 1] * a.scale.c2) * alpha : 0.0f;
             sr[0][r] = l0; sr[0][r + 1] = l1;
             lsum += l0;
             lsum += l1;
@@ -907,26 +891,24 @@ inline int res_blocks16(int S, int NT, bool bias) { return (S * NT * 2 + (bias ?
 
 }  // namespace
 
-static int affine_dense_launch(const float* cond, int64_t ldc, int32_t d_c, int32_t periodic,
-                               const void* sA0, const void* sA1, const void* sA1b, const void* sA2,
-                               float sc0, float sc1, float sc1b, float sc2, int32_t s_act,
-                               const void* tA0, const void* tA1, const void* tA1b, const void* tA2,
-                               float tc0, float tc1, float tc1b, float tc2, int32_t t_act,
-                               int32_t hidden, const float* log_alpha, int32_t preserve_volume,
-                               int32_t is_circular, int32_t inverse,
-                               const float* y, int64_t ldy, int64_t B, int32_t d,
-                               float* out, int64_t ldo, float* dlogp, int32_t accumulate, void* stream, const BgkCondSegs* segs = nullptr) {
+static int affine_dense_launch(const BgkAffDenseCall& c, int32_t hidden) {
+    const BgkCondSegs* segs = c.segs;
+    const BgkAffNetOps &s = c.shift, &t = c.scale;
     const bool multi = segs && segs->n > 1;       /* several conditioning tensors: the event-threaded width-128 kernel only */
-    if (segs && segs->n >= 1) { cond = segs->ptr[0]; ldc = segs->ld[0]; }
-    BGK_CHECK_ARG(cond && y && out && dlogp, "bgk_coupling_affine_dense_h2: null pointer");
+    const float* cond = segs && segs->n >= 1 ? segs->ptr[0] : c.cond;
+    const int64_t ldc = segs && segs->n >= 1 ? segs->ld[0] : c.ldc;
+    const float *y = c.y, *out = c.out;
+    const int64_t ldy = c.ldy, ldo = c.ldo, B = c.B;
+    const int d = c.d, d_c = c.d_c, periodic = c.periodic;
+    BGK_CHECK_ARG(cond && y && out && c.dlogp, "bgk_coupling_affine_dense_h2: null pointer");
     BGK_CHECK_ARG(B >= 0 && d > 0 && d_c > 0, "bgk_coupling_affine_dense_h2: bad sizes");
-    const int has_shift = sA0 != nullptr, has_scale = tA0 != nullptr;
+    const int has_shift = s.A0 != nullptr, has_scale = t.A0 != nullptr;
     BGK_CHECK_ARG(has_shift || has_scale, "bgk_coupling_affine_dense_h2: no conditioner network");
-    BGK_CHECK_ARG(!has_shift || (sA1 && sA2), "bgk_coupling_affine_dense_h2: incomplete shift network");
-    BGK_CHECK_ARG(!has_scale || (tA1 && tA2 && log_alpha), "bgk_coupling_affine_dense_h2: incomplete scale network");
-    BGK_CHECK_ARG(!(has_scale && is_circular), "Scaling is not compatible with periodicity.");
+    BGK_CHECK_ARG(!has_shift || (s.A1 && s.A2), "bgk_coupling_affine_dense_h2: incomplete shift network");
+    BGK_CHECK_ARG(!has_scale || (t.A1 && t.A2 && c.log_alpha), "bgk_coupling_affine_dense_h2: incomplete scale network");
+    BGK_CHECK_ARG(!(has_scale && c.is_circular), "Scaling is not compatible with periodicity.");
     const int n_in = periodic ? 2 * d_c : d_c;
-    if ((hidden != 64 && hidden != 128) || d > 96 || n_in > 127 || s_act < 0 || s_act > 3 || t_act < 0 || t_act > 3) {
+    if ((hidden != 64 && hidden != 128) || d > 96 || n_in > 127 || s.act < 0 || s.act > 3 || t.act < 0 || t.act > 3) {
         bgk_set_error("bgk_coupling_affine_dense_h2: only hidden = (64,64) | (128,128), d <= 96, <= 127 input features are fused "
                       "(got hidden=%d d=%d n_in=%d)", hidden, d, n_in);
         return BGK_EUNSUPPORTED;
@@ -934,11 +916,11 @@ static int affine_dense_launch(const float* cond, int64_t ldc, int32_t d_c, int3
     if (B == 0) return 0;
     FusedAffArgs a;
     a.cond = cond; a.ldc = ldc; a.d_c = d_c; a.periodic = periodic; a.S0 = (n_in + 1 + 15) / 16;
-    a.shift = AffNet{(const uint4*)sA0, (const uint4*)sA1, (const uint4*)sA2, sc0, sc1, sc2, s_act, (const uint4*)sA1b, sc1b};
-    a.scale = AffNet{(const uint4*)tA0, (const uint4*)tA1, (const uint4*)tA2, tc0, tc1, tc2, t_act, (const uint4*)tA1b, tc1b};
+    a.shift = AffNet{(const uint4*)s.A0, (const uint4*)s.A1, (const uint4*)s.A2, s.c0, s.c1, s.c2, s.act, (const uint4*)s.A1b, s.c1b};
+    a.scale = AffNet{(const uint4*)t.A0, (const uint4*)t.A1, (const uint4*)t.A2, t.c0, t.c1, t.c2, t.act, (const uint4*)t.A1b, t.c1b};
     a.has_shift = has_shift; a.has_scale = has_scale;
-    a.log_alpha = log_alpha; a.preserve_volume = preserve_volume; a.is_circular = is_circular; a.inverse = inverse;
-    a.y = y; a.ldy = ldy; a.B = B; a.d = d; a.out = out; a.ldo = ldo; a.dlogp = dlogp; a.accumulate = accumulate;
+    a.log_alpha = c.log_alpha; a.preserve_volume = c.preserve_volume; a.is_circular = c.is_circular; a.inverse = c.inverse;
+    a.y = y; a.ldy = ldy; a.B = B; a.d = d; a.out = c.out; a.ldo = ldo; a.dlogp = c.dlogp; a.accumulate = c.accumulate;
     a.lds_per_wave = 16 * a.S0 * ASROW;
     a.vec4 = (ldy % 4 == 0) && (ldo % 4 == 0) && (((uintptr_t)y | (uintptr_t)out) % 16 == 0);
     const size_t shmem = sizeof(float) * (size_t)AW * a.lds_per_wave;
@@ -946,9 +928,9 @@ static int affine_dense_launch(const float* cond, int64_t ldc, int32_t d_c, int3
     BGK_CHECK_ARG(n_wg < (int64_t)0x7fffffff, "bgk_coupling_affine_dense_h2: batch too large for one launch");
     a.cvec4 = (ldc % 4 == 0) && ((uintptr_t)cond % 16 == 0);
     const int OT = (d + 31) / 32;
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)c.stream;
     if (multi && !(hidden == 128 && bgk_affine_variant == 2)) return BGK_EUNSUPPORTED;
-    if (hidden == 64 && bgk_affine_variant == 2 && !sA1b && !tA1b) {
+    if (hidden == 64 && bgk_affine_variant == 2 && !s.A1b && !t.A1b) {
         /* weight-resident kernel: operands of both networks in LDS */
         const int n0 = res_blocks16(a.S0, RES_HT, false), n1 = res_blocks16(2 * RES_HT, RES_HT, true), n2 = res_blocks16(2 * RES_HT, OT, true);
         ResOff os{0, 0, 0}, ot{0, 0, 0};
@@ -966,8 +948,8 @@ static int affine_dense_launch(const float* cond, int64_t ldc, int32_t d_c, int3
             if (grid > 256) grid = 256;
             const int c_s = has_shift, c_t = has_scale;
             int pact = 0;                                     /* 16 AS + AT of the pipelined instances: equal activations, or the RealNVP pair ReLU / Tanh */
-            if (has_shift && has_scale && s_act >= 1 && s_act <= 3 && (s_act == t_act || (s_act == 2 && t_act == 3)) && !getenv("BGK_AFFINE_NO_PIPE2"))
-                pact = 16 * s_act + t_act;
+            if (has_shift && has_scale && s.act >= 1 && s.act <= 3 && (s.act == t.act || (s.act == 2 && t.act == 3)) && !getenv("BGK_AFFINE_NO_PIPE2"))
+                pact = 16 * s.act + t.act;
 #define BGK_LAUNCH_DMA(SA, TA) do { auto K = coupling_affine_resident_dma_kernel<DRW, 8, SA, TA>; \
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
             hipLaunchKernelGGL(K, dim3((int)grid), dim3(DRW * 64), dma_shmem, st, a, os, ot, c_s * n0, c_s * n1, c_s * n2, c_t * n0, c_t * n1, c_t * n2, top); } while (0)
@@ -997,9 +979,7 @@ static int affine_dense_launch(const float* cond, int64_t ldc, int32_t d_c, int3
     if (hidden == 128 && bgk_affine_variant == 2 && (size_t)(v2_tile + d * ASROW) * 16 <= 80 * 1024
         && ldc < (1 << 24) && ldy < (1 << 24) && ldo < (1 << 24)) {
         /* width 128: MFMA events threaded through the activation code (bgk_fused2.hip); it declines activation pairs it has no instance for */
-        const int st2 = bgk_launch_affine_dense_v2(cond, ldc, d_c, periodic, sA0, sA1, sA1b, sA2, sc0, sc1, sc1b, sc2, s_act,
-                                                   tA0, tA1, tA1b, tA2, tc0, tc1, tc1b, tc2, t_act, log_alpha, preserve_volume, is_circular,
-                                                   inverse, y, ldy, B, d, out, ldo, dlogp, accumulate, stream, segs);
+        const int st2 = bgk_launch_affine_dense_v2(c);
         if (st2 != BGK_EUNSUPPORTED) return st2;
     }
     if (multi) return BGK_EUNSUPPORTED;
@@ -1020,9 +1000,13 @@ extern "C" int bgk_coupling_affine_dense_h2(const float* cond, int64_t ldc, int3
                                             const float* y, int64_t ldy, int64_t B, int32_t d,
                                             float* out, int64_t ldo, float* dlogp, int32_t accumulate, void* stream) {
     if (B == 0) return 0;       /* an empty batch: nothing to do (its tensors have no storage, hence null pointers) */
-    return affine_dense_launch(cond, ldc, d_c, periodic, sA0, sA1, nullptr, sA2, sc0, sc1, 1.0f, sc2, s_act,
-                               tA0, tA1, nullptr, tA2, tc0, tc1, 1.0f, tc2, t_act, hidden, log_alpha, preserve_volume, is_circular, inverse,
-                               y, ldy, B, d, out, ldo, dlogp, accumulate, stream);
+    BgkAffDenseCall c{};
+    c.cond = cond; c.ldc = ldc; c.d_c = d_c; c.periodic = periodic;
+    c.shift = BgkAffNetOps{.A0 = sA0, .A1 = sA1, .A1b = nullptr, .A2 = sA2, .c0 = sc0, .c1 = sc1, .c1b = 1.0f, .c2 = sc2, .act = s_act};
+    c.scale = BgkAffNetOps{.A0 = tA0, .A1 = tA1, .A1b = nullptr, .A2 = tA2, .c0 = tc0, .c1 = tc1, .c1b = 1.0f, .c2 = tc2, .act = t_act};
+    c.log_alpha = log_alpha; c.preserve_volume = preserve_volume; c.is_circular = is_circular; c.inverse = inverse;
+    c.y = y; c.ldy = ldy; c.B = B; c.d = d; c.out = out; c.ldo = ldo; c.dlogp = dlogp; c.accumulate = accumulate; c.stream = stream;
+    return affine_dense_launch(c, hidden);
 }
 
 extern "C" int bgk_coupling_affine_dense_deep(const float* cond, int64_t ldc, int32_t d_c, int32_t periodic,
@@ -1087,9 +1071,13 @@ extern "C" int bgk_coupling_affine_dense_h3(const float* cond, int64_t ldc, int3
                                             float* out, int64_t ldo, float* dlogp, int32_t accumulate, void* stream) {
     if (B == 0) return 0;       /* an empty batch: nothing to do (its tensors have no storage, hence null pointers) */
     BGK_CHECK_ARG((sA0 == nullptr || sA1b) && (tA0 == nullptr || tA1b), "bgk_coupling_affine_dense_h3: missing third hidden layer");
-    return affine_dense_launch(cond, ldc, d_c, periodic, sA0, sA1, sA1b, sA2, sc0, sc1, sc1b, sc2, s_act,
-                               tA0, tA1, tA1b, tA2, tc0, tc1, tc1b, tc2, t_act, hidden, log_alpha, preserve_volume, is_circular, inverse,
-                               y, ldy, B, d, out, ldo, dlogp, accumulate, stream);
+    BgkAffDenseCall c{};
+    c.cond = cond; c.ldc = ldc; c.d_c = d_c; c.periodic = periodic;
+    c.shift = BgkAffNetOps{.A0 = sA0, .A1 = sA1, .A1b = sA1b, .A2 = sA2, .c0 = sc0, .c1 = sc1, .c1b = sc1b, .c2 = sc2, .act = s_act};
+    c.scale = BgkAffNetOps{.A0 = tA0, .A1 = tA1, .A1b = tA1b, .A2 = tA2, .c0 = tc0, .c1 = tc1, .c1b = tc1b, .c2 = tc2, .act = t_act};
+    c.log_alpha = log_alpha; c.preserve_volume = preserve_volume; c.is_circular = is_circular; c.inverse = inverse;
+    c.y = y; c.ldy = ldy; c.B = B; c.d = d; c.out = out; c.ldo = ldo; c.dlogp = dlogp; c.accumulate = accumulate; c.stream = stream;
+    return affine_dense_launch(c, hidden);
 }
 
 /* the same layers with the conditioning input given as 1..BGK_MAX_COND tensors [B, width_i] that stand for their concatenation along
@@ -1117,9 +1105,13 @@ extern "C" int bgk_coupling_affine_dense_h2_mc(const float* const* cond, const i
     int d_c = 0;
     const int st = affine_mc(cond, ldc, width, n_cond, segs, d_c);
     if (st) return st;
-    return affine_dense_launch(cond[0], ldc[0], d_c, periodic, sA0, sA1, nullptr, sA2, sc0, sc1, 1.0f, sc2, s_act,
-                               tA0, tA1, nullptr, tA2, tc0, tc1, 1.0f, tc2, t_act, hidden, log_alpha, preserve_volume, is_circular, inverse,
-                               y, ldy, B, d, out, ldo, dlogp, accumulate, stream, &segs);
+    BgkAffDenseCall c{};
+    c.cond = cond[0]; c.ldc = ldc[0]; c.d_c = d_c; c.periodic = periodic; c.segs = &segs;
+    c.shift = BgkAffNetOps{.A0 = sA0, .A1 = sA1, .A1b = nullptr, .A2 = sA2, .c0 = sc0, .c1 = sc1, .c1b = 1.0f, .c2 = sc2, .act = s_act};
+    c.scale = BgkAffNetOps{.A0 = tA0, .A1 = tA1, .A1b = nullptr, .A2 = tA2, .c0 = tc0, .c1 = tc1, .c1b = 1.0f, .c2 = tc2, .act = t_act};
+    c.log_alpha = log_alpha; c.preserve_volume = preserve_volume; c.is_circular = is_circular; c.inverse = inverse;
+    c.y = y; c.ldy = ldy; c.B = B; c.d = d; c.out = out; c.ldo = ldo; c.dlogp = dlogp; c.accumulate = accumulate; c.stream = stream;
+    return affine_dense_launch(c, hidden);
 }
 
 extern "C" int bgk_coupling_affine_dense_h3_mc(const float* const* cond, const int64_t* ldc, const int32_t* width, int32_t n_cond, int32_t periodic,
@@ -1137,7 +1129,11 @@ extern "C" int bgk_coupling_affine_dense_h3_mc(const float* const* cond, const i
     int d_c = 0;
     const int st = affine_mc(cond, ldc, width, n_cond, segs, d_c);
     if (st) return st;
-    return affine_dense_launch(cond[0], ldc[0], d_c, periodic, sA0, sA1, sA1b, sA2, sc0, sc1, sc1b, sc2, s_act,
-                               tA0, tA1, tA1b, tA2, tc0, tc1, tc1b, tc2, t_act, hidden, log_alpha, preserve_volume, is_circular, inverse,
-                               y, ldy, B, d, out, ldo, dlogp, accumulate, stream, &segs);
+    BgkAffDenseCall c{};
+    c.cond = cond[0]; c.ldc = ldc[0]; c.d_c = d_c; c.periodic = periodic; c.segs = &segs;
+    c.shift = BgkAffNetOps{.A0 = sA0, .A1 = sA1, .A1b = sA1b, .A2 = sA2, .c0 = sc0, .c1 = sc1, .c1b = sc1b, .c2 = sc2, .act = s_act};
+    c.scale = BgkAffNetOps{.A0 = tA0, .A1 = tA1, .A1b = tA1b, .A2 = tA2, .c0 = tc0, .c1 = tc1, .c1b = tc1b, .c2 = tc2, .act = t_act};
+    c.log_alpha = log_alpha; c.preserve_volume = preserve_volume; c.is_circular = is_circular; c.inverse = inverse;
+    c.y = y; c.ldy = ldy; c.B = B; c.d = d; c.out = out; c.ldo = ldo; c.dlogp = dlogp; c.accumulate = accumulate; c.stream = stream;
+    return affine_dense_launch(c, hidden);
 }

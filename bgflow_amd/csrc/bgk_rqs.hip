@@ -229,6 +229,8 @@ extern "C" int bgk_rqs_transform(const float* y, int64_t ldy, const float* param
                                  int64_t ldo, float* dlogp, int32_t accumulate, int32_t* bin_idx,
                                  int32_t* oob_count, void* stream) {
     if (B == 0) return 0;       /* an empty batch: nothing to do (its tensors have no storage, hence null pointers) */
+    const BgkSplineBox box{.left = left, .right = right, .bottom = bottom, .top = top, .min_bin_width = min_bin_width,
+                           .min_bin_height = min_bin_height, .min_derivative = min_derivative, .identity_init = identity_init};
     BGK_CHECK_ARG(B >= 0 && d > 0 && K > 0, "bgk_rqs_transform: bad sizes B=%lld d=%d K=%d", (long long)B, d, K);
     BGK_CHECK_ARG(y && params && nc_slot && out && dlogp, "bgk_rqs_transform: null pointer");
     BGK_CHECK_ARG(min_bin_width * K <= 1.0 && min_bin_height * K <= 1.0,
@@ -242,7 +244,7 @@ extern "C" int bgk_rqs_transform(const float* y, int64_t ldy, const float* param
     a.P = P;
     BGK_CHECK_ARG(P >= 3 * K * d && P <= 3 * K * d + d && ldp >= P,
                   "bgk_rqs_transform: params width %d (ld %lld) not in [3Kd, 3Kd+d] for d=%d K=%d", P, (long long)ldp, d, K);
-    a.cfg = bgk_make_rqs_cfg(left, right, bottom, top, min_bin_width, min_bin_height, min_derivative, identity_init, K);
+    a.cfg = bgk_make_rqs_cfg(box, K);
     a.Pp = a.P | 1;
     a.magicP = (uint32_t)((0x100000000ull + (uint64_t)a.P - 1) / (uint64_t)a.P);
     /* tile size: largest multiple of 4 samples whose LDS footprint stays under ~52 KiB (3 workgroups

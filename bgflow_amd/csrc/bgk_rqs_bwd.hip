@@ -160,6 +160,8 @@ extern "C" int bgk_rqs_backward(const float* y, int64_t ldy, const float* params
                                 const float* g_dlogp, float* g_y, int64_t ldgy, float* g_params,
                                 int64_t ldgp, float* g_absmax, int32_t params_layout, void* stream) {
     if (B == 0) return 0;       /* an empty batch: nothing to do (its tensors have no storage, hence null pointers) */
+    const BgkSplineBox box{.left = left, .right = right, .bottom = bottom, .top = top, .min_bin_width = min_bin_width,
+                           .min_bin_height = min_bin_height, .min_derivative = min_derivative, .identity_init = identity_init};
     BGK_CHECK_ARG(B >= 0 && d > 0 && K > 0, "bgk_rqs_backward: bad sizes");
     BGK_CHECK_ARG(y && params && nc_slot && g_out && g_dlogp && g_y && g_params, "bgk_rqs_backward: null pointer");
     BGK_CHECK_ARG(params_layout == 0 || (params_layout == 1 && K == 8), "bgk_rqs_backward: params_layout %d (1 = element-major: 8 bins only)", params_layout);
@@ -169,7 +171,7 @@ extern "C" int bgk_rqs_backward(const float* y, int64_t ldy, const float* params
     a.y = y; a.ldy = ldy; a.params = params; a.ldp = ldp; a.nc_slot = nc_slot; a.B = B; a.d = d; a.K = K; a.P = P;
     a.inverse = inverse; a.g_out = g_out; a.ldgo = ldgo; a.g_dlogp = g_dlogp; a.g_y = g_y; a.ldgy = ldgy;
     a.g_params = g_params; a.ldgp = ldgp; a.g_absmax = g_absmax;
-    a.cfg = bgk_make_rqs_cfg(left, right, bottom, top, min_bin_width, min_bin_height, min_derivative, identity_init, K);
+    a.cfg = bgk_make_rqs_cfg(box, K);
     a.Pp = P | 1; a.TS = BWD_TS; a.magicP = 0;
     int64_t n_tiles = (B + BWD_TS - 1) / BWD_TS;
     int grid = (int)(n_tiles < 256 * 16 ? n_tiles : 256 * 16);

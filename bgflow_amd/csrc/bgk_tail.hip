@@ -141,10 +141,6 @@ __device__ __forceinline__ void sincos2pi(float x, float& so, float& co) {
     co = __builtin_amdgcn_cosf(fr);
 }
 
-__device__ __forceinline__ float rcp1(float d) {                          /* 1 / d, one Newton step: ~1 ulp */
-    const float r = __builtin_amdgcn_rcpf(d);
-    return __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
-}
 __device__ __forceinline__ float rsq_nr(float q) {                       /* 1 / sqrt(q), one Newton step: ~1 ulp */
     const float r = __builtin_amdgcn_rsqf(q);
     return r * __builtin_fmaf(-0.5f * q, r * r, 1.5f);
@@ -591,9 +587,9 @@ __global__ __launch_bounds__(TW * 64) void icdf_ic2xyz_uni_kernel(TailArgs a) {
 __device__ __forceinline__ float atan2_fast(float y, float x) {
     const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
     const float mx = __builtin_fmaxf(ax, ay), mn = __builtin_fminf(ax, ay);
-    const float q = mn * rcp1(mx);                                      /* in [0, 1]; 0 / 0 -> handled by the callers' clamps */
+    const float q = mn * bgk_rcp_refined(mx);                           /* in [0, 1]; 0 / 0 -> handled by the callers' clamps */
     const bool big = q > 0.41421356237309503f;
-    const float xr = big ? (q - 1.0f) * rcp1(q + 1.0f) : q;
+    const float xr = big ? (q - 1.0f) * bgk_rcp_refined(q + 1.0f) : q;
     const float z = xr * xr;
     float p = __builtin_fmaf(8.05374449538e-2f, z, -1.38776856032e-1f);
     p = __builtin_fmaf(p, z, 1.99777106478e-1f);
@@ -704,7 +700,7 @@ __global__ __launch_bounds__(TW * 64) void xyz2ic_cdf_uni_kernel(TailArgs a) {
     /* ---- fixed atoms: whitening + cdf map ---- */
     {
         const Desc df = load_desc(desc, 3);
-        const float inv_f = rcp1(__builtin_bit_cast(int, df.f[0]) == 0 ? df.f[2] : df.f[3]);
+        const float inv_f = bgk_rcp_refined(__builtin_bit_cast(int, df.f[0]) == 0 ? df.f[2] : df.f[3]);
         const cf32_t T = (cf32_t)a.T, mean = (cf32_t)a.mean;
         float fz[KMAX];
 #pragma unroll
@@ -739,9 +735,9 @@ __global__ __launch_bounds__(TW * 64) void xyz2ic_cdf_uni_kernel(TailArgs a) {
     int warn = 0;
     const float eps2 = a.eps * a.eps;
     const Desc db = load_desc(desc, 0), da = load_desc(desc, 1), dt = load_desc(desc, 2);
-    const float inv_b = rcp1(__builtin_bit_cast(int, db.f[0]) == 0 ? db.f[2] : db.f[3]);
-    const float inv_a = rcp1(__builtin_bit_cast(int, da.f[0]) == 0 ? da.f[2] : da.f[3]);
-    const float inv_t = rcp1(__builtin_bit_cast(int, dt.f[0]) == 0 ? dt.f[2] : dt.f[3]);
+    const float inv_b = bgk_rcp_refined(__builtin_bit_cast(int, db.f[0]) == 0 ? db.f[2] : db.f[3]);
+    const float inv_a = bgk_rcp_refined(__builtin_bit_cast(int, da.f[0]) == 0 ? da.f[2] : da.f[3]);
+    const float inv_t = bgk_rcp_refined(__builtin_bit_cast(int, dt.f[0]) == 0 ? dt.f[2] : dt.f[3]);
     Rec r = load_rec(recs, 0);
     for (int i = 0; i < n; ++i) {
         const Rec rn = load_rec(recs, i + 1 < n ? i + 1 : i);

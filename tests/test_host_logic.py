@@ -1026,6 +1026,40 @@ def test_exported_symbols_are_the_headers_prototypes():
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
     have = {ln.split()[-1] for ln in out.splitlines() if re.match(r"^[0-9a-f]+ [A-Za-z] ", ln)}
     assert have == want, f"only in the library: {sorted(have - want)}; only in the header: {sorted(want - have)}"
+    sigs = build.abi_signatures()
+    assert set(sigs) == want == set(_lib.ABI_SYMBOLS)
+    handle = _lib.lib()
+    for name, (res, args) in sigs.items():          # every function of the loaded handle carries the header's types
+        fn = getattr(handle, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+
+
+def test_ctypes_signatures_are_derived_from_the_header():
+    """the ctypes table is parsed from include/bgflow_amd.h; four rows written out by hand (no arguments and a string return; the
+    eight spline scalars; unsigned 64- and 32-bit parameters; a 64-bit return)"""
+    from ctypes import c_char_p, c_double as f64, c_int, c_int32 as i32, c_int64 as i64, c_uint32, c_uint64, c_void_p as vp
+    from bgflow_amd import _lib
+    sigs = _lib._SIGNATURES
+    assert sigs["bgk_last_error"] == (c_char_p, [])
+    assert sigs["bgk_rqs_transform"] == (c_int, [vp, i64, vp, i64, i32, vp, i64, i32, i32, i32,
+                                                 f64, f64, f64, f64, f64, f64, f64, i32,
+                                                 vp, i64, vp, i32, vp, vp, vp])
+    assert sigs["bgk_philox_fields"] == (c_int, [c_uint64, c_uint32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, f64, i64, vp, vp])
+    assert sigs["bgk_dense_weight_grad_workspace"] == (i64, [i64, i32, i32])
+
+
+def test_header_parser_refuses_what_it_does_not_know():
+    from bgflow_amd._abi import abi_signatures
+    ok = abi_signatures(text="/* a comment ( */\nint bgk_a(const float* x, int64_t n);\nconst char* bgk_b(void);\n")
+    assert ok == {"bgk_a": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]), "bgk_b": (ctypes.c_char_p, [])}
+    with pytest.raises(ValueError, match="bgk_bad.*size_t n"):
+        abi_signatures(text="int bgk_fine(int32_t a);\nint bgk_bad(const float* x, size_t n);\n")
+    with pytest.raises(ValueError, match=r"bgk_arr.*float x\[3\]"):
+        abi_signatures(text="int bgk_arr(float x[3]);\n")
+    with pytest.raises(ValueError, match="bgk_ret"):
+        abi_signatures(text="long bgk_ret(int32_t a);\n")
+    with pytest.raises(ValueError, match="bgk_open.*cannot split"):
+        abi_signatures(text="int bgk_open(int32_t a, int (*cb)(int));\n")
 
 
 def test_kl_trainer_runs_a_generators_own_kldiv():
