@@ -9,7 +9,7 @@ Only the modules on the accelerated hot path are mapped; a
 import sys
 import types
 
-# reference module path (relative to the package root) -> name of the flat module here that holds its public names
+# reference module path (relative to the package root) -> name of the flat module here that holds its public names (a tuple: several)
 _MAP = {
     "nn": None,
     "nn.dense": "dense",
@@ -31,11 +31,13 @@ _MAP = {
     "nn.flow.crd_transform": "ic",
     "nn.flow.crd_transform.ic": "ic",
     "nn.flow.crd_transform.pca": "ic",
-    "distribution": "distributions",
+    "distribution": ("distributions", "particles"),
     "distribution.distributions": "distributions",
-    "distribution.normal": "distributions",
+    "distribution.normal": ("distributions", "particles"),
     "distribution.product": "distributions",
-    "distribution.energy": "distributions",
+    "distribution.energy": ("distributions", "particles"),
+    "distribution.energy.lennard_jones": "particles",
+    "distribution.energy.multi_double_well_potential": "particles",
     "distribution.energy.base": "distributions",
     "distribution.energy.double_well": "distributions",
     "distribution.energy.clipped": "clipped",
@@ -63,7 +65,7 @@ def register(root, package):
             continue
         mod = types.ModuleType(full, f"alias of {package.__name__}.{flat}" if flat else "namespace")
         mod.__path__ = []          # behaves like a package: sub-imports go through sys.modules
-        if flat is not None:
+        for flat in ((flat,) if isinstance(flat, str) else flat or ()):
             src = getattr(package, flat)
             names = getattr(src, "__all__", None) or [n for n in vars(src) if not n.startswith("__")]
             for n in names:

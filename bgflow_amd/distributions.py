@@ -6,6 +6,8 @@ Minimal, API-compatible subset of bgflow/distribution: ``Energy`` / ``Sampler`` 
 domain-mapping layers), ``UniformDistribution`` / ``SloppyUniform`` (distributions.py:71-117),
 ``ProductDistribution`` (product.py:13-117) and ``DoubleWellEnergy`` (energy/double_well.py:10-22).
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -287,6 +289,11 @@ class _CutKLSumsFn(torch.autograd.Function):
         return (None, None, None, None, None, None, None if g_dl is None else g_dl.reshape(dl_shape), *gx)
 
 
+# the plan of a particle-system energy over ONE tensor (csrc/bgk_pair.hip; the classes of particles.py describe themselves with it):
+# nine entries, so every caller that folds FIELD plans (length 5, or 6 with wrappers) passes it by
+PairPlan = collections.namedtuple("PairPlan", "kind n_particles n_dims p0 p1 p2 p3 osc_scale temperature")
+
+
 def _own_methods(obj, cls):
     """``obj`` evaluates its energy with the code of ``cls`` (no subclass override of ``energy`` / ``_energy``)"""
     return all(getattr(type(obj), name, None) is getattr(cls, name) for name in ("energy", "_energy"))
@@ -333,6 +340,12 @@ def _kernel_plan(dist, temperature):
     one the wrappers' settings (``_wrapper_plan``); callers that cannot fold them in treat a plan of another length than 5 as None."""
     describe = getattr(dist, "_kernel_fields", None)
     if describe is None:
+        pair = getattr(dist, "_pair_kernel", None)
+        if pair is not None:             # a particle system over one tensor (particles.py): a plan kind of its own, a PairPlan
+            owner = next(c for c in type(dist).__mro__ if "_pair_kernel" in c.__dict__)
+            if any(getattr(type(dist), name, None) is not getattr(owner, name, None) for name in ("energy", "_energy")):
+                return None
+            return pair(temperature)
         if hasattr(dist, "delegate"):
             from . import clipped
             if isinstance(dist, (clipped.LinLogCutEnergy, clipped.GradientClippedEnergy)):
@@ -351,6 +364,9 @@ def kernel_energy(dist, xs, temperature=1.0):
     plan = _kernel_plan(dist, temperature)
     if plan is None:
         return None
+    if isinstance(plan, PairPlan):
+        from . import particles
+        return particles.pair_energy(plan, xs)
     specs, dims, c_in, c_out, t_eff, *wrap = plan
     if not (_fields_ok(xs, dims) and isinstance(temperature, (int, float)) and temperature > 0):
         return None
@@ -366,6 +382,9 @@ def kl_loss_sums(target, xs, dlogp, temperature=1.0, drop_nonfinite=False):
     plan = _kernel_plan(target, temperature)
     if plan is None:
         return None
+    if isinstance(plan, PairPlan):       # a particle system over one tensor: the same pair from bgk_pair_energy_kl_sums
+        from . import particles
+        return particles.pair_kl_loss_sums(plan, xs, dlogp, drop_nonfinite)
     specs, dims, c_in, c_out, t_eff, *wrap = plan
     if not (_fields_ok(xs, dims) and isinstance(temperature, (int, float)) and temperature > 0 and torch.is_tensor(dlogp)
             and dlogp.is_cuda and dlogp.numel() == xs[0].shape[0]):

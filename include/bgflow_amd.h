@@ -682,6 +682,33 @@ int bgk_clip_gradient(const float* g, int64_t ldg, int64_t B, int32_t D, double 
                       float* out, int64_t ldo, double* workspace, int32_t nblk, void* stream);
 int bgk_linlogcut(const float* v, const float* g, int64_t n, double high, double max_val, float* out, void* stream);
 
+/* Many-particle targets and their prior over ONE tensor x [B, n_particles * n_dims] (row stride ldx, particle-major rows), one launch
+ * forward and one backward (csrc/bgk_pair.hip), replacing the [B, n, n, d] distance-vector tensor / the cdist matrix and the op chain
+ * on it of:
+ *   kind 0  LennardJonesPotential._energy (distribution/energy/lennard_jones.py:9-64 with utils/geometry.py:5-48, 93-111):
+ *           p0 = eps, p1 = rm:  eps sum_{i<j} [(rm / r_ij)^12 - 2 (rm / r_ij)^6], r_ij = sqrt(|x_i - x_j|^2 + 1e-6),
+ *           + osc_scale 0.5 sum_i |x_i - xbar|^2 (xbar: the sample's centroid; osc_scale = 0: no oscillator)
+ *   kind 1  MultiDoubleWellPotential._energy (distribution/energy/multi_double_well_potential.py:37-43, utils/geometry.py:114-139):
+ *           p0 = a, p1 = b, p2 = c, p3 = offset:  sum_{i<j} [a (d_ij - offset)^4 + b (d_ij - offset)^2 + c], d_ij = |x_i - x_j|
+ *   kind 2  MeanFreeNormalDistribution._energy (distribution/normal.py:267-283): osc_scale 0.5 sum_i |x_i - xbar|^2, osc_scale = 1 / std^2
+ * u[b] = e(x[b]) / temperature (energy/base.py:124-146).  Pairs are added in a fixed ascending (i, j) order: deterministic.
+ * Envelope: 2 <= n_particles <= 64, 1 <= n_dims <= 3; BGK_EUNSUPPORTED beyond (the caller's torch formula then).
+ * bgk_pair_energy_kl_sums: the same launch + the KL integrand's sums as in bgk_energy_fields: loss_sums [2] (f64) = [sum_b (u[b] -
+ *   dlogp[b]), samples kept] (non-finite ones dropped if drop_nonfinite), workspace partial [nblk, 2] floats, fixed summation order.
+ * bgk_pair_energy_backward: g_x[b] = g_row (d e / d x)(x[b]) / temperature (row stride ldg); g_row = g_u[b], or, in the loss-sum form
+ *   (g_u == NULL), g_scalar[0] for the kept samples (u: the energies the forward wrote), with g_dlogp[b] = -g_row (g_dlogp may be
+ *   NULL).  The double-well pair gradient at d_ij = 0 is 0, like torch.cdist's backward. */
+int bgk_pair_energy(const float* x, int64_t ldx, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
+                    double p0, double p1, double p2, double p3, double osc_scale, double temperature, float* u, void* stream);
+int bgk_pair_energy_kl_sums(const float* x, int64_t ldx, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
+                            double p0, double p1, double p2, double p3, double osc_scale, double temperature,
+                            float* u, const float* dlogp, int32_t drop_nonfinite, float* partial, int32_t nblk, double* loss_sums,
+                            void* stream);
+int bgk_pair_energy_backward(const float* x, int64_t ldx, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
+                             double p0, double p1, double p2, double p3, double osc_scale, double temperature,
+                             const float* g_u, const float* g_scalar, const float* u, const float* dlogp, int32_t drop_nonfinite,
+                             float* g_dlogp, float* g_x, int64_t ldg, void* stream);
+
 /* Prior sampling in one launch from a counter-based generator (Philox4x32-10; counter = (global row, field, 4-column block, offset),
  * key = seed: independent of launch geometry and of the sharding of a batch, row0 = first global row of this launch), replacing
  * torch.randn / Uniform.sample + the shift / scale ops of NormalDistribution._sample_with_temperature (distribution/normal.py:74-92),
