@@ -22,6 +22,7 @@ _MAP = {
     "nn.flow.cdf": "cdf",
     "nn.flow.modulo": "modulo",
     "nn.flow.torchtransform": "modulo",
+    "nn.flow.diffeq": "dynamics",
     "nn.flow.stochastic": "flow",
     "nn.flow.stochastic.augment": "flow",
     "nn.flow.transformer": "transformer",

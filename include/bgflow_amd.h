@@ -709,6 +709,36 @@ int bgk_pair_energy_backward(const float* x, int64_t ldx, int64_t B, int32_t n_p
                              const float* g_u, const float* g_scalar, const float* u, const float* dlogp, int32_t drop_nonfinite,
                              float* g_dlogp, float* g_x, int64_t ldg, void* stream);
 
+/* Equivariant kernel dynamics of a particle system x [B, n_particles * n_dims] (contiguous rows) and its fixed-step integration
+ * (csrc/bgk_kdyn.hip), one lane per sample, the sample's row in LDS -- no [B, n, n - 1, d] distance-vector or [B, n, n - 1, K] kernel tensor:
+ *   d_ij = sqrt(|x_i - x_j|^2 + 1e-6); g_k = exp(-(d - mus[k])^2 exp(neg_log_gammas[k])^2), s = sum_k g_k, kern_k = g_k / (1e-6 + s),
+ *   dkern_k = dg_k / (1e-6 + s) - g_k sum(dg) / (1e-6 + s^2); F = sum_k kern_k w_k + c, dF = sum_k dkern_k w_k with the time contraction
+ *   w_k = sum_o weights[k, o] tau_o, c = sum_k importance[k]^2 w_k + sum_o bias[o] tau_o, tau = the normalised radial basis functions of t
+ *   over mus_time [n_out] (mus_time == NULL: n_out = 1, tau = 1), formed inside the launch from the raw parameter tensors.
+ * bgk_kdyn_eval replaces KernelDynamics.forward (nn/flow/dynamics/kernel_dynamic.py:59-116 with utils/rbf_kernels.py:134-144 and
+ *   utils/geometry.py:5-48, 93-111): forces[b, i] = sum_{j != i} (x_i - x_j) F_ij, divergence[b] = sum_i sum_{j != i} (d_ij dF_ij + n_dims F_ij)
+ *   (divergence == NULL: not computed; the reference returns its negative).
+ * bgk_kdyn_eval_backward replaces the autograd graph of those lines: g_x [B, n d] and g_wc [n_kernels + 1] = the gradients of (w, c)
+ *   given g_forces [B, n d] and g_div [B] (NULL: zero), reduced over the batch through partial [nblk, n_kernels + 1] (block partials,
+ *   finished in f64) in a fixed order; the chain from (w, c) to the parameters is the caller's.
+ * bgk_kdyn_integrate replaces the solver loop that DiffEqFlow._run_ode (nn/flow/diffeq.py:51-96) hands DensityDynamics (dynamics/density.py:
+ *   11-38) and InversedDynamics (dynamics/inversed.py:14-34) to: n_steps steps h = t_max / n_steps of classical RK4 (method 0; stages at t,
+ *   t + h/2, t + h/2, t + h) or explicit Euler (method 1) of d x / dt = forces(t, x), d dlogp / dt = divergence(t, x) from dlogp = 0;
+ *   inverse != 0: -forces(t_max - t, x) and -divergence.  One launch: x is read once, y [B, n d] and dlogp [B] are written once.
+ * Envelope: 2 <= n_particles <= 64, 1 <= n_dims <= 3, 1 <= n_kernels <= 64, 1 <= n_out <= 16; BGK_EUNSUPPORTED beyond. */
+int bgk_kdyn_eval(const float* x, int64_t B, int32_t n_particles, int32_t n_dims, int32_t n_kernels, int32_t n_out,
+                  const float* mus, const float* neg_log_gammas, const float* weights, const float* bias, const float* importance,
+                  const float* mus_time, const float* neg_log_gammas_time, double t, float* forces, float* divergence, void* stream);
+int bgk_kdyn_eval_backward(const float* x, int64_t B, int32_t n_particles, int32_t n_dims, int32_t n_kernels, int32_t n_out,
+                           const float* mus, const float* neg_log_gammas, const float* weights, const float* bias,
+                           const float* importance, const float* mus_time, const float* neg_log_gammas_time, double t,
+                           const float* g_forces, const float* g_div, float* g_x, float* partial, int32_t nblk, float* g_wc,
+                           void* stream);
+int bgk_kdyn_integrate(const float* x, int64_t B, int32_t n_particles, int32_t n_dims, int32_t n_kernels, int32_t n_out,
+                       const float* mus, const float* neg_log_gammas, const float* weights, const float* bias, const float* importance,
+                       const float* mus_time, const float* neg_log_gammas_time, double t_max, int32_t n_steps, int32_t method,
+                       int32_t inverse, float* y, float* dlogp, void* stream);
+
 /* Prior sampling in one launch from a counter-based generator (Philox4x32-10; counter = (global row, field, 4-column block, offset),
  * key = seed: independent of launch geometry and of the sharding of a batch, row0 = first global row of this launch), replacing
  * torch.randn / Uniform.sample + the shift / scale ops of NormalDistribution._sample_with_temperature (distribution/normal.py:74-92),
