@@ -32,7 +32,7 @@ _MAP = {
     "nn.flow.crd_transform": "ic",
     "nn.flow.crd_transform.ic": "ic",
     "nn.flow.crd_transform.pca": "ic",
-    "distribution": ("distributions", "particles"),
+    "distribution": ("distributions", "particles", "sampling"),
     "distribution.distributions": "distributions",
     "distribution.normal": ("distributions", "particles"),
     "distribution.product": "distributions",
@@ -42,7 +42,9 @@ _MAP = {
     "distribution.energy.base": "distributions",
     "distribution.energy.double_well": "distributions",
     "distribution.energy.clipped": "clipped",
-    "distribution.sampling": "distributions",
+    "distribution.sampling": ("distributions", "sampling"),
+    "distribution.sampling.iterative": "sampling",
+    "distribution.sampling.mcmc": "sampling",
     "distribution.sampling.base": "distributions",
     "distribution.sampling.dataset": "training",
     "nn.training": "training",

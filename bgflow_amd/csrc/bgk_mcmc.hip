@@ -1,0 +1,185 @@
+/* bgk_mcmc.hip -- Metropolis chains on a particle-system target, a whole run of steps in one launch
+ *   MCMCStep._step with a GaussianProposal (bgflow/distribution/sampling/mcmc.py:29-46, 86-122) and metropolis_accept (mcmc.py:192-222):
+ *     x' = x + noise_std eps,  accept iff min(0, -(e(x') - e(x)) / T) >= log r,  eps ~ N(0, 1)^{n d}, r ~ U(0, 1)
+ *   on the targets of bgk_pair.hip (kind 0 Lennard-Jones, 1 multi-double-well, 2 mean-free normal).  In stock ops one step is about a dozen
+ *   launches (randn_like, add, the energy's op chain, rand_like, log, min, compare, two where) over a state of n d <= 192 floats per chain;
+ *   here the state of a chain never leaves LDS between recorded frames.
+ *
+ * Like bgk_pair.hip / bgk_kdyn.hip: one wave per workgroup, ONE LANE PER CHAIN, a tile of rows staged coalesced through LDS with the odd
+ * row stride S = (n d) | 1 (lane r reads word r S + k: distinct banks within a 32-lane group).  Two LDS tiles, A and B: a lane's current
+ * row is in one, its proposal is written into the other, and accepting is a per-lane flip of which is which -- no copy.  B starts a
+ * multiple of 32 words behind A, so lanes whose current rows sit in different tiles still hit distinct banks.  The steps run in lockstep
+ * across the wave (the accept flag only selects); a recorded frame leaves as one coalesced tile store through a per-row tile flag in LDS.
+ *
+ * Energy: bgk_pair_row_energy of bgk_pair_terms.h -- the code of pair_energy_kernel, so e is, bit for bit, what bgk_pair_energy returns for
+ * the row at temperature 1.  min(0, .) is dropped: log r < 0, so v >= log r and min(0, v) >= log r decide alike.  A proposal whose energy
+ * is NaN or +inf is rejected by the comparison itself, as in the reference.
+ *
+ * Random numbers: explicit (noise [n_steps, B, n d] and uniforms [n_steps, B], read by the chain's lane) or drawn in the kernel from
+ * Philox4x32-10 in the counter layout of bgk_philox.hip (bgk_philox.h): counter = (global chain low, high, field << 20 | 4-column block,
+ * offset + step), field 0 = the n d normals (Box-Muller), field 1 / block 0 / word 0 = the uniform.  The stream is a pure function of
+ * (seed, step, global chain, column): the same bits whatever the tiling, the grid, row0 sharding or the split of a run into launches, and
+ * the bits bgk_philox_fields writes for (seed, offset + step) with fields [normal n d, uniform 1].
+ *
+ * Envelope 2 <= n <= 64, 1 <= d <= 3.  Dynamic LDS <= 63,488 B: rows per tile = the most (<= 64) with (round32(rows S) + rows S) 4 B within
+ * it; lanes beyond the rows only stage and store:
+ *   n d = 192 (S = 193): 41 rows, 63,396 B       LJ13 (S = 39): 64 rows, 19,968 B       DW4 (S = 9): 64 rows, 4,608 B */
+#include "bgk_common.h"
+#include "bgk_pair_terms.h"
+#include "bgk_philox.h"
+
+namespace {
+
+constexpr int MC_THREADS = 64;
+constexpr int MC_MAX_N = 64, MC_MAX_D = 3;
+constexpr int MC_LDS_DYNAMIC = 63488;
+constexpr int MC_MAX_GRID = 256 * 16;
+
+struct McArgs {
+    float* x; int64_t B, row0;
+    int n, nd, rows, tile_b; uint32_t magic;            /* tile_b: word offset of the second tile, a multiple of 32 */
+    float p0, p1, p2, p3, osc;
+    float* e; int e_valid;
+    float temperature; const float* temperatures;
+    float noise_std; int n_steps;
+    const float* noise; const float* uniforms;
+    uint32_t seed_lo, seed_hi, offset;
+    float* traj; float* traj_e; int traj_every;
+    int* n_accepted; int accumulate;
+};
+
+template <int D, int KIND>
+__global__ __launch_bounds__(MC_THREADS) void pair_mcmc_kernel(McArgs a) {
+    extern __shared__ float s_mem[];
+    __shared__ int s_sel[MC_THREADS];                   /* which tile holds row r's current state */
+    const int tid = threadIdx.x, n = a.n, nd = a.nd, S = a.nd | 1;
+    const float rm2 = a.p1 * a.p1;
+    const int64_t n_tiles = (a.B + a.rows - 1) / a.rows;
+    for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const int64_t b0 = t * a.rows;
+        const int rows = (int)((a.B - b0) < a.rows ? (a.B - b0) : a.rows);
+        for (int i = tid; i < rows * nd; i += MC_THREADS) {
+            const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * nd;
+            s_mem[r * S + c] = a.x[(b0 + r) * nd + c];
+        }
+        __syncthreads();
+        const bool active = tid < rows;
+        const int64_t b = b0 + (active ? tid : 0);
+        const uint64_t grow = (uint64_t)(a.row0 + b);
+        const uint32_t r_lo = (uint32_t)grow, r_hi = (uint32_t)(grow >> 32);
+        int cur = 0, acc = 0;
+        float e = 0.0f, temp = 1.0f;
+        if (active) {
+            temp = a.temperatures ? a.temperatures[b] : a.temperature;
+            e = a.e_valid ? a.e[b] : (float)bgk_pair_row_energy<D, KIND>(s_mem + tid * S, n, a.p0, a.p1, a.p2, a.p3, rm2, a.osc);
+        }
+        int frame = 0, since = 0;
+        for (int step = 0; step < a.n_steps; ++step) {
+            if (active) {
+                const float* xc = s_mem + (cur ? a.tile_b : 0) + tid * S;
+                float* xp = s_mem + (cur ? 0 : a.tile_b) + tid * S;
+                float r;
+                if (a.noise) {
+                    const float* ns = a.noise + ((int64_t)step * a.B + b) * nd;
+                    for (int c = 0; c < nd; ++c) xp[c] = xc[c] + a.noise_std * ns[c];
+                    r = a.uniforms[(int64_t)step * a.B + b];
+                } else {
+                    const uint32_t off = a.offset + (uint32_t)step;
+                    uint32_t o[4];
+                    for (int cb = 0; 4 * cb < nd; ++cb) {
+                        philox4x32_10(r_lo, r_hi, (uint32_t)cb, off, a.seed_lo, a.seed_hi, o);
+                        float v[4];
+                        philox_normal4(o, v);
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const int c = 4 * cb + q;
+                            if (c < nd) xp[c] = xc[c] + a.noise_std * v[q];
+                        }
+                    }
+                    philox4x32_10(r_lo, r_hi, 1u << 20, off, a.seed_lo, a.seed_hi, o);
+                    r = u01(o[0]);
+                }
+                const float ep = (float)bgk_pair_row_energy<D, KIND>(xp, n, a.p0, a.p1, a.p2, a.p3, rm2, a.osc);
+                const bool accept = -(ep - e) / temp >= bgk_logf(r);      /* false for a NaN on either side */
+                cur = accept ? cur ^ 1 : cur;
+                e = accept ? ep : e;
+                acc += accept ? 1 : 0;
+            }
+            if (a.traj && ++since == a.traj_every) {    /* uniform over the wave */
+                since = 0;
+                s_sel[tid] = cur;
+                __syncthreads();
+                float* dst = a.traj + ((int64_t)frame * a.B + b0) * nd;
+                for (int i = tid; i < rows * nd; i += MC_THREADS) {
+                    const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * nd;
+                    dst[i] = s_mem[(s_sel[r] ? a.tile_b : 0) + r * S + c];
+                }
+                if (active && a.traj_e) a.traj_e[(int64_t)frame * a.B + b] = e;
+                ++frame;
+                __syncthreads();                        /* the next proposals overwrite rows this store reads */
+            }
+        }
+        s_sel[tid] = cur;
+        __syncthreads();
+        for (int i = tid; i < rows * nd; i += MC_THREADS) {
+            const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * nd;
+            a.x[(b0 + r) * nd + c] = s_mem[(s_sel[r] ? a.tile_b : 0) + r * S + c];
+        }
+        if (active) {
+            a.e[b] = e;
+            if (a.n_accepted) a.n_accepted[b] = a.accumulate ? a.n_accepted[b] + acc : acc;
+        }
+        __syncthreads();
+    }
+}
+
+template <int KIND>
+void launch_mcmc(int d, int grid, size_t lds, hipStream_t s, const McArgs& a) {
+    if (d == 1) hipLaunchKernelGGL((pair_mcmc_kernel<1, KIND>), dim3(grid), dim3(MC_THREADS), lds, s, a);
+    else if (d == 2) hipLaunchKernelGGL((pair_mcmc_kernel<2, KIND>), dim3(grid), dim3(MC_THREADS), lds, s, a);
+    else hipLaunchKernelGGL((pair_mcmc_kernel<3, KIND>), dim3(grid), dim3(MC_THREADS), lds, s, a);
+}
+
+}  // namespace
+
+extern "C" int bgk_pair_mcmc(float* x, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
+                             double p0, double p1, double p2, double p3, double osc_scale,
+                             float* e, int32_t e_valid, double temperature, const float* temperatures,
+                             double noise_std, int32_t n_steps, const float* noise, const float* uniforms,
+                             uint64_t seed, uint32_t offset, int64_t row0,
+                             float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream) {
+    BGK_CHECK_ARG(B >= 0 && row0 >= 0 && n_steps >= 0, "bgk_pair_mcmc: bad batch size / row0 / n_steps");
+    BGK_CHECK_ARG(kind >= 0 && kind <= 2, "bgk_pair_mcmc: kind %d (0 Lennard-Jones, 1 multi-double-well, 2 mean-free normal)", kind);
+    if (!(n_particles >= 2 && n_particles <= MC_MAX_N && n_dims >= 1 && n_dims <= MC_MAX_D)) {
+        bgk_set_error("bgk_pair_mcmc: %d particles in %d dimensions are outside the kernel's envelope (2..%d particles, 1..%d dimensions)",
+                      n_particles, n_dims, MC_MAX_N, MC_MAX_D);
+        return BGK_EUNSUPPORTED;
+    }
+    BGK_CHECK_ARG(temperatures || temperature > 0.0, "bgk_pair_mcmc: the temperature must be positive");
+    BGK_CHECK_ARG(noise_std >= 0.0, "bgk_pair_mcmc: noise_std must not be negative");
+    BGK_CHECK_ARG((noise != nullptr) == (uniforms != nullptr), "bgk_pair_mcmc: noise and uniforms go together");
+    BGK_CHECK_ARG(!traj_e || traj, "bgk_pair_mcmc: traj_e without traj");
+    BGK_CHECK_ARG(!traj || traj_every >= 1, "bgk_pair_mcmc: traj_every %d", traj_every);
+    if (B == 0) return 0;
+    BGK_CHECK_ARG(x && e, "bgk_pair_mcmc: null tensor");
+    McArgs a{};
+    a.x = x; a.B = B; a.row0 = row0; a.n = n_particles; a.nd = n_particles * n_dims;
+    a.magic = (uint32_t)(((1ull << 32) + (uint64_t)a.nd - 1) / (uint64_t)a.nd);
+    const int S = a.nd | 1;
+    int rows = MC_THREADS;
+    while ((((rows * S + 31) & ~31) + rows * S) * (int)sizeof(float) > MC_LDS_DYNAMIC) --rows;
+    a.rows = rows; a.tile_b = (rows * S + 31) & ~31;
+    a.p0 = (float)p0; a.p1 = (float)p1; a.p2 = (float)p2; a.p3 = (float)p3; a.osc = (float)osc_scale;
+    a.e = e; a.e_valid = e_valid != 0; a.temperature = (float)temperature; a.temperatures = temperatures;
+    a.noise_std = (float)noise_std; a.n_steps = n_steps; a.noise = noise; a.uniforms = uniforms;
+    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.offset = offset;
+    a.traj = traj; a.traj_e = traj_e; a.traj_every = traj_every; a.n_accepted = n_accepted; a.accumulate = accumulate != 0;
+    const size_t lds = (size_t)(a.tile_b + rows * S) * sizeof(float);
+    const int64_t n_tiles = (B + rows - 1) / rows;
+    const int grid = (int)(n_tiles < MC_MAX_GRID ? n_tiles : MC_MAX_GRID);
+    hipStream_t s = (hipStream_t)stream;
+    if (kind == 0) launch_mcmc<0>(n_dims, grid, lds, s, a);
+    else if (kind == 1) launch_mcmc<1>(n_dims, grid, lds, s, a);
+    else launch_mcmc<2>(n_dims, grid, lds, s, a);
+    return bgk_launch_status("bgk_pair_mcmc");
+}

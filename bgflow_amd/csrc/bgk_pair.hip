@@ -22,6 +22,7 @@
  *   backward  x tile + gradient tile + 64 row scales: 64 rows while 2 x 64 x S x 4 + 256 <= 65,536 B (S <= 127: 65,280 B),
  *             else 32 rows: 2 x 32 x 193 x 4 + 256 = 49,664 B at n d = 192 (lanes 32..63 only stage and store). */
 #include "bgk_common.h"
+#include "bgk_pair_terms.h"
 
 namespace {
 
@@ -45,26 +46,6 @@ __device__ __forceinline__ void stage_rows(const PairArgs& a, int64_t b0, int ro
     }
 }
 
-/* 0.5 sum_i |x_i - xbar|^2 of the lane's row (f64 sum of f32 squares); xbar[k] left in `mean` */
-template <int D>
-__device__ __forceinline__ double centroid_term(const float* xr, int n, float* mean) {
-    float inv_n = 1.0f / (float)n;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        float s = 0.0f;
-        for (int i = 0; i < n; ++i) s += xr[i * D + k];
-        mean[k] = s * inv_n;
-    }
-    double acc = 0.0;
-    for (int i = 0; i < n; ++i) {
-        float q = 0.0f;
-#pragma unroll
-        for (int k = 0; k < D; ++k) { const float t = xr[i * D + k] - mean[k]; q += t * t; }
-        acc += (double)q;
-    }
-    return 0.5 * acc;
-}
-
 template <int D, int KIND>
 __global__ __launch_bounds__(PR_THREADS) void pair_energy_kernel(PairArgs a) {
     extern __shared__ float s_x[];
@@ -80,30 +61,7 @@ __global__ __launch_bounds__(PR_THREADS) void pair_energy_kernel(PairArgs a) {
         __syncthreads();
         if (tid < rows) {
             const float* xr = s_x + tid * S;
-            double e = 0.0;
-            if (KIND != 2) {
-                for (int i = 0; i + 1 < n; ++i) {
-                    float xi[D];
-#pragma unroll
-                    for (int k = 0; k < D; ++k) xi[k] = xr[i * D + k];
-                    float row = 0.0f;
-                    for (int j = i + 1; j < n; ++j) {
-                        float d2 = 0.0f;
-#pragma unroll
-                        for (int k = 0; k < D; ++k) { const float t = xi[k] - xr[j * D + k]; d2 += t * t; }
-                        if (KIND == 0) {
-                            const float s = rm2 / (d2 + 1e-6f), s3 = s * s * s;
-                            row += s3 * s3 - 2.0f * s3;
-                        } else {
-                            const float t = __builtin_sqrtf(d2) - a.p3, t2 = t * t;
-                            row += (a.p0 * t2) * t2 + a.p1 * t2 + a.p2;
-                        }
-                    }
-                    e += (double)row;
-                }
-                if (KIND == 0) e *= (double)a.p0;
-            }
-            if (a.osc != 0.0f) { float mean[D]; e += (double)a.osc * centroid_term<D>(xr, n, mean); }
+            const double e = bgk_pair_row_energy<D, KIND>(xr, n, a.p0, a.p1, a.p2, a.p3, rm2, a.osc);   /* bgk_pair_terms.h */
             const float u = (float)e * a.inv_t;
             a.u[b0 + tid] = u;
             if (a.partial) {

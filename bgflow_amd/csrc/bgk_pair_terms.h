@@ -1,0 +1,62 @@
+/* bgk_pair_terms.h -- the energy of ONE particle-system sample, as bgk_pair.hip's forward and bgk_mcmc.hip's chain step both add it up:
+ * the pairs i < j in ascending (i, j) order, the terms of one i in f32, the n - 1 row sums and the centroid term in f64.  One source, so
+ * the two kernels give the same bits for the same row (the library is built with -ffp-contract=off: the same sequence of IEEE ops).
+ *   KIND 0  Lennard-Jones        p0 = eps, rm2 = rm^2:  eps sum [(rm2 / (d2 + 1e-6))^6 - 2 (rm2 / (d2 + 1e-6))^3]
+ *   KIND 1  multi-double-well    p0 = a, p1 = b, p2 = c, p3 = offset:  sum [a t^4 + b t^2 + c], t = sqrt(d2) - offset
+ *   KIND 2  mean-free normal     no pair term
+ *   + osc 0.5 sum_i |x_i - xbar|^2 when osc != 0
+ * xr: the sample's row [n D] (LDS or registers' backing memory), read-only. */
+#ifndef BGK_PAIR_TERMS_H
+#define BGK_PAIR_TERMS_H
+
+/* 0.5 sum_i |x_i - xbar|^2 of the row (f64 sum of f32 squares); xbar[k] left in `mean` */
+template <int D>
+__device__ __forceinline__ double bgk_pair_centroid_term(const float* xr, int n, float* mean) {
+    float inv_n = 1.0f / (float)n;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        float s = 0.0f;
+        for (int i = 0; i < n; ++i) s += xr[i * D + k];
+        mean[k] = s * inv_n;
+    }
+    double acc = 0.0;
+    for (int i = 0; i < n; ++i) {
+        float q = 0.0f;
+#pragma unroll
+        for (int k = 0; k < D; ++k) { const float t = xr[i * D + k] - mean[k]; q += t * t; }
+        acc += (double)q;
+    }
+    return 0.5 * acc;
+}
+
+/* e(x) of the row at temperature 1, before the rounding to f32 */
+template <int D, int KIND>
+__device__ __forceinline__ double bgk_pair_row_energy(const float* xr, int n, float p0, float p1, float p2, float p3, float rm2, float osc) {
+    double e = 0.0;
+    if (KIND != 2) {
+        for (int i = 0; i + 1 < n; ++i) {
+            float xi[D];
+#pragma unroll
+            for (int k = 0; k < D; ++k) xi[k] = xr[i * D + k];
+            float row = 0.0f;
+            for (int j = i + 1; j < n; ++j) {
+                float d2 = 0.0f;
+#pragma unroll
+                for (int k = 0; k < D; ++k) { const float t = xi[k] - xr[j * D + k]; d2 += t * t; }
+                if (KIND == 0) {
+                    const float s = rm2 / (d2 + 1e-6f), s3 = s * s * s;
+                    row += s3 * s3 - 2.0f * s3;
+                } else {
+                    const float t = __builtin_sqrtf(d2) - p3, t2 = t * t;
+                    row += (p0 * t2) * t2 + p1 * t2 + p2;
+                }
+            }
+            e += (double)row;
+        }
+        if (KIND == 0) e *= (double)p0;
+    }
+    if (osc != 0.0f) { float mean[D]; e += (double)osc * bgk_pair_centroid_term<D>(xr, n, mean); }
+    return e;
+}
+
+#endif

@@ -14,6 +14,7 @@
  * Layout: lane = row of a 64-row tile; a field's [64][d] tile is assembled in LDS (the tile's memory image when rows are contiguous)
  * and leaves as coalesced stores; the energy 0.5 sum n^2 accumulates per lane in column order (deterministic). */
 #include "bgk_common.h"
+#include "bgk_philox.h"
 
 namespace {
 
@@ -28,18 +29,6 @@ struct PArgs {
     int lds_per_wave;
 };
 typedef const __attribute__((address_space(4))) PArgs* pargs_t;
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&o)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-__device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * 5.9604644775390625e-08f; }   /* 2^-24 */
 
 __global__ __launch_bounds__(PW * 64) void philox_fields_kernel(PArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -65,13 +54,7 @@ __global__ __launch_bounds__(PW * 64) void philox_fields_kernel(PArgs a) {
             philox4x32_10(r_lo, r_hi, ((uint32_t)fi << 20) | (uint32_t)cb, a.offset, a.seed_lo, a.seed_hi, o);
             float v[4];
             if (kind == 1) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const float rad = __builtin_sqrtf(-2.0f * bgk_logf(u01(o[2 * h])));
-                    float sn, cs;
-                    bgk_sincos2pif(u01(o[2 * h + 1]), &sn, &cs);
-                    v[2 * h] = rad * cs; v[2 * h + 1] = rad * sn;
-                }
+                philox_normal4(o, v);              /* bgk_philox.h */
             } else {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = u01(o[q]);

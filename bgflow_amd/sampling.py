@@ -1,0 +1,598 @@
+"""Iterative samplers: ``SamplerState`` / ``SamplerStep`` / ``IterativeSampler`` (bgflow/distribution/sampling/iterative.py,
+_iterative_helpers.py) and Metropolis Monte Carlo -- ``GaussianProposal``, ``LatentProposal``, ``MCMCStep``, ``GaussianMCMCSampler``,
+``metropolis_accept`` (sampling/mcmc.py) -- with the reference's constructor signatures, defaults and state bookkeeping.
+
+The general path is the reference's step in torch ops over ``energy.energy(...)``: any ``Energy``, any proposal, any device and dtype.
+
+The fused path (csrc/bgk_mcmc.hip, entry bgk_pair_mcmc) runs whole chains in one launch: a particle-system target with a ``PairPlan``
+(2..64 particles in 1..3 dimensions), a plain ``GaussianProposal`` with a numeric ``noise_std``, one contiguous f32 HIP samples tensor
+[B, n d] or [B, n, d], no box vectors, the default samples hook, and a positive number or a tensor of B positive values as
+``target_temperatures``.  ``MCMCStep.forward`` is then one launch for its ``n_steps``; an ``IterativeSampler`` whose only step is such a
+step (and whose ``extract_sample_hook`` is the default) runs ``stride * n_steps`` steps per iteration inside the launch and has the kernel
+write every recorded state straight into the ``[n, B, ...]`` result.  ``MCMCStep.fused = False`` forces the general path.
+
+Not in the reference: ``MCMCStep.n_accepted`` (per-chain accepted steps) / ``n_proposed``, ``MCMCStep.feed_noise`` and ``chain_offset``.
+"""
+import dataclasses
+import warnings
+from typing import Sequence
+
+import torch
+
+from .distributions import PairPlan, Sampler, _FusedSampling, _kernel_plan
+from .utils import pack_tensor_in_list, pack_tensor_in_tuple, unpack_tensor_tuple
+
+__all__ = ["AbstractSamplerState", "SamplerState", "SamplerStep", "IterativeSampler", "GaussianProposal", "LatentProposal", "MCMCStep",
+           "GaussianMCMCSampler", "metropolis_accept", "default_set_samples_hook", "default_extract_sample_hook"]
+
+# The most Metropolis steps one launch of bgk_pair_mcmc runs; longer runs are split (bitwise the same chain: the random stream and the
+# carried f32 energies do not depend on the split), so that no single launch holds a shared GPU for long.  Measured on an MI355X
+# (tools/mcmc_time.py, its last line): the widest shape of the envelope -- Lennard-Jones, n = 64, d = 3, 2^16 chains -- takes 70.46 ms
+# for one launch of 64 steps (70.29 .. 70.74 over three rounds), 1.10 ms per step, so 224 steps are 0.247 s.
+MCMC_MAX_STEPS_PER_LAUNCH = 224
+
+
+# ---- state ---------------------------------------------------------------------------------------------------------------------
+class AbstractSamplerState:
+    """Interface of the internal state of iterative samplers (_iterative_helpers.py:9-71)."""
+
+    def as_dict(self):
+        raise NotImplementedError()
+
+    def _replace(self, **kwargs):
+        raise NotImplementedError()
+
+    def evaluate_energy_force(self, energy_model, evaluate_energies=True, evaluate_forces=True):
+        """a new state with up-to-date energies / forces"""
+        state = self.as_dict()
+        evaluate_energies = evaluate_energies and not state["energies_up_to_date"]
+        energies = energy_model.energy(*state["samples"])[..., 0] if evaluate_energies else state["energies"]
+        evaluate_forces = evaluate_forces and not state["forces_up_to_date"]
+        forces = energy_model.force(*state["samples"]) if evaluate_forces else state["forces"]
+        return self.replace(energies=energies, forces=forces)
+
+    def replace(self, **kwargs):
+        """a new state with updated fields: setting energies / forces marks them up to date, setting samples alone marks them
+        stale; samples are mapped to the primary cell of the box vectors"""
+        state_dict = self.as_dict()
+        if "energies" in kwargs:
+            kwargs = {**kwargs, "energies_up_to_date": True}
+        elif "samples" in kwargs:
+            kwargs = {**kwargs, "energies_up_to_date": False}
+        if "forces" in kwargs:
+            kwargs = {**kwargs, "forces_up_to_date": True}
+        elif "samples" in kwargs:
+            kwargs = {**kwargs, "forces_up_to_date": False}
+        box_vectors = None
+        if "box_vectors" in kwargs:
+            box_vectors = kwargs["box_vectors"]
+        elif "box_vectors" in state_dict:
+            box_vectors = state_dict["box_vectors"]
+        if "samples" in kwargs and box_vectors is not None:
+            kwargs = {**kwargs, "samples": tuple(_map_to_primary_cell(x, cell) for x, cell in zip(kwargs["samples"], box_vectors))}
+        return self._replace(**kwargs)
+
+
+def default_set_samples_hook(x):
+    """by default, use samples as is"""
+    return x
+
+
+def default_extract_sample_hook(state):
+    """the samples of a state"""
+    return state.as_dict()["samples"]
+
+
+def _bmv(m, bv):
+    return torch.einsum("ij,...j->...i", m, bv)
+
+
+def _map_to_primary_cell(x, cell):
+    """coordinates x [..., n] mapped into the primary cell of the lattice vectors ``cell`` (column-wise, upper triangular)"""
+    if cell is None:
+        return x
+    n = torch.floor(_bmv(torch.inverse(cell), x))
+    return x - _bmv(cell, n)
+
+
+@dataclasses.dataclass(frozen=True)
+class _SamplerStateData:
+    samples: Sequence[torch.Tensor]
+    velocities: Sequence[torch.Tensor] = None
+    energies: torch.Tensor = None
+    forces: Sequence[torch.Tensor] = None
+    box_vectors: Sequence[torch.Tensor] = None
+    energies_up_to_date: bool = False
+    forces_up_to_date: bool = False
+
+
+class SamplerState(AbstractSamplerState):
+    """A minibatch of samples with optional velocities, energies, forces and box vectors (iterative.py:49-118); samples, velocities,
+    forces and box vectors are stored as tuples of tensors."""
+    _tuple_kwargs = ["samples", "velocities", "forces", "box_vectors"]
+
+    def __init__(self, dataclass=_SamplerStateData, set_samples_hook=default_set_samples_hook, **kwargs):
+        self._dataclass = dataclass
+        self.set_samples_hook = set_samples_hook
+        kwargs_with_tuples = dict()
+        for key, value in kwargs.items():
+            if key in self._tuple_kwargs:
+                value = pack_tensor_in_tuple(value)
+            kwargs_with_tuples[key] = value
+        self._data = dataclass(**kwargs_with_tuples)
+
+    def __getattr__(self, field):
+        try:
+            return getattr(self.__dict__["_data"], field)
+        except (AttributeError, KeyError) as e:
+            raise AttributeError(f"SamplerState has no attribute '{field}'; {str(e)}")
+
+    def __str__(self):
+        return str(self._data)
+
+    def as_dict(self):
+        return dataclasses.asdict(self._data)
+
+    def _replace(self, **kwargs):
+        data = {**self.as_dict(), **kwargs}
+        if "samples" in kwargs:
+            data["samples"] = self.set_samples_hook(data["samples"])
+        return SamplerState(dataclass=self._dataclass, set_samples_hook=self.set_samples_hook, **data)
+
+
+# ---- the kernel launch ------------------------------------------------------------------------------------------------------------
+def pair_mcmc(plan, x, e, e_valid, temperature, noise_std, n_steps, noise=None, uniforms=None, seed=0, offset=0, row0=0,
+              traj=None, traj_e=None, traj_every=0, n_accepted=None, accumulate=False):
+    """One launch of bgk_pair_mcmc: ``n_steps`` Metropolis steps of the chains x [B, n d] (f32, contiguous, HIP; updated IN PLACE) on
+    the target of the ``PairPlan``.  e [B]: raw energies (temperature 1), read if ``e_valid``, written for the final state.
+    ``temperature``: a positive number or an f32 tensor [B].  noise [n_steps, B, n d] and uniforms [n_steps, B], or neither (Philox
+    numbers of (seed, offset + step, chain row0 + b)).  traj [n_steps // traj_every, B, n d] / traj_e [n_steps // traj_every, B]: the
+    state / energy after every ``traj_every``-th step.  n_accepted [B] (int32): written, or added to with ``accumulate``."""
+    from . import _lib
+    B, nd = x.shape
+    if nd != plan.n_particles * plan.n_dims:
+        raise ValueError(f"pair_mcmc: x has {nd} columns, the target {plan.n_particles} x {plan.n_dims}")
+    if (noise is None) != (uniforms is None):
+        raise ValueError("pair_mcmc: noise and uniforms go together")
+    temps = temperature if torch.is_tensor(temperature) else None
+    n_frames = n_steps // traj_every if traj is not None else 0
+    floats = [(x, (B, nd)), (e, (B,)), (temps, (B,)), (noise, (n_steps, B, nd)), (uniforms, (n_steps, B)), (traj, (n_frames, B, nd)),
+              (traj_e, (n_frames, B))]
+    for t, shape in floats + [(n_accepted, (B,))]:
+        if t is None:
+            continue
+        want = torch.int32 if t is n_accepted else torch.float32
+        if not (t.is_cuda and t.device == x.device and t.dtype == want and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"pair_mcmc: expected a contiguous {want} HIP tensor of shape {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    if traj is not None and traj_every < 1:
+        raise ValueError("pair_mcmc: traj_every must be at least 1")
+    with torch.cuda.device(x.device):
+        st = _lib.lib().bgk_pair_mcmc(_lib.ptr(x), B, plan.n_particles, plan.n_dims, plan.kind, plan.p0, plan.p1, plan.p2, plan.p3,
+                                      plan.osc_scale, _lib.ptr(e), int(bool(e_valid)), 1.0 if temps is not None else float(temperature),
+                                      _lib.ptr(temps), float(noise_std), int(n_steps), _lib.ptr(noise), _lib.ptr(uniforms),
+                                      int(seed) & (2 ** 64 - 1), int(offset) & 0xffffffff, int(row0), _lib.ptr(traj), _lib.ptr(traj_e),
+                                      int(traj_every), _lib.ptr(n_accepted), int(bool(accumulate)), _lib.stream_ptr(x.device))
+    _lib.check(st, "bgk_pair_mcmc")
+
+
+def _launch_plan(unit, count, cap):
+    """[(steps, traj_every, frames)] of the launches that run ``count`` units of ``unit`` steps and record the state after every unit,
+    no launch longer than ``cap`` steps (traj_every = 0: a piece of a unit longer than the cap, nothing recorded)"""
+    cap = max(1, int(cap))
+    out = []
+    if unit <= cap:
+        per = cap // unit
+        done = 0
+        while done < count:
+            k = min(per, count - done)
+            out.append((k * unit, unit, k))
+            done += k
+    else:
+        for _ in range(count):
+            left = unit
+            while left > cap:
+                out.append((cap, 0, 0))
+                left -= cap
+            out.append((left, left, 1))
+    return out
+
+
+# ---- steps ----------------------------------------------------------------------------------------------------------------------
+class SamplerStep(torch.nn.Module):
+    """Base class of sampler steps: ``_step`` maps a state to a state; ``forward`` applies it ``n_steps`` times (iterative.py:195-214)."""
+
+    def __init__(self, n_steps=1):
+        super().__init__()
+        self._n_steps = n_steps
+
+    def _step(self, state):
+        raise NotImplementedError()
+
+    def forward(self, state):
+        for _ in range(self._n_steps):
+            state = self._step(state)
+        return state
+
+
+class GaussianProposal(torch.nn.Module):
+    """Normal distributed displacement of the samples by ``noise_std`` (mcmc.py:29-46)."""
+
+    def __init__(self, noise_std=0.1):
+        super().__init__()
+        self._noise_std = noise_std
+
+    def forward(self, state):
+        delta_log_prob = 0.0  # symmetric density
+        proposed_state = state.replace(samples=tuple(x + torch.randn_like(x) * self._noise_std for x in state.as_dict()["samples"]))
+        return proposed_state, delta_log_prob
+
+
+class LatentProposal(torch.nn.Module):
+    """Proposal in the latent space of a flow whose forward direction is latent-to-target (mcmc.py:49-83):
+    delta_log_prob = base delta - (logdet of the forward map at the proposal + logdet of the inverse map at the state)."""
+
+    def __init__(self, flow, base_proposal=GaussianProposal(noise_std=0.1), flow_kwargs=dict()):
+        super().__init__()
+        self.flow = flow
+        self.base_proposal = base_proposal
+        self.flow_kwargs = flow_kwargs
+
+    def forward(self, state):
+        *z, logdet_inverse = self.flow.forward(*state.as_dict()["samples"], inverse=True, **self.flow_kwargs)
+        proposed_latent, delta_log_prob = self.base_proposal.forward(state.replace(samples=z))
+        *proposed_samples, logdet_forward = self.flow.forward(*proposed_latent.as_dict()["samples"])
+        delta_log_prob = delta_log_prob - (logdet_forward + logdet_inverse)
+        return proposed_latent.replace(samples=proposed_samples), delta_log_prob[:, 0]
+
+
+def metropolis_accept(current_energies, proposed_energies, proposal_delta_log_prob):
+    """Metropolis criterion (mcmc.py:192-222): True where min(0, -(u' - u) - delta_log_prob) >= log r, r ~ U(0, 1); a NaN or +inf
+    proposed energy is never accepted (the comparison is False)."""
+    log_prob = -(proposed_energies - current_energies) - proposal_delta_log_prob
+    log_acceptance_ratio = torch.min(torch.zeros_like(proposed_energies), log_prob)
+    log_random = torch.rand_like(log_acceptance_ratio).log()
+    return log_acceptance_ratio >= log_random
+
+
+class MCMCStep(SamplerStep, _FusedSampling):
+    """Metropolis Monte Carlo on ``target_energy`` with ``proposal`` at ``target_temperatures`` (a number or a tensor broadcast along the
+    batch), ``n_steps`` steps per ``forward`` (mcmc.py:86-122).
+
+    Where the fused path applies (module docstring) ``forward`` is one launch of bgk_pair_mcmc on a copy of the samples.  Its random
+    numbers come from the Philox stream of this object (``_FusedSampling``: key from ``torch.initial_seed()``, rank and stream id, the
+    per-object counter is the index of the next step, both travel in ``state_dict``), unless ``feed_noise`` has handed it explicit ones.
+    ``n_accepted`` (int32 [B]) counts the accepted steps per chain and ``n_proposed`` the steps taken, on either path."""
+    fused = True
+
+    def __init__(self, target_energy, proposal=GaussianProposal(), target_temperatures=1.0, n_steps=1):
+        super().__init__(n_steps=n_steps)
+        self.target_energy = target_energy
+        self.target_temperatures = target_temperatures
+        self.proposal = proposal
+        self.n_accepted = None
+        self.n_proposed = 0
+        self.chain_offset = 0          # global index of this state's first chain: chains sharded over processes draw the numbers of the whole
+        self._fed = None
+
+    # -- the general path: the reference's step
+    def _step(self, state):
+        state = state.evaluate_energy_force(self.target_energy, evaluate_forces=False)
+        proposed_state, delta_log_prob = self.proposal.forward(state)
+        proposed_state = proposed_state.evaluate_energy_force(self.target_energy, evaluate_forces=False)
+        new_dict = proposed_state.as_dict()
+        old_dict = state.as_dict()
+        accept = metropolis_accept(
+            current_energies=old_dict["energies"] / self.target_temperatures,
+            proposed_energies=new_dict["energies"] / self.target_temperatures,
+            proposal_delta_log_prob=delta_log_prob
+        )
+        counts = accept.to(torch.int32)
+        if self.n_accepted is None or self.n_accepted.shape != counts.shape or self.n_accepted.device != counts.device:
+            self.n_accepted, self.n_proposed = counts, 0
+        else:
+            self.n_accepted = self.n_accepted + counts
+        self.n_proposed += 1
+        return state.replace(
+            samples=tuple(torch.where(accept[..., None], new, old) for new, old in zip(new_dict["samples"], old_dict["samples"])),
+            energies=torch.where(accept, new_dict["energies"], old_dict["energies"])
+        )
+
+    # -- the fused path
+    def feed_noise(self, noise, uniforms):
+        """explicit random numbers for the next fused steps instead of the Philox stream: noise [S, B, n d] standard normals and
+        uniforms [S, B] (f32, on the samples' device); each fused step consumes one row of either, ``feed_noise(None, None)``
+        returns to the Philox stream"""
+        if noise is None and uniforms is None:
+            self._fed = None
+            return self
+        if noise.dim() != 3 or uniforms.dim() != 2 or uniforms.shape != noise.shape[:2]:
+            raise ValueError("feed_noise: noise [S, B, n d] and uniforms [S, B]")
+        self._fed = [noise.contiguous(), uniforms.contiguous(), 0]
+        return self
+
+    def _temperatures(self, B, device):
+        """the kernel's temperature argument -- a float, or an f32 tensor [B] on the device -- or None; a tensor's host check is made
+        once per state of the tensor"""
+        t = self.target_temperatures
+        if isinstance(t, (int, float)) and not isinstance(t, bool):
+            return float(t) if t > 0 else None
+        if not torch.is_tensor(t) or t.numel() != B or t.dim() > 1 or not t.dtype.is_floating_point:
+            return None
+        key = (t.data_ptr(), t._version, t.device, t.dtype, device)
+        hit = self.__dict__.get("_temp_cache")
+        if hit is None or hit[0] != key:
+            ok = bool((t > 0).all()) and bool(torch.isfinite(t).all())
+            dev_t = t.detach().reshape(B).to(device=device, dtype=torch.float32).contiguous() if ok else None
+            hit = self.__dict__["_temp_cache"] = (key, dev_t)
+        return hit[1]
+
+    def _fused_setup(self, state):
+        """(plan, B, temperature argument) if the kernel takes this state, else None"""
+        if not self.fused or type(self.proposal) is not GaussianProposal:
+            return None
+        std = self.proposal._noise_std
+        if not (isinstance(std, (int, float)) and not isinstance(std, bool) and std >= 0):
+            return None
+        if not isinstance(state, SamplerState) or state.set_samples_hook is not default_set_samples_hook:
+            return None
+        data = state.__dict__["_data"]
+        samples = data.samples
+        if getattr(data, "box_vectors", None) is not None or len(samples) != 1 or not torch.is_tensor(samples[0]):
+            return None
+        plan = _kernel_plan(self.target_energy, 1.0)
+        if not isinstance(plan, PairPlan):
+            return None
+        x, nd = samples[0], plan.n_particles * plan.n_dims
+        if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() in (2, 3) and x.shape[0] > 0):
+            return None
+        if tuple(x.shape[1:]) not in ((nd,), (plan.n_particles, plan.n_dims)):
+            return None
+        temps = self._temperatures(x.shape[0], x.device)
+        if temps is None:
+            return None
+        return plan, x.shape[0], temps
+
+    def _carried_energies(self, state, B):
+        """the state's energies as the kernel's f32 [B], if they are up to date (a copy: the launch overwrites them)"""
+        data = state.__dict__["_data"]
+        e = data.energies
+        if not data.energies_up_to_date or not torch.is_tensor(e) or e.numel() != B or e.device != data.samples[0].device:
+            return None
+        return e.detach().reshape(B).to(torch.float32).clone()
+
+    def _run_chains(self, setup, x2, e, e_valid, launches, traj=None, traj_e=None, tick=None):
+        """the launches of ``_launch_plan`` on the chains x2 [B, n d] / e [B] in place; frames go to traj / traj_e in order;
+        ``tick(steps enqueued so far)`` is called after every launch"""
+        plan, B, temps = setup
+        total = sum(steps for steps, _, _ in launches)
+        if total == 0:
+            return
+        if self.n_accepted is None or self.n_accepted.shape != (B,) or self.n_accepted.device != x2.device or self.n_accepted.dtype != torch.int32:
+            self.n_accepted, self.n_proposed, fresh = torch.empty(B, dtype=torch.int32, device=x2.device), 0, True
+        else:
+            fresh = False
+        fed = self._fed
+        if fed is not None:
+            if fed[0].shape[0] - fed[2] < total or fed[0].shape[1:] != x2.shape or fed[0].device != x2.device:
+                raise ValueError(f"MCMCStep: {total} steps of {tuple(x2.shape)} chains need as many rows of fed noise; "
+                                 f"{fed[0].shape[0] - fed[2]} rows of {tuple(fed[0].shape[1:])} are left")
+            seed = offset = 0
+        else:
+            from . import dp
+            st = self._philox_ids()
+            seed = (dp.rank_seed(torch.initial_seed()) + 0x9E3779B97F4A7C15 * (st[0] + 1)) & (2 ** 64 - 1)
+            offset, st[1] = st[1], st[1] + total
+        frame = 0
+        done = 0
+        for steps, every, frames in launches:
+            noise = uniforms = None
+            if fed is not None:
+                noise, uniforms = fed[0][fed[2]:fed[2] + steps], fed[1][fed[2]:fed[2] + steps]
+                fed[2] += steps
+            pair_mcmc(plan, x2, e, e_valid, temps, self.proposal._noise_std, steps, noise, uniforms, seed, offset, self.chain_offset,
+                      None if not frames else traj[frame:frame + frames].view(frames, B, -1),
+                      None if not frames or traj_e is None else traj_e[frame:frame + frames], every, self.n_accepted, not fresh)
+            e_valid, fresh = True, False
+            offset += steps
+            frame += frames
+            done += steps
+            if tick is not None:
+                tick(done)
+        self.n_proposed += total
+
+    def _fused_forward(self, state, setup, n_steps):
+        plan, B, _ = setup
+        x = state.__dict__["_data"].samples[0]
+        y = x.detach().clone()
+        e = self._carried_energies(state, B)
+        e_valid = e is not None
+        if e is None:
+            e = torch.empty(B, dtype=torch.float32, device=x.device)
+        self._run_chains(setup, y.view(B, -1), e, e_valid, [(k, 0, 0) for k in _split(n_steps, MCMC_MAX_STEPS_PER_LAUNCH)])
+        return _advanced_state(state, y, e)
+
+    def forward(self, state):
+        setup = self._fused_setup(state)
+        if setup is None:
+            return super().forward(state)
+        return self._fused_forward(state, setup, self._n_steps)
+
+
+def _split(total, cap):
+    cap = max(1, int(cap))
+    return [min(cap, total - s) for s in range(0, total, cap)]
+
+
+def _advanced_state(state, samples, energies):
+    """``state.replace(samples=(samples,), energies=energies)`` for a state the fused path takes (default samples hook, no box vectors),
+    without the deep copy of every field that ``as_dict`` makes"""
+    data = dataclasses.replace(state.__dict__["_data"], samples=(samples,), energies=energies, energies_up_to_date=True, forces_up_to_date=False)
+    new = SamplerState.__new__(SamplerState)
+    new._dataclass, new.set_samples_hook, new._data = state._dataclass, state.set_samples_hook, data
+    return new
+
+
+# ---- the driver -----------------------------------------------------------------------------------------------------------------
+class IterativeSampler(Sampler, torch.utils.data.Dataset):
+    """Drives ``sampler_steps`` over a ``SamplerState`` (iterative.py:121-192): an iteration applies every step ``stride`` times;
+    ``sample(n)`` returns the samples after each of n iterations, [n, B, ...]; ``n_burnin`` iterations run at construction;
+    ``max_iterations`` bounds the iterations (``StopIteration`` beyond).  Also an iterable-style torch dataset.  ``return_hook``
+    (keyword, as of the reference's ``Sampler``) post-processes the list of sampled tensors.
+
+    With one fusable ``MCMCStep`` and the default ``extract_sample_hook`` an iteration is one launch of ``stride * n_steps`` steps and
+    ``sample(n)`` has the kernel write the n states into the result (launches of at most ``MCMC_MAX_STEPS_PER_LAUNCH`` steps); the
+    state's samples are then the last recorded frame."""
+
+    def __init__(
+            self,
+            sampler_state,
+            sampler_steps,
+            stride=1,
+            n_burnin=0,
+            max_iterations=None,
+            extract_sample_hook=default_extract_sample_hook,
+            progress_bar=lambda x: x,
+            **kwargs
+    ):
+        return_hook = kwargs.pop("return_hook", lambda x: x)
+        super().__init__(**kwargs)
+        self.return_hook = return_hook
+        if isinstance(sampler_state, torch.Tensor):
+            sampler_state = SamplerState(samples=sampler_state)
+        self.state = sampler_state
+        self.sampler_steps = sampler_steps
+        self.extract_sample_hook = extract_sample_hook
+        self.progress_bar = progress_bar
+        self.stride = stride
+        self.max_iterations = max_iterations
+        self.i = 0
+        self._chains = None            # (state handed out last, x [B, n d], e [B]): the fused path's working buffers
+        fused = self._fused_setup() if n_burnin > 0 else None
+        if fused is not None:
+            self._fused_iterations(n_burnin, False, fused)
+        else:
+            for _ in self.progress_bar(range(n_burnin)):
+                self.state = next(self)
+
+    def _fused_setup(self):
+        """(step, setup) if the iterations run inside the kernel, else None"""
+        steps = self.sampler_steps
+        if self.extract_sample_hook is not default_extract_sample_hook or not isinstance(steps, (list, tuple)) or len(steps) != 1:
+            return None
+        step = steps[0]
+        if not isinstance(step, MCMCStep) or type(step).forward is not MCMCStep.forward or type(step)._step is not MCMCStep._step:
+            return None
+        if not (isinstance(self.stride, int) and self.stride >= 1 and isinstance(step._n_steps, int) and step._n_steps >= 1):
+            return None
+        setup = step._fused_setup(self.state)
+        return None if setup is None else (step, setup)
+
+    def _fused_iterations(self, n, record, fused, show=True):
+        """n iterations inside the kernel (fused = ``_fused_setup()``); returns the [n, B, ...] frames if ``record``, else only
+        advances the state.  ``show``: ``progress_bar`` is handed ``range(n)`` as on the general path and advanced, after every launch,
+        by the iterations that launch completed (the launches are asynchronous: the bar shows what is enqueued)"""
+        step, setup = fused
+        n_ok = n if self.max_iterations is None else max(0, min(n, self.max_iterations - self.i))
+        x = self.state.__dict__["_data"].samples[0]
+        B, dev = x.shape[0], x.device
+        frames = None
+        if n_ok > 0:
+            chains = self._chains
+            if chains is None or chains[0] is not self.state:          # a state from outside: take a working copy of it
+                e = step._carried_energies(self.state, B)
+                chains = [None, x.detach().clone().view(B, -1), e, e is not None]
+                if e is None:
+                    chains[2] = torch.empty(B, dtype=torch.float32, device=dev)
+            else:
+                chains = [None, chains[1], chains[2], True]
+            unit = self.stride * step._n_steps
+            launches = _launch_plan(unit, n_ok, MCMC_MAX_STEPS_PER_LAUNCH) if record else _launch_plan(unit * n_ok, 1, MCMC_MAX_STEPS_PER_LAUNCH)
+            n_frames = n_ok if record else 1
+            frames = torch.empty((n_frames,) + tuple(x.shape), dtype=torch.float32, device=dev)
+            frames_e = torch.empty((n_frames, B), dtype=torch.float32, device=dev)
+            bar, shown = (iter(self.progress_bar(range(n_ok))) if show else None), [0]
+
+            def tick(steps_done):
+                while bar is not None and shown[0] < steps_done // unit:
+                    next(bar, None)
+                    shown[0] += 1
+
+            step._run_chains(setup, chains[1], chains[2], chains[3], launches, frames, frames_e, tick)
+            for _ in (bar or ()):                                       # let the bar finish
+                pass
+            self.state = _advanced_state(self.state, frames[-1], frames_e[-1])
+            self._chains = (self.state, chains[1], chains[2])
+            self.i += n_ok
+        if n_ok < n:
+            raise StopIteration
+        return frames
+
+    def _sample(self, n_samples, *args, **kwargs):
+        fused = self._fused_setup() if n_samples > 0 else None
+        if fused is not None:
+            return [self._fused_iterations(n_samples, True, fused)]
+        samples = None
+        for _ in self.progress_bar(range(n_samples)):
+            self.state = next(self)
+            new_samples = self.extract_sample_hook(self.state)
+            if samples is None:
+                samples = [x[None, ...].clone() for x in new_samples]     # add the batch dimension
+            else:
+                for i, (x, new) in enumerate(zip(samples, new_samples)):
+                    samples[i] = torch.cat((x, new[None, ...]), dim=0)
+        return samples
+
+    def sample(self, n_samples, temperature=1.0, *args, **kwargs):
+        samples = pack_tensor_in_list(super().sample(n_samples, temperature, *args, **kwargs))
+        return unpack_tensor_tuple(self.return_hook(samples))
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self.max_iterations is not None and self.i >= self.max_iterations:
+            raise StopIteration
+        fused = self._fused_setup()
+        if fused is not None:
+            self._fused_iterations(1, False, fused, show=False)
+            return self.state
+        for _ in range(self.stride):
+            for sampler_step in self.sampler_steps:
+                self.state = sampler_step.forward(self.state)
+        self.i += 1
+        return self.state
+
+
+class GaussianMCMCSampler(IterativeSampler):
+    """Shortcut for a Gaussian Metropolis sampler (mcmc.py:125-189): ``box_constraint`` is applied whenever samples are set, the default
+    ``return_hook`` combines the sample and batch dimensions, ``n_stride`` is the deprecated spelling of ``stride``."""
+
+    def __init__(
+            self,
+            energy,
+            init_state,
+            temperature=1.,
+            noise_std=.1,
+            stride=1,
+            n_burnin=0,
+            box_constraint=None,
+            return_hook=None,
+            **kwargs
+    ):
+        set_samples_hook = default_set_samples_hook
+        if box_constraint is not None:
+            set_samples_hook = lambda samples: [box_constraint(x) for x in samples]     # noqa: E731
+        if not isinstance(init_state, SamplerState):
+            init_state = SamplerState(samples=init_state, set_samples_hook=set_samples_hook)
+        if return_hook is None:
+            return_hook = lambda samples: [x.reshape(-1, *shape) for x, shape in zip(samples, energy.event_shapes)]     # noqa: E731
+        if "n_stride" in kwargs:
+            warnings.warn("keyword n_stride is deprecated, use stride instead", DeprecationWarning)
+            stride = kwargs["n_stride"]
+        super().__init__(
+            init_state,
+            sampler_steps=[MCMCStep(energy, proposal=GaussianProposal(noise_std=noise_std), target_temperatures=temperature)],
+            stride=stride,
+            n_burnin=n_burnin,
+            return_hook=return_hook
+        )

@@ -739,6 +739,27 @@ int bgk_kdyn_integrate(const float* x, int64_t B, int32_t n_particles, int32_t n
                        const float* mus_time, const float* neg_log_gammas_time, double t_max, int32_t n_steps, int32_t method,
                        int32_t inverse, float* y, float* dlogp, void* stream);
 
+/* Metropolis chains on the targets of bgk_pair_energy, a whole run of steps in one launch (csrc/bgk_mcmc.hip), replacing the per-step op
+ * chain of MCMCStep._step with a GaussianProposal and metropolis_accept (distribution/sampling/mcmc.py:29-46, 86-122, 192-222): per step
+ *   x' = x + noise_std eps,  accept iff -(e(x') - e(x)) / T >= log r   (= the reference's min(0, .) >= log r; a NaN or +inf proposal
+ *   energy is rejected by the comparison), one lane per chain, the chain's row and its proposal in LDS.
+ * x [B, n_particles * n_dims] (contiguous rows) is updated in place.  e [B]: raw energies at temperature 1, bit for bit what
+ * bgk_pair_energy gives at temperature 1 -- read when e_valid != 0 (else the kernel computes the initial energy), written for the final
+ * state.  T = temperatures[b] if temperatures != NULL, else `temperature`.
+ * Random numbers: noise [n_steps, B, n d] and uniforms [n_steps, B] (both or neither), or, when NULL, Philox4x32-10 in the counter layout
+ * of bgk_philox_fields: (global chain row0 + b, field << 20 | 4-column block, offset + step), field 0 = the n d normals, field 1 block 0
+ * word 0 = the uniform -- the numbers bgk_philox_fields(seed, offset + step, row0, fields [normal n d, uniform 1]) writes, whatever
+ * the grid, the sharding (row0) or the split of a run into launches.
+ * traj [n_steps / traj_every, B, n d] and traj_e [n_steps / traj_every, B] (NULL: not recorded): the state / energy after every
+ * traj_every-th step.  n_accepted [B] (int32, may be NULL): accepted steps per chain, written (accumulate = 0) or added to.
+ * Envelope as bgk_pair_energy; BGK_EUNSUPPORTED beyond. */
+int bgk_pair_mcmc(float* x, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
+                  double p0, double p1, double p2, double p3, double osc_scale,
+                  float* e, int32_t e_valid, double temperature, const float* temperatures,
+                  double noise_std, int32_t n_steps, const float* noise, const float* uniforms,
+                  uint64_t seed, uint32_t offset, int64_t row0,
+                  float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream);
+
 /* Prior sampling in one launch from a counter-based generator (Philox4x32-10; counter = (global row, field, 4-column block, offset),
  * key = seed: independent of launch geometry and of the sharding of a batch, row0 = first global row of this launch), replacing
  * torch.randn / Uniform.sample + the shift / scale ops of NormalDistribution._sample_with_temperature (distribution/normal.py:74-92),
