@@ -15,6 +15,7 @@ from .distributions import * # noqa: F401,F403
 from .particles import *     # noqa: F401,F403
 from .dynamics import *      # noqa: F401,F403
 from .sampling import *      # noqa: F401,F403
+from .stochastic import *    # noqa: F401,F403
 from .cdf import *           # noqa: F401,F403
 from .modulo import *        # noqa: F401,F403
 from .moments import *       # noqa: F401,F403
@@ -22,7 +23,7 @@ from .bg import *            # noqa: F401,F403
 from .factory import *       # noqa: F401,F403
 from .training import *      # noqa: F401,F403
 from .clipped import *       # noqa: F401,F403
-from . import clipped, configs, dp, dynamics, factory, particles, sampling, training, utils      # noqa: F401
+from . import clipped, configs, dp, dynamics, factory, particles, sampling, stochastic, training, utils      # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -23,8 +23,10 @@ _MAP = {
     "nn.flow.modulo": "modulo",
     "nn.flow.torchtransform": "modulo",
     "nn.flow.diffeq": "dynamics",
-    "nn.flow.stochastic": "flow",
+    "nn.flow.stochastic": ("flow", "stochastic"),
     "nn.flow.stochastic.augment": "flow",
+    "nn.flow.stochastic.langevin": "stochastic",
+    "nn.flow.stochastic.mcmc": "stochastic",
     "nn.flow.transformer": "transformer",
     "nn.flow.transformer.base": "transformer",
     "nn.flow.transformer.affine": "transformer",

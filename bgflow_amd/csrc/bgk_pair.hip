@@ -106,46 +106,7 @@ __global__ __launch_bounds__(PR_THREADS) void pair_energy_bwd_kernel(PairArgs a)
             else gr = (!a.drop_nonfinite || __builtin_isfinite(a.u[b] - a.dlogp[b])) ? gs : 0.0f;
             if (a.g_dlogp) a.g_dlogp[b] = -gr;          /* d(sum_i (u_i - dlogp_i)) / d dlogp_i = -1 for the kept samples */
             s_scale[tid] = gr * a.inv_t;
-            const float* xr = s_x + tid * S;
-            float* gw = s_g + tid * S;
-            for (int c = 0; c < a.nd; ++c) gw[c] = 0.0f;
-            if (KIND != 2) {
-                for (int i = 0; i + 1 < n; ++i) {
-                    float xi[D], gi[D];
-#pragma unroll
-                    for (int k = 0; k < D; ++k) { xi[k] = xr[i * D + k]; gi[k] = 0.0f; }
-                    for (int j = i + 1; j < n; ++j) {
-                        float df[D], d2 = 0.0f;
-#pragma unroll
-                        for (int k = 0; k < D; ++k) { df[k] = xi[k] - xr[j * D + k]; d2 += df[k] * df[k]; }
-                        float cf;                       /* d e_ij / d x_i = cf (x_i - x_j) */
-                        if (KIND == 0) {
-                            const float s = rm2 / (d2 + 1e-6f), s3 = s * s * s;
-                            cf = c12 * ((s3 * s3 - s3) * s);
-                        } else {
-                            const float dist = __builtin_sqrtf(d2), t = dist - a.p3;
-                            cf = dist > 0.0f ? (4.0f * a.p0 * (t * t * t) + 2.0f * a.p1 * t) / dist : 0.0f;
-                        }
-#pragma unroll
-                        for (int k = 0; k < D; ++k) { const float v = cf * df[k]; gi[k] += v; gw[j * D + k] -= v; }
-                    }
-#pragma unroll
-                    for (int k = 0; k < D; ++k) gw[i * D + k] += gi[k];
-                }
-            }
-            if (a.osc != 0.0f) {                        /* d / d x_i of osc 0.5 sum |x - xbar|^2 = osc (x_i - xbar) */
-                float mean[D];
-                const float inv_n = 1.0f / (float)n;
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    float s = 0.0f;
-                    for (int i = 0; i < n; ++i) s += xr[i * D + k];
-                    mean[k] = s * inv_n;
-                }
-                for (int i = 0; i < n; ++i)
-#pragma unroll
-                    for (int k = 0; k < D; ++k) gw[i * D + k] += a.osc * (xr[i * D + k] - mean[k]);
-            }
+            bgk_pair_row_gradient<D, KIND>(s_x + tid * S, s_g + tid * S, n, a.p0, a.p1, a.p3, rm2, c12, a.osc);     /* bgk_pair_terms.h */
         }
         __syncthreads();
         for (int i = tid; i < rows * a.nd; i += PR_THREADS) {

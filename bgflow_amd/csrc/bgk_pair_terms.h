@@ -5,7 +5,8 @@
  *   KIND 1  multi-double-well    p0 = a, p1 = b, p2 = c, p3 = offset:  sum [a t^4 + b t^2 + c], t = sqrt(d2) - offset
  *   KIND 2  mean-free normal     no pair term
  *   + osc 0.5 sum_i |x_i - xbar|^2 when osc != 0
- * xr: the sample's row [n D] (LDS or registers' backing memory), read-only. */
+ * xr: the sample's row [n D] (LDS or registers' backing memory), read-only.
+ * bgk_pair_row_gradient: d e / d x of the same row, as bgk_pair.hip's backward and bgk_langevin.hip's force both add it up. */
 #ifndef BGK_PAIR_TERMS_H
 #define BGK_PAIR_TERMS_H
 
@@ -57,6 +58,52 @@ __device__ __forceinline__ double bgk_pair_row_energy(const float* xr, int n, fl
     }
     if (osc != 0.0f) { float mean[D]; e += (double)osc * bgk_pair_centroid_term<D>(xr, n, mean); }
     return e;
+}
+
+/* d e / d x of the row at temperature 1, as bgk_pair.hip's backward and bgk_langevin.hip's force both add it up: gw [n D] is the lane's
+ * OWN row of an LDS tile (zeroed here; g_i in registers over the j loop, g_j read-modify-write, pairs in ascending (i, j) order, then
+ * the oscillator term), all in f32.  c12 = -12 p0 / rm2 (KIND 0).  At d_ij = 0 the double-well pair gradient is 0. */
+template <int D, int KIND>
+__device__ __forceinline__ void bgk_pair_row_gradient(const float* xr, float* gw, int n, float p0, float p1, float p3, float rm2, float c12,
+                                                      float osc) {
+    for (int c = 0; c < n * D; ++c) gw[c] = 0.0f;
+    if (KIND != 2) {
+        for (int i = 0; i + 1 < n; ++i) {
+            float xi[D], gi[D];
+#pragma unroll
+            for (int k = 0; k < D; ++k) { xi[k] = xr[i * D + k]; gi[k] = 0.0f; }
+            for (int j = i + 1; j < n; ++j) {
+                float df[D], d2 = 0.0f;
+#pragma unroll
+                for (int k = 0; k < D; ++k) { df[k] = xi[k] - xr[j * D + k]; d2 += df[k] * df[k]; }
+                float cf;                       /* d e_ij / d x_i = cf (x_i - x_j) */
+                if (KIND == 0) {
+                    const float s = rm2 / (d2 + 1e-6f), s3 = s * s * s;
+                    cf = c12 * ((s3 * s3 - s3) * s);
+                } else {
+                    const float dist = __builtin_sqrtf(d2), t = dist - p3;
+                    cf = dist > 0.0f ? (4.0f * p0 * (t * t * t) + 2.0f * p1 * t) / dist : 0.0f;
+                }
+#pragma unroll
+                for (int k = 0; k < D; ++k) { const float v = cf * df[k]; gi[k] += v; gw[j * D + k] -= v; }
+            }
+#pragma unroll
+            for (int k = 0; k < D; ++k) gw[i * D + k] += gi[k];
+        }
+    }
+    if (osc != 0.0f) {                          /* d / d x_i of osc 0.5 sum |x - xbar|^2 = osc (x_i - xbar) */
+        float mean[D];
+        const float inv_n = 1.0f / (float)n;
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            float s = 0.0f;
+            for (int i = 0; i < n; ++i) s += xr[i * D + k];
+            mean[k] = s * inv_n;
+        }
+        for (int i = 0; i < n; ++i)
+#pragma unroll
+            for (int k = 0; k < D; ++k) gw[i * D + k] += osc * (xr[i * D + k] - mean[k]);
+    }
 }
 
 #endif

@@ -760,6 +760,26 @@ int bgk_pair_mcmc(float* x, int64_t B, int32_t n_particles, int32_t n_dims, int3
                   uint64_t seed, uint32_t offset, int64_t row0,
                   float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream);
 
+/* Brownian and Langevin dynamics with the path-probability ratio on the targets of bgk_pair_energy, a whole run of steps in one launch
+ * (csrc/bgk_langevin.hip), replacing the per-step op chain of BrownianFlow._forward and LangevinFlow._forward (nn/flow/stochastic/
+ * langevin.py:32-45, 86-118) with f = -d e / d x at temperature 1, h = stepsize.  v == NULL, Brownian:
+ *   y = x + h f(x) + sqrt(2 h) w,  w_ = (x - y - h f(y)) / sqrt(2 h),  dW += 0.5 sum (w^2 - w_^2)
+ * v != NULL, Langevin (gm = gamma mass, fac1 = sqrt(4 gm kT / h), fac2 = sqrt(gm h / kT)):
+ *   vh = v1 + h / (2 mass) (f(q1) - gm v1 + fac1 w1),  q2 = q1 + h vh,  v2 = (vh + h / (2 mass) (f(q2) + fac1 w2)) / (1 + gamma h / 2),
+ *   w1_ = w2 - fac2 v2,  w2_ = w1 - fac2 v1,  dW += 0.5 sum (w1^2 + w2^2 - w1_^2 - w2_^2)
+ * one lane per sample, the sample's rows in LDS, one force evaluation per step plus one at the start; the elementwise terms in f32 in
+ * the reference's order of operations, the row sums and the running dW in f64.  q and v [B, n_particles * n_dims] (contiguous rows) are
+ * updated in place.  dW [B]: written (accumulate = 0) or added to in f32 (a run split into launches).
+ * Random numbers: w1 (Brownian: w) and, for Langevin, w2 [n_steps, B, n d], or, when NULL, Philox4x32-10 in the counter layout of
+ * bgk_philox_fields: (global row row0 + b, field << 20 | 4-column block, offset + step), field 0 = w / w1, field 1 = w2 -- the numbers
+ * bgk_philox_fields(seed, offset + step, row0, fields [normal n d, normal n d]) writes, whatever the grid, the sharding (row0) or the
+ * split of a run into launches.  Envelope as bgk_pair_energy; BGK_EUNSUPPORTED beyond. */
+int bgk_pair_langevin(float* q, float* v, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
+                      double p0, double p1, double p2, double p3, double osc_scale,
+                      double stepsize, double mass, double gamma, double kT, int32_t n_steps,
+                      const float* w1, const float* w2, uint64_t seed, uint32_t offset, int64_t row0,
+                      float* dW, int32_t accumulate, void* stream);
+
 /* Prior sampling in one launch from a counter-based generator (Philox4x32-10; counter = (global row, field, 4-column block, offset),
  * key = seed: independent of launch geometry and of the sharding of a batch, row0 = first global row of this launch), replacing
  * torch.randn / Uniform.sample + the shift / scale ops of NormalDistribution._sample_with_temperature (distribution/normal.py:74-92),
