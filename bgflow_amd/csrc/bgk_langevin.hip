@@ -37,6 +37,28 @@
  * same bits whatever the tiling, the grid, row0 sharding or the split of a run into launches, and the bits bgk_philox_fields writes for
  * (seed, offset + step) with fields [normal n d, normal n d].
  *
+ * Backward (training through the layers; stochastic.py's _BrownianFn / _LangevinFn).  The forward with the template flag RECORD also
+ * stores the tile after every step, coalesced (traj_q / traj_v [n_steps, B, n d]); q, v, dW are the non-recording launch's bits.
+ * pair_langevin_bwd_kernel sweeps a recorded segment in reverse for the loss L with d L / d dW[b] = gamma, same lane mapping and tiles
+ * of stride S, a fixed order, no atomics; H = d^2 e / d x^2 through bgk_pair_row_hvp of bgk_pair_terms.h.  Three running vectors per
+ * sample live in LDS over the sweep and in gq, gv, carry [B, n d] between launches (last segment first):
+ *   Brownian   w_k_ = (x_k - x_(k+1) + h g_(k+1)) / r, r = sqrt(2 h);  a_k = -gamma w_k_ / r, a_(-1) = a_K = 0;
+ *              L_k = L_(k+1) + a_k - a_(k-1) - h H(x_k) (L_(k+1) - a_(k-1)),  L_K = g_y - a_(K-1) + h H(x_K) a_(K-1)
+ *              kept as gq = L_(k+1) + a_k, carry = L_(k+1) (start: g_y, 0).  State k: g_k (one gradient) for a_(k-1), u = carry - a_(k-1),
+ *              H(x_k) u (one product), L_k = (gq - a_(k-1)) - h H u, carry = L_k, gq = L_k + a_(k-1).  No noise is needed.
+ *   Langevin   per step in reverse, b1 = w2 - fac2 v_(k+1), b2 = w1 - fac2 v_k:  Lv += gamma fac2 b1,  p = c2 Lv,  Lq -= c1 H(q_(k+1)) p,
+ *              Lvh = p + h Lq,  Lv_k = (1 - c1 gm) Lvh + gamma fac2 b2,  Lq_k = Lq - c1 H(q_k) Lvh.  The two products at one state are
+ *              one, with the vector c1 (Lvh_k + p_(k-1)); gq = Lq, gv = Lv, carry = Lvh (start: g_q, g_v, 0).  State j: Lv += ..b1 and p of
+ *              step j - 1, carry = c1 (carry + p), Lq -= H(q_j) carry, then Lvh, Lv of step j - 1.  The noise: w1 / w2, or Philox as the
+ *              forward drew it.
+ * A launch handles the states n_steps .. 1 of its segment (0: the state before it, j > 0: frame j - 1) and, for the run's first
+ * segment, state 0; every state by one launch, with the same operations whatever the split: the gradients do not depend on it.
+ * Tiles (5 for either): X the state q_j (Langevin: then v_(j-1));  Y x_(j-1) / v_j, then H u;  GQ;  GV (Brownian: g_j, then a_(j-1));
+ * GC the carry = the product's vector.  States are staged coalesced per state (barriers around them, uniform over the wave).
+ * Rows per tile = the most (<= 64) with 5 rows S 4 B within the dynamic LDS:
+ *                 n d = 192 (S = 193)       LJ13, n d = 39 (S = 39)     DW4, n d = 8 (S = 9)
+ *   backward      16 rows, 61,760 B         64 rows, 49,920 B           64 rows, 11,520 B
+ *
  * Envelope 2 <= n <= 64, 1 <= d <= 3. */
 #include "bgk_common.h"
 #include "bgk_pair_terms.h"
@@ -57,6 +79,7 @@ struct LgArgs {
     const float* w1; const float* w2;
     uint32_t seed_lo, seed_hi, offset;
     float* dW; int accumulate;
+    float* traj_q; float* traj_v;                      /* RECORD: the state after every step [n_steps, B, n d] */
 };
 
 /* the four normals of columns 4 cb .. 4 cb + 3 of a field: the explicit row (columns beyond n d: 0) or the Philox block */
@@ -72,7 +95,7 @@ __device__ __forceinline__ void lg_normal4(const float* row, int nd, int cb, uin
     }
 }
 
-template <int D, int KIND, bool LANGEVIN>
+template <int D, int KIND, bool LANGEVIN, bool RECORD>
 __global__ __launch_bounds__(LG_THREADS) void pair_langevin_kernel(LgArgs a) {
     extern __shared__ float s_mem[];
     const int tid = threadIdx.x, n = a.n, nd = a.nd, S = a.nd | 1;
@@ -162,6 +185,17 @@ __global__ __launch_bounds__(LG_THREADS) void pair_langevin_kernel(LgArgs a) {
                 }
                 dw += 0.5 * sum;
             }
+            if (RECORD) {                                              /* the state after the step, as coalesced tile stores */
+                __syncthreads();
+                const int64_t f0 = ((int64_t)step * a.B + b0) * nd;
+                const int oq = LANGEVIN ? 0 : oy;
+                for (int i = tid; i < rows * nd; i += LG_THREADS) {
+                    const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * nd;
+                    a.traj_q[f0 + i] = s_mem[oq + r * S + c];
+                    if (LANGEVIN) a.traj_v[f0 + i] = s_mem[T + r * S + c];
+                }
+                __syncthreads();
+            }
             if (!LANGEVIN) { const int sx = ox; ox = oy; oy = sx; }
             const int sf = of; of = og; og = sf;
         }
@@ -176,46 +210,201 @@ __global__ __launch_bounds__(LG_THREADS) void pair_langevin_kernel(LgArgs a) {
     }
 }
 
-template <int KIND, bool LANGEVIN>
+template <int KIND, bool LANGEVIN, bool RECORD>
 void launch_langevin_d(int d, int grid, size_t lds, hipStream_t s, const LgArgs& a) {
-    if (d == 1) hipLaunchKernelGGL((pair_langevin_kernel<1, KIND, LANGEVIN>), dim3(grid), dim3(LG_THREADS), lds, s, a);
-    else if (d == 2) hipLaunchKernelGGL((pair_langevin_kernel<2, KIND, LANGEVIN>), dim3(grid), dim3(LG_THREADS), lds, s, a);
-    else hipLaunchKernelGGL((pair_langevin_kernel<3, KIND, LANGEVIN>), dim3(grid), dim3(LG_THREADS), lds, s, a);
+    if (d == 1) hipLaunchKernelGGL((pair_langevin_kernel<1, KIND, LANGEVIN, RECORD>), dim3(grid), dim3(LG_THREADS), lds, s, a);
+    else if (d == 2) hipLaunchKernelGGL((pair_langevin_kernel<2, KIND, LANGEVIN, RECORD>), dim3(grid), dim3(LG_THREADS), lds, s, a);
+    else hipLaunchKernelGGL((pair_langevin_kernel<3, KIND, LANGEVIN, RECORD>), dim3(grid), dim3(LG_THREADS), lds, s, a);
 }
 
 template <int KIND>
-void launch_langevin(bool langevin, int d, int grid, size_t lds, hipStream_t s, const LgArgs& a) {
-    if (langevin) launch_langevin_d<KIND, true>(d, grid, lds, s, a);
-    else launch_langevin_d<KIND, false>(d, grid, lds, s, a);
+void launch_langevin(bool langevin, bool record, int d, int grid, size_t lds, hipStream_t s, const LgArgs& a) {
+    if (langevin) { if (record) launch_langevin_d<KIND, true, true>(d, grid, lds, s, a); else launch_langevin_d<KIND, true, false>(d, grid, lds, s, a); }
+    else { if (record) launch_langevin_d<KIND, false, true>(d, grid, lds, s, a); else launch_langevin_d<KIND, false, false>(d, grid, lds, s, a); }
 }
 
-}  // namespace
+/* ---- the adjoint sweep over a recorded segment (header: "Backward") ---- */
+struct LbArgs {
+    const float* q0; const float* v0; const float* traj_q; const float* traj_v; int64_t B, row0;
+    int n, nd, rows; uint32_t magic;
+    float p0, p1, p2, p3, osc;
+    float h, sq2h, c1, c2, omg, fac2; int n_steps;
+    const float* w1; const float* w2;
+    uint32_t seed_lo, seed_hi, offset;
+    const float* g_dW; float* gq; float* gv; float* carry; int first;
+};
 
-extern "C" int bgk_pair_langevin(float* q, float* v, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
-                                 double p0, double p1, double p2, double p3, double osc_scale,
-                                 double stepsize, double mass, double gamma, double kT, int32_t n_steps,
-                                 const float* w1, const float* w2, uint64_t seed, uint32_t offset, int64_t row0,
-                                 float* dW, int32_t accumulate, void* stream) {
-    BGK_CHECK_ARG(B >= 0 && row0 >= 0 && n_steps >= 0, "bgk_pair_langevin: bad batch size / row0 / n_steps");
-    BGK_CHECK_ARG(kind >= 0 && kind <= 2, "bgk_pair_langevin: kind %d (0 Lennard-Jones, 1 multi-double-well, 2 mean-free normal)", kind);
+/* rows [b0, b0 + rows) of a contiguous [B, n d] tensor into / out of a tile (row stride S), every lane of the wave */
+__device__ __forceinline__ void lb_stage(const LbArgs& a, const float* src, int64_t b0, int rows, int S, float* tile) {
+    for (int i = threadIdx.x; i < rows * a.nd; i += LG_THREADS) {
+        const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * a.nd;
+        tile[r * S + c] = src[b0 * a.nd + i];
+    }
+}
+
+__device__ __forceinline__ void lb_store(const LbArgs& a, float* dst, int64_t b0, int rows, int S, const float* tile) {
+    for (int i = threadIdx.x; i < rows * a.nd; i += LG_THREADS) {
+        const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * a.nd;
+        dst[b0 * a.nd + i] = tile[r * S + c];
+    }
+}
+
+template <int D, int KIND, bool LANGEVIN>
+__global__ __launch_bounds__(LG_THREADS) void pair_langevin_bwd_kernel(LbArgs a) {
+    extern __shared__ float s_mem[];
+    const int tid = threadIdx.x, n = a.n, nd = a.nd, S = a.nd | 1;
+    const int T = a.rows * S;
+    const float rm2 = a.p1 * a.p1, c12 = -12.0f * a.p0 / rm2;
+    const int64_t n_tiles = (a.B + a.rows - 1) / a.rows;
+    const int64_t frame = a.B * (int64_t)nd;
+    float* s_x = s_mem;                 /* the state q_j; Langevin: then v_(j-1) */
+    float* s_y = s_mem + T;             /* Brownian x_(j-1), Langevin v_j; then H u */
+    float* s_gq = s_mem + 2 * T;
+    float* s_gv = s_mem + 3 * T;        /* Langevin: the velocity adjoint; Brownian: g_j, then a_(j-1) */
+    float* s_gc = s_mem + 4 * T;        /* the carry; the vector of the Hessian product */
+    for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const int64_t b0 = t * a.rows;
+        const int rows = (int)((a.B - b0) < a.rows ? (a.B - b0) : a.rows);
+        lb_stage(a, a.gq, b0, rows, S, s_gq);
+        lb_stage(a, a.carry, b0, rows, S, s_gc);
+        if (LANGEVIN) lb_stage(a, a.gv, b0, rows, S, s_gv);
+        const bool active = tid < rows;
+        const int64_t b = b0 + (active ? tid : 0);
+        const uint64_t grow = (uint64_t)(a.row0 + b);
+        const uint32_t r_lo = (uint32_t)grow, r_hi = (uint32_t)(grow >> 32);
+        const float gamma = a.g_dW[b], gf2 = gamma * a.fac2;
+        float* xr = s_x + tid * S;
+        float* yr = s_y + tid * S;
+        float* gq = s_gq + tid * S;
+        float* gv = s_gv + tid * S;
+        float* gc = s_gc + tid * S;
+        for (int j = a.n_steps; j >= (a.first ? 0 : 1); --j) {       /* state j of the segment: 0 the state before it, j > 0 frame j - 1 */
+            __syncthreads();
+            lb_stage(a, j > 0 ? a.traj_q + (int64_t)(j - 1) * frame : a.q0, b0, rows, S, s_x);
+            if (j > 0) {
+                if (LANGEVIN) lb_stage(a, a.traj_v + (int64_t)(j - 1) * frame, b0, rows, S, s_y);
+                else lb_stage(a, j > 1 ? a.traj_q + (int64_t)(j - 2) * frame : a.q0, b0, rows, S, s_y);
+            }
+            __syncthreads();
+            const uint32_t off = a.offset + (uint32_t)(j - 1);         /* the step that led to state j */
+            const float* n1 = (a.w1 && j > 0) ? a.w1 + ((int64_t)(j - 1) * a.B + b) * nd : nullptr;
+            const float* n2 = (a.w2 && j > 0) ? a.w2 + ((int64_t)(j - 1) * a.B + b) * nd : nullptr;
+            if (active) {
+                if (!LANGEVIN) {
+                    if (j > 0) {
+                        bgk_pair_row_gradient<D, KIND>(xr, gv, n, a.p0, a.p1, a.p3, rm2, c12, a.osc);
+                        for (int c = 0; c < nd; ++c) {
+                            const float wb = ((yr[c] - xr[c]) - a.h * (-gv[c])) / a.sq2h;     /* the forward's w_ of step j - 1 */
+                            const float am = -(gamma * wb) / a.sq2h;                          /* a_(j-1) */
+                            gv[c] = am; gc[c] = gc[c] - am;
+                        }
+                    }
+                    bgk_pair_row_hvp<D, KIND, false>(xr, gc, nullptr, yr, n, a.p0, a.p1, a.p3, rm2, c12, a.osc);
+                    for (int c = 0; c < nd; ++c) {
+                        const float am = j > 0 ? gv[c] : 0.0f;
+                        const float lam = (gq[c] - am) - a.h * yr[c];
+                        gc[c] = lam; gq[c] = lam + am;
+                    }
+                } else {
+                    if (j > 0) {
+                        for (int cb = 0; 4 * cb < nd; ++cb) {
+                            float w[4];
+                            lg_normal4(n2, nd, cb, r_lo, r_hi, 1u, off, a.seed_lo, a.seed_hi, w);
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                const int c = 4 * cb + k;
+                                if (c < nd) {
+                                    const float lv = gv[c] + gf2 * (w[k] - a.fac2 * yr[c]);
+                                    gv[c] = lv; gc[c] = a.c1 * (gc[c] + a.c2 * lv);
+                                }
+                            }
+                        }
+                    } else {
+                        for (int c = 0; c < nd; ++c) gc[c] = a.c1 * gc[c];
+                    }
+                    bgk_pair_row_hvp<D, KIND, false>(xr, gc, nullptr, yr, n, a.p0, a.p1, a.p3, rm2, c12, a.osc);
+                    for (int c = 0; c < nd; ++c) gq[c] -= yr[c];
+                }
+            }
+            if (LANGEVIN && j > 0) {
+                __syncthreads();
+                lb_stage(a, j > 1 ? a.traj_v + (int64_t)(j - 2) * frame : a.v0, b0, rows, S, s_x);
+                __syncthreads();
+                if (active) {
+                    for (int cb = 0; 4 * cb < nd; ++cb) {
+                        float w[4];
+                        lg_normal4(n1, nd, cb, r_lo, r_hi, 0u, off, a.seed_lo, a.seed_hi, w);
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const int c = 4 * cb + k;
+                            if (c < nd) {
+                                const float vh = a.c2 * gv[c] + a.h * gq[c];
+                                gc[c] = vh; gv[c] = a.omg * vh + gf2 * (w[k] - a.fac2 * xr[c]);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        lb_store(a, a.gq, b0, rows, S, s_gq);
+        lb_store(a, a.carry, b0, rows, S, s_gc);
+        if (LANGEVIN) lb_store(a, a.gv, b0, rows, S, s_gv);
+        __syncthreads();
+    }
+}
+
+template <int KIND, bool LANGEVIN>
+void launch_langevin_bwd_d(int d, int grid, size_t lds, hipStream_t s, const LbArgs& a) {
+    if (d == 1) hipLaunchKernelGGL((pair_langevin_bwd_kernel<1, KIND, LANGEVIN>), dim3(grid), dim3(LG_THREADS), lds, s, a);
+    else if (d == 2) hipLaunchKernelGGL((pair_langevin_bwd_kernel<2, KIND, LANGEVIN>), dim3(grid), dim3(LG_THREADS), lds, s, a);
+    else hipLaunchKernelGGL((pair_langevin_bwd_kernel<3, KIND, LANGEVIN>), dim3(grid), dim3(LG_THREADS), lds, s, a);
+}
+
+template <int KIND>
+void launch_langevin_bwd(bool langevin, int d, int grid, size_t lds, hipStream_t s, const LbArgs& a) {
+    if (langevin) launch_langevin_bwd_d<KIND, true>(d, grid, lds, s, a);
+    else launch_langevin_bwd_d<KIND, false>(d, grid, lds, s, a);
+}
+
+/* the checks every entry shares */
+int langevin_check(const char* what, int64_t B, int64_t row0, int32_t n_steps, int32_t n_particles, int32_t n_dims, int32_t kind,
+                   double stepsize, double mass, double gamma, double kT, const float* w1, const float* w2, bool langevin) {
+    BGK_CHECK_ARG(B >= 0 && row0 >= 0 && n_steps >= 0, "%s: bad batch size / row0 / n_steps", what);
+    BGK_CHECK_ARG(kind >= 0 && kind <= 2, "%s: kind %d (0 Lennard-Jones, 1 multi-double-well, 2 mean-free normal)", what, kind);
     if (!(n_particles >= 2 && n_particles <= LG_MAX_N && n_dims >= 1 && n_dims <= LG_MAX_D)) {
-        bgk_set_error("bgk_pair_langevin: %d particles in %d dimensions are outside the kernel's envelope (2..%d particles, 1..%d dimensions)",
+        bgk_set_error("%s: %d particles in %d dimensions are outside the kernel's envelope (2..%d particles, 1..%d dimensions)", what,
                       n_particles, n_dims, LG_MAX_N, LG_MAX_D);
         return BGK_EUNSUPPORTED;
     }
-    BGK_CHECK_ARG(stepsize > 0.0 && stepsize < INFINITY, "bgk_pair_langevin: the step size must be positive and finite");
-    BGK_CHECK_ARG(mass > 0.0 && gamma >= 0.0 && kT > 0.0, "bgk_pair_langevin: mass and kT must be positive, gamma not negative");
-    BGK_CHECK_ARG(!w2 || (w1 && v), "bgk_pair_langevin: w2 goes with w1 and with velocities");
-    BGK_CHECK_ARG(!(v && w1) || w2, "bgk_pair_langevin: with velocities w1 and w2 go together");
-    if (B == 0) return 0;
-    BGK_CHECK_ARG(q && dW, "bgk_pair_langevin: null tensor");
+    BGK_CHECK_ARG(stepsize > 0.0 && stepsize < INFINITY, "%s: the step size must be positive and finite", what);
+    BGK_CHECK_ARG(mass > 0.0 && gamma >= 0.0 && kT > 0.0, "%s: mass and kT must be positive, gamma not negative", what);
+    BGK_CHECK_ARG(!w2 || (w1 && langevin), "%s: w2 goes with w1 and with velocities", what);
+    BGK_CHECK_ARG(!(langevin && w1) || w2, "%s: with velocities w1 and w2 go together", what);
+    return 0;
+}
+
+int langevin_rows(int nd, int tiles) {
+    int rows = LG_THREADS;
+    while (tiles * rows * (nd | 1) * (int)sizeof(float) > LG_LDS_DYNAMIC) --rows;
+    return rows;
+}
+
+int langevin_forward(const char* what, float* q, float* v, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
+                     double p0, double p1, double p2, double p3, double osc_scale,
+                     double stepsize, double mass, double gamma, double kT, int32_t n_steps,
+                     const float* w1, const float* w2, uint64_t seed, uint32_t offset, int64_t row0,
+                     float* dW, int32_t accumulate, float* traj_q, float* traj_v, void* stream) {
     const bool langevin = v != nullptr;
+    const int st = langevin_check(what, B, row0, n_steps, n_particles, n_dims, kind, stepsize, mass, gamma, kT, w1, w2, langevin);
+    if (st) return st;
+    if (B == 0) return 0;
+    BGK_CHECK_ARG(q && dW, "%s: null tensor", what);
     LgArgs a{};
     a.q = q; a.v = v; a.B = B; a.row0 = row0; a.n = n_particles; a.nd = n_particles * n_dims;
     a.magic = (uint32_t)(((1ull << 32) + (uint64_t)a.nd - 1) / (uint64_t)a.nd);
     const int S = a.nd | 1, tiles = langevin ? 5 : 4;
-    int rows = LG_THREADS;
-    while (tiles * rows * S * (int)sizeof(float) > LG_LDS_DYNAMIC) --rows;
+    const int rows = langevin_rows(a.nd, tiles);
     a.rows = rows;
     a.p0 = (float)p0; a.p1 = (float)p1; a.p2 = (float)p2; a.p3 = (float)p3; a.osc = (float)osc_scale;
     const double gm = gamma * mass;
@@ -225,12 +414,73 @@ extern "C" int bgk_pair_langevin(float* q, float* v, int64_t B, int32_t n_partic
     a.n_steps = n_steps; a.w1 = w1; a.w2 = w2;
     a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.offset = offset;
     a.dW = dW; a.accumulate = accumulate != 0;
+    a.traj_q = traj_q; a.traj_v = traj_v;
     const size_t lds = (size_t)tiles * rows * S * sizeof(float);
     const int64_t n_tiles = (B + rows - 1) / rows;
     const int grid = (int)(n_tiles < LG_MAX_GRID ? n_tiles : LG_MAX_GRID);
     hipStream_t s = (hipStream_t)stream;
-    if (kind == 0) launch_langevin<0>(langevin, n_dims, grid, lds, s, a);
-    else if (kind == 1) launch_langevin<1>(langevin, n_dims, grid, lds, s, a);
-    else launch_langevin<2>(langevin, n_dims, grid, lds, s, a);
-    return bgk_launch_status("bgk_pair_langevin");
+    const bool record = traj_q != nullptr;
+    if (kind == 0) launch_langevin<0>(langevin, record, n_dims, grid, lds, s, a);
+    else if (kind == 1) launch_langevin<1>(langevin, record, n_dims, grid, lds, s, a);
+    else launch_langevin<2>(langevin, record, n_dims, grid, lds, s, a);
+    return bgk_launch_status(what);
+}
+
+}  // namespace
+
+extern "C" int bgk_pair_langevin(float* q, float* v, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
+                                 double p0, double p1, double p2, double p3, double osc_scale,
+                                 double stepsize, double mass, double gamma, double kT, int32_t n_steps,
+                                 const float* w1, const float* w2, uint64_t seed, uint32_t offset, int64_t row0,
+                                 float* dW, int32_t accumulate, void* stream) {
+    return langevin_forward("bgk_pair_langevin", q, v, B, n_particles, n_dims, kind, p0, p1, p2, p3, osc_scale, stepsize, mass, gamma, kT,
+                            n_steps, w1, w2, seed, offset, row0, dW, accumulate, nullptr, nullptr, stream);
+}
+
+extern "C" int bgk_pair_langevin_record(float* q, float* v, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
+                                        double p0, double p1, double p2, double p3, double osc_scale,
+                                        double stepsize, double mass, double gamma, double kT, int32_t n_steps,
+                                        const float* w1, const float* w2, uint64_t seed, uint32_t offset, int64_t row0,
+                                        float* dW, int32_t accumulate, float* traj_q, float* traj_v, void* stream) {
+    BGK_CHECK_ARG(B == 0 || (traj_q && (traj_v != nullptr) == (v != nullptr)),
+                  "bgk_pair_langevin_record: traj_q [n_steps, B, n d], and traj_v exactly with velocities");
+    return langevin_forward("bgk_pair_langevin_record", q, v, B, n_particles, n_dims, kind, p0, p1, p2, p3, osc_scale, stepsize, mass, gamma,
+                            kT, n_steps, w1, w2, seed, offset, row0, dW, accumulate, traj_q, traj_v, stream);
+}
+
+extern "C" int bgk_pair_langevin_backward(const float* q0, const float* v0, const float* traj_q, const float* traj_v, int64_t B,
+                                          int32_t n_particles, int32_t n_dims, int32_t kind,
+                                          double p0, double p1, double p2, double p3, double osc_scale,
+                                          double stepsize, double mass, double gamma, double kT, int32_t n_steps,
+                                          const float* w1, const float* w2, uint64_t seed, uint32_t offset, int64_t row0,
+                                          const float* g_dW, float* gq, float* gv, float* carry, int32_t first, void* stream) {
+    const char* what = "bgk_pair_langevin_backward";
+    const bool langevin = v0 != nullptr;
+    const int st = langevin_check(what, B, row0, n_steps, n_particles, n_dims, kind, stepsize, mass, gamma, kT, w1, w2, langevin);
+    if (st) return st;
+    if (B == 0) return 0;
+    BGK_CHECK_ARG(q0 && g_dW && gq && carry && (traj_q || n_steps == 0), "%s: null tensor", what);
+    BGK_CHECK_ARG(langevin ? ((traj_v || n_steps == 0) && gv) : (!traj_v && !gv), "%s: traj_v and gv exactly with velocities", what);
+    LbArgs a{};
+    a.q0 = q0; a.v0 = v0; a.traj_q = traj_q; a.traj_v = traj_v; a.B = B; a.row0 = row0; a.n = n_particles; a.nd = n_particles * n_dims;
+    a.magic = (uint32_t)(((1ull << 32) + (uint64_t)a.nd - 1) / (uint64_t)a.nd);
+    const int S = a.nd | 1, tiles = 5;
+    const int rows = langevin_rows(a.nd, tiles);
+    a.rows = rows;
+    a.p0 = (float)p0; a.p1 = (float)p1; a.p2 = (float)p2; a.p3 = (float)p3; a.osc = (float)osc_scale;
+    const double c1 = stepsize / (2.0 * mass), gm = gamma * mass;
+    a.h = (float)stepsize; a.sq2h = (float)sqrt(2.0 * stepsize);
+    a.c1 = (float)c1; a.c2 = (float)(1.0 / (1.0 + gamma * stepsize / 2.0)); a.omg = (float)(1.0 - c1 * gm);
+    a.fac2 = (float)sqrt(gm * stepsize / kT);
+    a.n_steps = n_steps; a.w1 = w1; a.w2 = w2;
+    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.offset = offset;
+    a.g_dW = g_dW; a.gq = gq; a.gv = gv; a.carry = carry; a.first = first != 0;
+    const size_t lds = (size_t)tiles * rows * S * sizeof(float);
+    const int64_t n_tiles = (B + rows - 1) / rows;
+    const int grid = (int)(n_tiles < LG_MAX_GRID ? n_tiles : LG_MAX_GRID);
+    hipStream_t s = (hipStream_t)stream;
+    if (kind == 0) launch_langevin_bwd<0>(langevin, n_dims, grid, lds, s, a);
+    else if (kind == 1) launch_langevin_bwd<1>(langevin, n_dims, grid, lds, s, a);
+    else launch_langevin_bwd<2>(langevin, n_dims, grid, lds, s, a);
+    return bgk_launch_status(what);
 }

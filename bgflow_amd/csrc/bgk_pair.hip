@@ -20,7 +20,9 @@
  * Envelope 2 <= n <= 64, 1 <= d <= 3, i.e. n d <= 192, S <= 193.  One wave per workgroup, dynamic LDS below 64 KiB:
  *   forward   64 rows:  64 x 193 x 4 B = 49,408 B at n d = 192 (three workgroups per CU; LJ13: 64 x 39 x 4 = 9,984 B)
  *   backward  x tile + gradient tile + 64 row scales: 64 rows while 2 x 64 x S x 4 + 256 <= 65,536 B (S <= 127: 65,280 B),
- *             else 32 rows: 2 x 32 x 193 x 4 + 256 = 49,664 B at n d = 192 (lanes 32..63 only stage and store). */
+ *             else 32 rows: 2 x 32 x 193 x 4 + 256 = 49,664 B at n d = 192 (lanes 32..63 only stage and store).
+ *   hvp       tiles x, u, g, Hu: the most rows (<= 64) with 4 rows S 4 B <= 65,536 B: 21 rows, 64,848 B at n d = 192; 64 rows at S <= 64
+ *             (LJ13: 39,936 B).  g and Hu = (d^2 e / d x^2) u of a sample in one pass over its pairs (bgk_pair_row_hvp). */
 #include "bgk_common.h"
 #include "bgk_pair_terms.h"
 
@@ -36,6 +38,7 @@ struct PairArgs {
     float p0, p1, p2, p3, osc, inv_t;
     float* u; const float* dlogp; int drop_nonfinite; float* partial;                     /* forward (+ loss partials [gridDim.x][2]) */
     const float* g_u; const float* g_scalar; float* g_dlogp; float* g_x; int64_t ldg;     /* backward */
+    const float* vec; float* hu;                                                          /* Hessian-vector product (contiguous rows) */
 };
 
 /* stage rows [b0, b0 + rows) of x into s_x (row stride S), every lane of the wave */
@@ -117,6 +120,36 @@ __global__ __launch_bounds__(PR_THREADS) void pair_energy_bwd_kernel(PairArgs a)
     }
 }
 
+/* g = (d e / d x)(x) / T and Hu = (d^2 e / d x^2)(x) u / T of every row: tiles x, u, g, Hu; bgk_pair_row_hvp of bgk_pair_terms.h */
+template <int D, int KIND>
+__global__ __launch_bounds__(PR_THREADS) void pair_energy_hvp_kernel(PairArgs a) {
+    extern __shared__ float s_mem[];
+    const int tid = threadIdx.x, n = a.n, nd = a.nd, S = a.nd | 1, T = a.rows * S;
+    float* s_x = s_mem;
+    const int64_t n_tiles = (a.B + a.rows - 1) / a.rows;
+    const float rm2 = a.p1 * a.p1, c12 = -12.0f * a.p0 / rm2;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t b0 = tile * a.rows;
+        const int rows = (int)((a.B - b0) < a.rows ? (a.B - b0) : a.rows);
+        stage_rows(a, b0, rows, S, s_x);
+        for (int i = tid; i < rows * nd; i += PR_THREADS) {
+            const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * nd;
+            s_mem[T + r * S + c] = a.vec[(b0 + r) * nd + c];
+        }
+        __syncthreads();
+        if (tid < rows)
+            bgk_pair_row_hvp<D, KIND>(s_x + tid * S, s_mem + T + tid * S, s_mem + 2 * T + tid * S, s_mem + 3 * T + tid * S, n, a.p0, a.p1,
+                                      a.p3, rm2, c12, a.osc);
+        __syncthreads();
+        for (int i = tid; i < rows * nd; i += PR_THREADS) {
+            const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * nd;
+            if (a.g_x) a.g_x[(b0 + r) * nd + c] = s_mem[2 * T + r * S + c] * a.inv_t;
+            a.hu[(b0 + r) * nd + c] = s_mem[3 * T + r * S + c] * a.inv_t;
+        }
+        __syncthreads();
+    }
+}
+
 template <int KIND>
 void launch_fwd(int d, int grid, size_t lds, hipStream_t s, const PairArgs& a) {
     if (d == 1) hipLaunchKernelGGL((pair_energy_kernel<1, KIND>), dim3(grid), dim3(PR_THREADS), lds, s, a);
@@ -129,6 +162,13 @@ void launch_bwd(int d, int grid, size_t lds, hipStream_t s, const PairArgs& a) {
     if (d == 1) hipLaunchKernelGGL((pair_energy_bwd_kernel<1, KIND>), dim3(grid), dim3(PR_THREADS), lds, s, a);
     else if (d == 2) hipLaunchKernelGGL((pair_energy_bwd_kernel<2, KIND>), dim3(grid), dim3(PR_THREADS), lds, s, a);
     else hipLaunchKernelGGL((pair_energy_bwd_kernel<3, KIND>), dim3(grid), dim3(PR_THREADS), lds, s, a);
+}
+
+template <int KIND>
+void launch_hvp(int d, int grid, size_t lds, hipStream_t s, const PairArgs& a) {
+    if (d == 1) hipLaunchKernelGGL((pair_energy_hvp_kernel<1, KIND>), dim3(grid), dim3(PR_THREADS), lds, s, a);
+    else if (d == 2) hipLaunchKernelGGL((pair_energy_hvp_kernel<2, KIND>), dim3(grid), dim3(PR_THREADS), lds, s, a);
+    else hipLaunchKernelGGL((pair_energy_hvp_kernel<3, KIND>), dim3(grid), dim3(PR_THREADS), lds, s, a);
 }
 
 /* one call of the pair-energy launchers, filled by field name in the extern "C" entries */
@@ -202,6 +242,26 @@ int pair_backward(const BgkPairCall& c) {
     return bgk_launch_status(c.what);
 }
 
+int pair_hvp(const BgkPairCall& c, const float* vec, float* hu) {
+    PairArgs a{};
+    const int st = pair_common(c, &a);
+    if (st) return st;
+    if (c.B == 0) return 0;
+    BGK_CHECK_ARG(c.x && vec && hu && c.ldx >= a.nd, "%s: null tensor / row stride", c.what);
+    const int S = a.nd | 1;
+    a.rows = PR_THREADS;
+    while (4 * a.rows * S * (int)sizeof(float) > PR_LDS_LIMIT) --a.rows;
+    a.vec = vec; a.hu = hu; a.g_x = c.g_x;
+    const size_t lds = (size_t)4 * a.rows * S * sizeof(float);
+    const int64_t n_tiles = (c.B + a.rows - 1) / a.rows;
+    const int grid = (int)(n_tiles < 256 * 16 ? n_tiles : 256 * 16);
+    hipStream_t s = (hipStream_t)c.stream;
+    if (c.kind == 0) launch_hvp<0>(c.n_dims, grid, lds, s, a);
+    else if (c.kind == 1) launch_hvp<1>(c.n_dims, grid, lds, s, a);
+    else launch_hvp<2>(c.n_dims, grid, lds, s, a);
+    return bgk_launch_status(c.what);
+}
+
 }  // namespace
 
 extern "C" int bgk_pair_energy(const float* x, int64_t ldx, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
@@ -240,4 +300,15 @@ extern "C" int bgk_pair_energy_backward(const float* x, int64_t ldx, int64_t B, 
     c.g_u = g_u; c.g_scalar = g_scalar; c.u_saved = u; c.dlogp = dlogp; c.drop_nonfinite = drop_nonfinite;
     c.g_dlogp = g_dlogp; c.g_x = g_x; c.ldg = ldg; c.stream = stream;
     return pair_backward(c);
+}
+
+extern "C" int bgk_pair_energy_hvp(const float* x, int64_t ldx, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
+                                   double p0, double p1, double p2, double p3, double osc_scale, double temperature,
+                                   const float* u, float* g_out, float* hu_out, void* stream) {
+    BgkPairCall c{};
+    c.what = "bgk_pair_energy_hvp";
+    c.x = x; c.ldx = ldx; c.B = B; c.n_particles = n_particles; c.n_dims = n_dims; c.kind = kind;
+    c.p0 = p0; c.p1 = p1; c.p2 = p2; c.p3 = p3; c.osc_scale = osc_scale; c.temperature = temperature;
+    c.g_x = g_out; c.stream = stream;
+    return pair_hvp(c, u, hu_out);
 }

@@ -6,7 +6,9 @@
  *   KIND 2  mean-free normal     no pair term
  *   + osc 0.5 sum_i |x_i - xbar|^2 when osc != 0
  * xr: the sample's row [n D] (LDS or registers' backing memory), read-only.
- * bgk_pair_row_gradient: d e / d x of the same row, as bgk_pair.hip's backward and bgk_langevin.hip's force both add it up. */
+ * bgk_pair_row_gradient: d e / d x of the same row, as bgk_pair.hip's backward and bgk_langevin.hip's force both add it up.
+ * bgk_pair_row_hvp: that gradient and (d^2 e / d x^2) u in one pass over the pairs, for bgk_pair.hip's hvp kernel and bgk_langevin.hip's
+ * adjoint sweep. */
 #ifndef BGK_PAIR_TERMS_H
 #define BGK_PAIR_TERMS_H
 
@@ -103,6 +105,71 @@ __device__ __forceinline__ void bgk_pair_row_gradient(const float* xr, float* gw
         for (int i = 0; i < n; ++i)
 #pragma unroll
             for (int k = 0; k < D; ++k) gw[i * D + k] += osc * (xr[i * D + k] - mean[k]);
+    }
+}
+
+/* g = d e / d x AND Hu = (d^2 e / d x^2) u of the row at temperature 1 in ONE pass over the pairs, in bgk_pair_row_gradient's order and
+ * with its arithmetic for g (the same bits); ur [n D]: the vector, gw and hw [n D]: the lane's OWN rows of two LDS tiles (zeroed here).
+ * WITH_G = false: only Hu (gw is not touched).  Per pair, df = x_i - x_j, d2 = |df|^2, du = u_i - u_j, s = df . du:
+ *   (Hu)_i += cf du + 2 cf' s df,  (Hu)_j -= the same,  cf as in the gradient, cf' = d cf / d d2:
+ *   KIND 0  q = d2 + 1e-6, sg = rm2 / q:  cf = c12 (sg^7 - sg^4),  cf' = -c12 (7 sg^7 - 4 sg^4) / q
+ *   KIND 1  r = sqrt(d2), t = r - offset, f1 = 4 a t^3 + 2 b t, f2 = 12 a t^2 + 2 b:  cf = f1 / r,  cf' = (f2 / r - f1 / r^2) / (2 r);
+ *           at r = 0 both are 0, the gradient's convention
+ *   oscillator  (Hu)_i += osc (u_i - ubar) */
+template <int D, int KIND, bool WITH_G = true>
+__device__ __forceinline__ void bgk_pair_row_hvp(const float* xr, const float* ur, float* gw, float* hw, int n, float p0, float p1, float p3,
+                                                 float rm2, float c12, float osc) {
+    for (int c = 0; c < n * D; ++c) { if (WITH_G) gw[c] = 0.0f; hw[c] = 0.0f; }
+    if (KIND != 2) {
+        for (int i = 0; i + 1 < n; ++i) {
+            float xi[D], ui[D], gi[D], hi[D];
+#pragma unroll
+            for (int k = 0; k < D; ++k) { xi[k] = xr[i * D + k]; ui[k] = ur[i * D + k]; gi[k] = 0.0f; hi[k] = 0.0f; }
+            for (int j = i + 1; j < n; ++j) {
+                float df[D], du[D], d2 = 0.0f, s = 0.0f;
+#pragma unroll
+                for (int k = 0; k < D; ++k) {
+                    df[k] = xi[k] - xr[j * D + k]; du[k] = ui[k] - ur[j * D + k];
+                    d2 += df[k] * df[k]; s += df[k] * du[k];
+                }
+                float cf, cfp;                  /* d e_ij / d x_i = cf (x_i - x_j); cfp = d cf / d d2 */
+                if (KIND == 0) {
+                    const float q = d2 + 1e-6f, sg = rm2 / q, s3 = sg * sg * sg, s4 = s3 * sg, s7 = (s3 * s3) * sg;
+                    cf = c12 * ((s3 * s3 - s3) * sg);
+                    cfp = -c12 * (7.0f * s7 - 4.0f * s4) / q;
+                } else {
+                    const float dist = __builtin_sqrtf(d2), t = dist - p3;
+                    const float f1 = 4.0f * p0 * (t * t * t) + 2.0f * p1 * t, f2 = 12.0f * p0 * (t * t) + 2.0f * p1;
+                    cf = dist > 0.0f ? f1 / dist : 0.0f;
+                    cfp = dist > 0.0f ? (f2 / dist - f1 / d2) / (2.0f * dist) : 0.0f;
+                }
+                const float c2s = 2.0f * cfp * s;
+#pragma unroll
+                for (int k = 0; k < D; ++k) {
+                    if (WITH_G) { const float v = cf * df[k]; gi[k] += v; gw[j * D + k] -= v; }
+                    const float w = cf * du[k] + c2s * df[k];
+                    hi[k] += w; hw[j * D + k] -= w;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < D; ++k) { if (WITH_G) gw[i * D + k] += gi[k]; hw[i * D + k] += hi[k]; }
+        }
+    }
+    if (osc != 0.0f) {                          /* the Hessian of osc 0.5 sum |x - xbar|^2 is osc (1 - 1 1^T / n) per dimension */
+        float mean[D], umean[D];
+        const float inv_n = 1.0f / (float)n;
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            float s = 0.0f, su = 0.0f;
+            for (int i = 0; i < n; ++i) { s += xr[i * D + k]; su += ur[i * D + k]; }
+            mean[k] = s * inv_n; umean[k] = su * inv_n;
+        }
+        for (int i = 0; i < n; ++i)
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                if (WITH_G) gw[i * D + k] += osc * (xr[i * D + k] - mean[k]);
+                hw[i * D + k] += osc * (ur[i * D + k] - umean[k]);
+            }
     }
 }
 

@@ -111,6 +111,22 @@ def pair_energy(plan, xs):
     return None if x2 is None else _PairEnergyFn.apply(plan, x2)
 
 
+def pair_energy_hvp(plan, x2, u2):
+    """(g, Hu) = (d u / d x, (d^2 u / d x^2) u2) of the PairPlan's energy u = e / T at the rows of x2 [B, n d] on bgk_pair_energy_hvp: one
+    pass over the pairs of a sample for both; x2 and u2 contiguous f32 HIP tensors.  A missing kernel is an error, not a fallback."""
+    from . import _lib
+    nd = plan.n_particles * plan.n_dims
+    for t in (x2, u2):
+        if not (torch.is_tensor(t) and t.is_cuda and t.device == x2.device and t.dtype == torch.float32 and t.is_contiguous()
+                and t.dim() == 2 and t.shape == x2.shape and t.shape[1] == nd):
+            raise ValueError(f"pair_energy_hvp: expected two contiguous float32 HIP tensors [B, {nd}]")
+    g, hu = torch.empty_like(x2), torch.empty_like(x2)
+    with torch.cuda.device(x2.device):
+        st = _lib.lib().bgk_pair_energy_hvp(*_launch_args(plan, x2), _lib.ptr(u2), _lib.ptr(g), _lib.ptr(hu), _lib.stream_ptr(x2.device))
+    _lib.check(st, "bgk_pair_energy_hvp")
+    return g, hu
+
+
 def pair_kl_loss_sums(plan, xs, dlogp, drop_nonfinite=False):
     """(sums, u) of distributions.kl_loss_sums for a PairPlan, or None"""
     x2 = _pair_rows(plan, xs)

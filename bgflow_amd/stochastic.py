@@ -14,7 +14,18 @@ bgk_pair_langevin; ``MetropolisMCFlow``: one bgk_pair_energy launch for E0, then
 its own cap) on copies of the inputs.  It applies when ``energy_model`` is a particle-system target with a ``PairPlan`` at temperature 1
 (2..64 particles in 1..3 dimensions), the inputs are contiguous f32 HIP tensors [B, n d] with B > 0, the settings are plain numbers
 (``stepsize > 0``, ``mass > 0``, ``gamma >= 0``, ``kT > 0``) and no input requires grad while grad is enabled.  The class attribute
-``fused = False`` forces the general path.  A fused backward is not built.
+``fused = False`` forces the general path.
+
+The fused backward is opt-in: with the class attribute ``fused_backward = True`` (default False: the general path stays twice
+differentiable, the fused one is not) an input that requires grad while grad is enabled, under every other condition of the fused
+path, runs the recording forward bgk_pair_langevin_record -- the same q, v and dW bit for bit, plus the state after every step -- and its
+``autograd.Function`` (``_BrownianFn`` / ``_LangevinFn``, once differentiable) sweeps the recorded run backwards with
+bgk_pair_langevin_backward, in launches of at most ``LANGEVIN_BACKWARD_MAX_STEPS_PER_LAUNCH`` steps, last segment first: one gradient
+and one Hessian-vector product of the pair energy per state for Brownian, one Hessian-vector product for Langevin, whose noise the
+kernel regenerates from the saved stream position (or reads from the fed slices).  The recorded states take ``nsteps B n d 4`` bytes
+(twice that for Langevin); above ``LANGEVIN_BACKWARD_MAX_BYTES`` the layer takes the general path with a ``RuntimeWarning``.
+``MetropolisMCFlow`` with ``fused_backward``: the fused forward, and g_x = g_y + g_dW (dE/dx(y) - dE/dx(x)) from two
+bgk_pair_energy_backward launches (the reference's selection (1 - acc) x + acc xprop has the identity as its Jacobian).
 
 Random numbers of the fused path come from the object's Philox stream (``_FusedSampling``: key from ``torch.initial_seed()``, rank and
 stream id, the per-object counter is the index of the next step, both travel in ``state_dict``), unless ``feed_noise`` has handed the
@@ -22,6 +33,7 @@ object explicit ones; fed numbers are also what the general path then uses, one 
 the batch's first row: a batch sharded over processes draws the numbers of the whole.
 """
 import math
+import warnings
 
 import torch
 
@@ -36,6 +48,17 @@ __all__ = ["BrownianFlow", "OverdampedLangevinFlow", "LangevinFlow", "Metropolis
 # one launch of 16 steps takes 38.66 ms for Brownian (2.42 ms per step) and 61.62 ms for Langevin (61.32 .. 61.95 over three rounds,
 # 3.85 ms per step), so 64 steps of the slower one are 0.246 s.
 LANGEVIN_MAX_STEPS_PER_LAUNCH = 64
+
+# The most steps one launch of bgk_pair_langevin_backward sweeps, by the same rule: no launch longer than a quarter of a second at the
+# widest shape.  Measured on an MI355X (tools/langevin_time.py --backward --cap-steps 4, its last lines): at Lennard-Jones, n = 64, d = 3,
+# 2^16 samples one launch over 4 steps (the run's first segment: five states) takes 35.77 ms for Brownian (35.32 .. 36.15 over three
+# rounds, 8.94 ms per step: a gradient and a Hessian-vector product per state) and 27.23 ms for Langevin (27.04 .. 27.32, 6.81 ms per
+# step), 3.7 and 1.8 times the forward's step.  24 steps of the slower one are 0.215 s (27 would be 0.241 s).
+LANGEVIN_BACKWARD_MAX_STEPS_PER_LAUNCH = 24
+
+# The most bytes of recorded states (nsteps B n d 4, twice that for Langevin) the fused backward keeps; beyond, the general path.  A
+# policy constant, not a measurement: 1 GiB beside the model's activations.
+LANGEVIN_BACKWARD_MAX_BYTES = 2 ** 30
 
 
 def _is_number(*values):
@@ -65,21 +88,28 @@ def _row_sum(t):
     return t.reshape(t.shape[0], -1).sum(dim=1, keepdim=True)
 
 
+def _check_launch(name, plan, q, v, w1, w2, tensors):
+    """the argument checks of the bgk_pair_langevin* wrappers: ``tensors`` = (tensor or None, shape) pairs"""
+    nd = q.shape[1]
+    if nd != plan.n_particles * plan.n_dims:
+        raise ValueError(f"{name}: q has {nd} columns, the target {plan.n_particles} x {plan.n_dims}")
+    if (w2 is not None) != (w1 is not None and v is not None):
+        raise ValueError(f"{name}: w1 alone without velocities, w1 and w2 with them")
+    for t, shape in tensors:
+        if t is None:
+            continue
+        if not (t.is_cuda and t.device == q.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"{name}: expected a contiguous float32 HIP tensor of shape {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
 def pair_langevin(plan, q, v, stepsize, mass, gamma, kT, n_steps, dW, w1=None, w2=None, seed=0, offset=0, row0=0, accumulate=False):
     """One launch of bgk_pair_langevin: ``n_steps`` Brownian (``v`` None) or Langevin steps of q (and v) [B, n d] (f32, contiguous, HIP;
     updated IN PLACE) on the target of the ``PairPlan``.  dW [B]: written, or added to with ``accumulate``.  w1 (and, with v, w2)
     [n_steps, B, n d], or neither (Philox numbers of (seed, offset + step, row row0 + b))."""
     from . import _lib
     B, nd = q.shape
-    if nd != plan.n_particles * plan.n_dims:
-        raise ValueError(f"pair_langevin: q has {nd} columns, the target {plan.n_particles} x {plan.n_dims}")
-    if (w2 is not None) != (w1 is not None and v is not None):
-        raise ValueError("pair_langevin: w1 alone without velocities, w1 and w2 with them")
-    for t, shape in ((q, (B, nd)), (v, (B, nd)), (dW, (B,)), (w1, (n_steps, B, nd)), (w2, (n_steps, B, nd))):
-        if t is None:
-            continue
-        if not (t.is_cuda and t.device == q.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError(f"pair_langevin: expected a contiguous float32 HIP tensor of shape {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    _check_launch("pair_langevin", plan, q, v, w1, w2,
+                  ((q, (B, nd)), (v, (B, nd)), (dW, (B,)), (w1, (n_steps, B, nd)), (w2, (n_steps, B, nd))))
     with torch.cuda.device(q.device):
         st = _lib.lib().bgk_pair_langevin(_lib.ptr(q), _lib.ptr(v), B, plan.n_particles, plan.n_dims, plan.kind, plan.p0, plan.p1, plan.p2,
                                           plan.p3, plan.osc_scale, float(stepsize), float(mass), float(gamma), float(kT), int(n_steps),
@@ -88,9 +118,138 @@ def pair_langevin(plan, q, v, stepsize, mass, gamma, kT, n_steps, dW, w1=None, w
     _lib.check(st, "bgk_pair_langevin")
 
 
+def pair_langevin_record(plan, q, v, stepsize, mass, gamma, kT, n_steps, dW, traj_q, traj_v=None, w1=None, w2=None, seed=0, offset=0, row0=0,
+                         accumulate=False):
+    """One launch of bgk_pair_langevin_record: ``pair_langevin`` (the same q, v, dW bit for bit) that also writes the state after every
+    step into traj_q [n_steps, B, n d] and, with velocities, traj_v."""
+    from . import _lib
+    B, nd = q.shape
+    if (traj_v is None) != (v is None):
+        raise ValueError("pair_langevin_record: traj_v exactly with velocities")
+    _check_launch("pair_langevin_record", plan, q, v, w1, w2,
+                  ((q, (B, nd)), (v, (B, nd)), (dW, (B,)), (w1, (n_steps, B, nd)), (w2, (n_steps, B, nd)), (traj_q, (n_steps, B, nd)),
+                   (traj_v, (n_steps, B, nd))))
+    with torch.cuda.device(q.device):
+        st = _lib.lib().bgk_pair_langevin_record(_lib.ptr(q), _lib.ptr(v), B, plan.n_particles, plan.n_dims, plan.kind, plan.p0, plan.p1,
+                                                 plan.p2, plan.p3, plan.osc_scale, float(stepsize), float(mass), float(gamma), float(kT),
+                                                 int(n_steps), _lib.ptr(w1), _lib.ptr(w2), int(seed) & (2 ** 64 - 1),
+                                                 int(offset) & 0xffffffff, int(row0), _lib.ptr(dW), int(bool(accumulate)), _lib.ptr(traj_q),
+                                                 _lib.ptr(traj_v), _lib.stream_ptr(q.device))
+    _lib.check(st, "bgk_pair_langevin_record")
+
+
+def pair_langevin_backward(plan, q0, v0, traj_q, traj_v, stepsize, mass, gamma, kT, g_dW, gq, gv, carry, first, w1=None, w2=None, seed=0,
+                           offset=0, row0=0):
+    """One launch of bgk_pair_langevin_backward: the reverse sweep over a recorded segment.  q0 (v0) [B, n d]: the state before the
+    segment, traj_q (traj_v) [n_steps, B, n d]: the states after its steps, w1 / w2 or (seed, offset, row0): the noise of these steps as
+    the forward launch had it, g_dW [B]: d L / d dW.  gq (gv) and carry [B, n d] are updated IN PLACE: before the last segment's sweep
+    gq (gv) = d L / d (final state) and carry = 0; after the first segment's (``first``) gq (gv) = d L / d (initial state)."""
+    from . import _lib
+    B, nd = q0.shape
+    n_steps = traj_q.shape[0]
+    if not (v0 is None) == (traj_v is None) == (gv is None):
+        raise ValueError("pair_langevin_backward: v0, traj_v and gv go together")
+    _check_launch("pair_langevin_backward", plan, q0, v0, w1, w2,
+                  ((q0, (B, nd)), (v0, (B, nd)), (traj_q, (n_steps, B, nd)), (traj_v, (n_steps, B, nd)), (g_dW, (B,)), (gq, (B, nd)),
+                   (gv, (B, nd)), (carry, (B, nd)), (w1, (n_steps, B, nd)), (w2, (n_steps, B, nd))))
+    with torch.cuda.device(q0.device):
+        st = _lib.lib().bgk_pair_langevin_backward(_lib.ptr(q0), _lib.ptr(v0), _lib.ptr(traj_q), _lib.ptr(traj_v), B, plan.n_particles,
+                                                   plan.n_dims, plan.kind, plan.p0, plan.p1, plan.p2, plan.p3, plan.osc_scale,
+                                                   float(stepsize), float(mass), float(gamma), float(kT), int(n_steps), _lib.ptr(w1),
+                                                   _lib.ptr(w2), int(seed) & (2 ** 64 - 1), int(offset) & 0xffffffff, int(row0),
+                                                   _lib.ptr(g_dW), _lib.ptr(gq), _lib.ptr(gv), _lib.ptr(carry), int(bool(first)),
+                                                   _lib.stream_ptr(q0.device))
+    _lib.check(st, "bgk_pair_langevin_backward")
+
+
+class _IntegratorFn(torch.autograd.Function):
+    """``BrownianFlow`` / ``LangevinFlow`` on the recording forward, with the adjoint sweep of bgk_pair_langevin_backward as backward:
+    ``apply(flow, plan, *xs)`` -> (*ys, dW [B, 1]).  Saved: the inputs, the recorded states and, for Langevin, the fed slices (views of
+    the caller's tensors) or the stream position."""
+
+    @staticmethod
+    def forward(ctx, flow, plan, *xs):
+        q = xs[0]
+        B, nd = q.shape
+        n_steps = flow.nsteps
+        fed, seed, offset = flow._stream(q, n_steps)
+        settings = flow._launch_settings()
+        state = [x.detach().clone() for x in xs]
+        traj = [torch.empty((n_steps, B, nd), dtype=torch.float32, device=q.device) for _ in xs]
+        dW = torch.empty(B, dtype=torch.float32, device=q.device)
+        done = 0
+        for k in _split(n_steps, LANGEVIN_MAX_STEPS_PER_LAUNCH):
+            noise = [None, None] if fed is None else [t[done:done + k] for t in fed] + [None] * (2 - len(fed))
+            pair_langevin_record(plan, state[0], state[1] if len(xs) == 2 else None, *settings, k, dW, traj[0][done:done + k],
+                                 traj[1][done:done + k] if len(xs) == 2 else None, noise[0], noise[1], seed, offset + done,
+                                 flow.chain_offset, accumulate=done > 0)
+            done += k
+        keep = (fed or []) if len(xs) == 2 else []      # the Brownian sweep needs no noise
+        ctx.save_for_backward(*[x.detach() for x in xs], *traj, *keep)
+        ctx.cfg = (plan, settings, len(xs), seed, offset, flow.chain_offset)
+        return (*state, dW[:, None])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        plan, settings, n_in, seed, offset, row0 = ctx.cfg
+        saved = ctx.saved_tensors
+        x0, traj, fed = saved[:n_in], saved[n_in:2 * n_in], saved[2 * n_in:]
+        n_steps = traj[0].shape[0]
+        adj = [g.to(torch.float32).contiguous().clone() for g in grads[:n_in]]
+        g_dW = grads[n_in].reshape(-1).to(torch.float32).contiguous()
+        carry = torch.zeros_like(adj[0])
+        sizes = _split(n_steps, LANGEVIN_BACKWARD_MAX_STEPS_PER_LAUNCH)
+        starts = [sum(sizes[:i]) for i in range(len(sizes))]
+        for s, k in reversed(list(zip(starts, sizes))):
+            before = [x0[i] if s == 0 else traj[i][s - 1] for i in range(n_in)]
+            noise = [t[s:s + k] for t in fed] + [None] * (2 - len(fed))
+            pair_langevin_backward(plan, before[0], before[1] if n_in == 2 else None, traj[0][s:s + k], traj[1][s:s + k] if n_in == 2 else None,
+                                   *settings, g_dW, adj[0], adj[1] if n_in == 2 else None, carry, s == 0, noise[0], noise[1], seed,
+                                   offset + s, row0)
+        return (None, None, *adj)
+
+
+# Two names on purpose: an output's ``grad_fn`` says which layer made it (the tests assert the names).  Do not fold them into one.
+class _BrownianFn(_IntegratorFn):
+    """``BrownianFlow`` with the fused backward"""
+
+
+class _LangevinFn(_IntegratorFn):
+    """``LangevinFlow`` with the fused backward"""
+
+
+class _MetropolisFn(torch.autograd.Function):
+    """``MetropolisMCFlow`` on its fused forward; backward g_x = g_y + g_dW (dE/dx(y) - dE/dx(x)), two bgk_pair_energy_backward launches"""
+
+    @staticmethod
+    def forward(ctx, flow, setup, x):
+        y, dW = flow._fused_forward(x, setup)
+        ctx.save_for_backward(x.detach(), y)
+        ctx.plan = setup[0]
+        return y, dW
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_y, g_dW):
+        from . import _lib, particles
+        x, y = ctx.saved_tensors
+        g = g_dW.reshape(-1).to(torch.float32).contiguous()
+        out = g_y.to(torch.float32).clone()
+        for state, g_u in ((y, g), (x, -g)):
+            gx = torch.empty_like(state)
+            with torch.cuda.device(state.device):
+                st = _lib.lib().bgk_pair_energy_backward(*particles._launch_args(ctx.plan, state), _lib.ptr(g_u), None, None, None, 0, None,
+                                                         _lib.ptr(gx), gx.shape[1], _lib.stream_ptr(state.device))
+            _lib.check(st, "bgk_pair_energy_backward")
+            out += gx
+        return None, None, out
+
+
 class _StochasticFlow(Flow, _FusedSampling):
     """what the three layers share: the settings, fed random numbers, the conditions of the fused path and its Philox position"""
     fused = True
+    fused_backward = False     # opt in to the once-differentiable fused backward (module docstring)
 
     def __init__(self, energy_model, nsteps, stepsize):
         super().__init__()
@@ -149,6 +308,31 @@ class _StochasticFlow(Flow, _FusedSampling):
                 return None
         return plan, xs[0].shape[0]
 
+    def _traj_bytes(self, B, nd):
+        """bytes of recorded states the fused backward keeps for a [B, n d] batch"""
+        return 0
+
+    def _fused_train_setup(self, *xs):
+        """(plan, B) if the fused backward takes these inputs -- the conditions of ``_fused_setup`` but for the inputs' requires_grad,
+        and the recorded states within ``LANGEVIN_BACKWARD_MAX_BYTES`` (else one RuntimeWarning) -- else None.  ``_forward`` asks only
+        with ``fused_backward`` set, grad enabled and an input that requires grad."""
+        with torch.no_grad():
+            setup = self._fused_setup(*xs)
+        if setup is None:
+            return None
+        need = self._traj_bytes(setup[1], xs[0].shape[1])
+        if need > LANGEVIN_BACKWARD_MAX_BYTES:
+            warnings.warn(f"{type(self).__name__}: the fused backward would record {need} bytes of states, more than "
+                          f"LANGEVIN_BACKWARD_MAX_BYTES = {LANGEVIN_BACKWARD_MAX_BYTES}; taking the general path", RuntimeWarning, stacklevel=3)
+            return None
+        return setup
+
+    def _trains_fused(self, *xs):
+        """the setup of the fused backward, or None: asked only when the layer is to be differentiated"""
+        if not (self.fused_backward and torch.is_grad_enabled() and any(torch.is_tensor(x) and x.requires_grad for x in xs)):
+            return None
+        return self._fused_train_setup(*xs)
+
     def _stream(self, x, total):
         """(fed tensors of the next ``total`` steps or None, seed, offset) and the stream / fed position advanced by ``total``"""
         fed = self._fed
@@ -187,6 +371,9 @@ class BrownianFlow(_StochasticFlow):
         setup = self._fused_setup(x)
         if setup is not None:
             return self._fused_forward(x, setup)
+        setup = self._trains_fused(x)
+        if setup is not None:
+            return _BrownianFn.apply(self, setup[0], x)
         dW = torch.zeros((x.shape[0], 1), dtype=x.dtype, device=x.device)
         root = math.sqrt(2 * self.stepsize)
         f = _force(self.energy_model, x) if self.nsteps > 0 else None
@@ -204,6 +391,12 @@ class BrownianFlow(_StochasticFlow):
             # update state
             x = y
         return x, dW
+
+    def _traj_bytes(self, B, nd):
+        return self.nsteps * B * nd * 4
+
+    def _launch_settings(self):
+        return self.stepsize, 1.0, 0.0, 1.0
 
     def _fused_forward(self, x, setup):
         plan, B = setup
@@ -250,6 +443,9 @@ class LangevinFlow(_StochasticFlow):
         setup = self._fused_setup(q, v)
         if setup is not None:
             return self._fused_forward(q, v, setup)
+        setup = self._trains_fused(q, v)
+        if setup is not None:
+            return _LangevinFn.apply(self, setup[0], q, v)
         dW = torch.zeros((q.shape[0], 1), dtype=q.dtype, device=q.device)
         gamma_m = self.gamma * self.mass
         # naming convention: 1, h, 2 timesteps. _: backward
@@ -276,6 +472,12 @@ class LangevinFlow(_StochasticFlow):
             # update state
             q1, v1, f1 = q2, v2, f2
         return q1, v1, dW
+
+    def _traj_bytes(self, B, nd):
+        return 2 * self.nsteps * B * nd * 4
+
+    def _launch_settings(self):
+        return self.stepsize, self.mass, self.gamma, self.kT
 
     def _fused_forward(self, q, v, setup):
         plan, B = setup
@@ -314,6 +516,9 @@ class MetropolisMCFlow(_StochasticFlow):
         setup = self._fused_setup(x)
         if setup is not None:
             return self._fused_forward(x, setup)
+        setup = self._trains_fused(x)
+        if setup is not None:
+            return _MetropolisFn.apply(self, setup, x)
         E0 = self.energy_model.energy(x)
         E = E0
         batch = (x.shape[0],) + (1,) * (x.dim() - 1)

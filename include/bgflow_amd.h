@@ -708,6 +708,12 @@ int bgk_pair_energy_backward(const float* x, int64_t ldx, int64_t B, int32_t n_p
                              double p0, double p1, double p2, double p3, double osc_scale, double temperature,
                              const float* g_u, const float* g_scalar, const float* u, const float* dlogp, int32_t drop_nonfinite,
                              float* g_dlogp, float* g_x, int64_t ldg, void* stream);
+/* bgk_pair_energy_hvp: g_out[b] = (d e / d x)(x[b]) / temperature (may be NULL) and hu_out[b] = (d^2 e / d x^2)(x[b]) u[b] / temperature in
+ *   one pass over the pairs of a sample; u, g_out, hu_out [B, n d] with contiguous rows.  g_out has the bits of bgk_pair_energy_backward
+ *   with g_u = 1.  The double-well pair term at d_ij = 0 contributes 0 to both. */
+int bgk_pair_energy_hvp(const float* x, int64_t ldx, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
+                        double p0, double p1, double p2, double p3, double osc_scale, double temperature,
+                        const float* u, float* g_out, float* hu_out, void* stream);
 
 /* Equivariant kernel dynamics of a particle system x [B, n_particles * n_dims] (contiguous rows) and its fixed-step integration
  * (csrc/bgk_kdyn.hip), one lane per sample, the sample's row in LDS -- no [B, n, n - 1, d] distance-vector or [B, n, n - 1, K] kernel tensor:
@@ -779,6 +785,28 @@ int bgk_pair_langevin(float* q, float* v, int64_t B, int32_t n_particles, int32_
                       double stepsize, double mass, double gamma, double kT, int32_t n_steps,
                       const float* w1, const float* w2, uint64_t seed, uint32_t offset, int64_t row0,
                       float* dW, int32_t accumulate, void* stream);
+
+/* Training through bgk_pair_langevin: a recording forward and the adjoint sweep over what it recorded (csrc/bgk_langevin.hip).
+ * bgk_pair_langevin_record: bgk_pair_langevin -- the same q, v and dW bit for bit -- that also writes the state after every step:
+ *   traj_q [n_steps, B, n d] and, with velocities, traj_v.
+ * bgk_pair_langevin_backward: one reverse sweep over a recorded segment of n_steps steps for the loss L with d L / d dW[b] = g_dW[b]:
+ *   q0 (v0) the state before the segment, traj_q (traj_v) the states after its steps, the noise specification of the forward launch of
+ *   these steps (w1 / w2, or seed, offset, row0: the kernel regenerates the numbers; Brownian needs none and ignores them).
+ *   gq (gv) [B, n d]: the running adjoints, updated in place; carry [B, n d]: a third running vector that travels with them.  Before
+ *   the sweep of the LAST segment of a run gq (gv) = d L / d (final state) and carry = 0; the segments are then swept last one first on
+ *   the same three buffers, first != 0 for the run's first segment, after which gq (gv) = d L / d (initial state).  The result does
+ *   not depend on the split, bit for bit.  Envelope as bgk_pair_langevin. */
+int bgk_pair_langevin_record(float* q, float* v, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
+                             double p0, double p1, double p2, double p3, double osc_scale,
+                             double stepsize, double mass, double gamma, double kT, int32_t n_steps,
+                             const float* w1, const float* w2, uint64_t seed, uint32_t offset, int64_t row0,
+                             float* dW, int32_t accumulate, float* traj_q, float* traj_v, void* stream);
+int bgk_pair_langevin_backward(const float* q0, const float* v0, const float* traj_q, const float* traj_v, int64_t B,
+                               int32_t n_particles, int32_t n_dims, int32_t kind,
+                               double p0, double p1, double p2, double p3, double osc_scale,
+                               double stepsize, double mass, double gamma, double kT, int32_t n_steps,
+                               const float* w1, const float* w2, uint64_t seed, uint32_t offset, int64_t row0,
+                               const float* g_dW, float* gq, float* gv, float* carry, int32_t first, void* stream);
 
 /* Prior sampling in one launch from a counter-based generator (Philox4x32-10; counter = (global row, field, 4-column block, offset),
  * key = seed: independent of launch geometry and of the sharding of a batch, row0 = first global row of this launch), replacing
