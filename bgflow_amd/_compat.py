@@ -41,6 +41,7 @@ _MAP = {
     "distribution.energy": ("distributions", "particles"),
     "distribution.energy.lennard_jones": "particles",
     "distribution.energy.multi_double_well_potential": "particles",
+    "distribution.energy.particles": "particles",
     "distribution.energy.base": "distributions",
     "distribution.energy.double_well": "distributions",
     "distribution.energy.clipped": "clipped",

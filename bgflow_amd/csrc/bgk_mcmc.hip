@@ -1,7 +1,8 @@
 /* bgk_mcmc.hip -- Metropolis chains on a particle-system target, a whole run of steps in one launch
  *   MCMCStep._step with a GaussianProposal (bgflow/distribution/sampling/mcmc.py:29-46, 86-122) and metropolis_accept (mcmc.py:192-222):
  *     x' = x + noise_std eps,  accept iff min(0, -(e(x') - e(x)) / T) >= log r,  eps ~ N(0, 1)^{n d}, r ~ U(0, 1)
- *   on the targets of bgk_pair.hip (kind 0 Lennard-Jones, 1 multi-double-well, 2 mean-free normal).  In stock ops one step is about a dozen
+ *   on the targets of bgk_pair.hip (kind 0 Lennard-Jones, 1 multi-double-well, 2 mean-free normal; through bgk_box_mcmc kind 3 / 4, the
+ *   particle box).  In stock ops one step is about a dozen
  *   launches (randn_like, add, the energy's op chain, rand_like, log, min, compare, two where) over a state of n d <= 192 floats per chain;
  *   here the state of a chain never leaves LDS between recorded frames.
  *
@@ -23,7 +24,8 @@
  *
  * Envelope 2 <= n <= 64, 1 <= d <= 3.  Dynamic LDS <= 63,488 B: rows per tile = the most (<= 64) with (round32(rows S) + rows S) 4 B within
  * it; lanes beyond the rows only stage and store:
- *   n d = 192 (S = 193): 41 rows, 63,396 B       LJ13 (S = 39): 64 rows, 19,968 B       DW4 (S = 9): 64 rows, 4,608 B */
+ *   n d = 192 (S = 193): 41 rows, 63,396 B       LJ13 (S = 39): 64 rows, 19,968 B       DW4 (S = 9): 64 rows, 4,608 B
+ *   the particle box of 38 particles (S = 77): 64 rows, 39,424 B       of 64 particles (S = 129): 61 rows, 62,964 B */
 #include "bgk_common.h"
 #include "bgk_pair_terms.h"
 #include "bgk_philox.h"
@@ -39,6 +41,7 @@ struct McArgs {
     float* x; int64_t B, row0;
     int n, nd, rows, tile_b; uint32_t magic;            /* tile_b: word offset of the second tile, a multiple of 32 */
     float p0, p1, p2, p3, osc;
+    BgkBoxParams box;                                   /* kinds 3 / 4 (the particle box) */
     float* e; int e_valid;
     float temperature; const float* temperatures;
     float noise_std; int n_steps;
@@ -47,6 +50,13 @@ struct McArgs {
     float* traj; float* traj_e; int traj_every;
     int* n_accepted; int accumulate;
 };
+
+/* e(row) at temperature 1: the call of pair_energy_kernel */
+template <int D, int KIND>
+__device__ __forceinline__ float mc_row_energy(const float* xr, int n, const McArgs& a, float rm2) {
+    if constexpr (KIND >= 3) return (float)bgk_box_row_energy<KIND>(xr, n, a.box);
+    else return (float)bgk_pair_row_energy<D, KIND>(xr, n, a.p0, a.p1, a.p2, a.p3, rm2, a.osc);
+}
 
 template <int D, int KIND>
 __global__ __launch_bounds__(MC_THREADS) void pair_mcmc_kernel(McArgs a) {
@@ -71,7 +81,7 @@ __global__ __launch_bounds__(MC_THREADS) void pair_mcmc_kernel(McArgs a) {
         float e = 0.0f, temp = 1.0f;
         if (active) {
             temp = a.temperatures ? a.temperatures[b] : a.temperature;
-            e = a.e_valid ? a.e[b] : (float)bgk_pair_row_energy<D, KIND>(s_mem + tid * S, n, a.p0, a.p1, a.p2, a.p3, rm2, a.osc);
+            e = a.e_valid ? a.e[b] : mc_row_energy<D, KIND>(s_mem + tid * S, n, a, rm2);
         }
         int frame = 0, since = 0;
         for (int step = 0; step < a.n_steps; ++step) {
@@ -99,7 +109,7 @@ __global__ __launch_bounds__(MC_THREADS) void pair_mcmc_kernel(McArgs a) {
                     philox4x32_10(r_lo, r_hi, 1u << 20, off, a.seed_lo, a.seed_hi, o);
                     r = u01(o[0]);
                 }
-                const float ep = (float)bgk_pair_row_energy<D, KIND>(xp, n, a.p0, a.p1, a.p2, a.p3, rm2, a.osc);
+                const float ep = mc_row_energy<D, KIND>(xp, n, a, rm2);
                 const bool accept = -(ep - e) / temp >= bgk_logf(r);      /* false for a NaN on either side */
                 cur = accept ? cur ^ 1 : cur;
                 e = accept ? ep : e;
@@ -142,44 +152,105 @@ void launch_mcmc(int d, int grid, size_t lds, hipStream_t s, const McArgs& a) {
 
 }  // namespace
 
+namespace {
+
+/* one call of either entry; is_box: the particle box, kinds 3 / 4 with a host parameter array instead of p0..p3, osc_scale */
+struct BgkMcmcCall {
+    const char* what;
+    float* x; int64_t B; int32_t n_particles, n_dims, kind;
+    double p0, p1, p2, p3, osc_scale;
+    const float* box_params; int32_t n_box_params; int32_t is_box;
+    float* e; int32_t e_valid; double temperature; const float* temperatures;
+    double noise_std; int32_t n_steps; const float* noise; const float* uniforms;
+    uint64_t seed; uint32_t offset; int64_t row0;
+    float* traj; float* traj_e; int32_t traj_every; int32_t* n_accepted; int32_t accumulate;
+    void* stream;
+};
+
+int mcmc_run(const BgkMcmcCall& c) {
+    const char* what = c.what;
+    const int64_t B = c.B;
+    const int32_t n_particles = c.n_particles, n_dims = c.n_dims, kind = c.kind;
+    BGK_CHECK_ARG(B >= 0 && c.row0 >= 0 && c.n_steps >= 0, "%s: bad batch size / row0 / n_steps", what);
+    if (c.is_box) {
+        BGK_CHECK_ARG(kind == 3 || kind == 4, "%s: kind %d (3 repulsive particles, 4 harmonic particles)", what, kind);
+        BGK_CHECK_ARG(c.box_params && c.n_box_params == BGK_BOX_N_PARAMS, "%s: params must be %d floats (see bgflow_amd.h)", what,
+                      BGK_BOX_N_PARAMS);
+    } else {
+        BGK_CHECK_ARG(kind >= 0 && kind <= 2, "%s: kind %d (0 Lennard-Jones, 1 multi-double-well, 2 mean-free normal)", what, kind);
+    }
+    if (!(n_particles >= 2 && n_particles <= MC_MAX_N && n_dims >= 1 && n_dims <= MC_MAX_D)) {
+        bgk_set_error("%s: %d particles in %d dimensions are outside the kernel's envelope (2..%d particles, 1..%d dimensions)", what,
+                      n_particles, n_dims, MC_MAX_N, MC_MAX_D);
+        return BGK_EUNSUPPORTED;
+    }
+    BGK_CHECK_ARG(c.temperatures || c.temperature > 0.0, "%s: the temperature must be positive", what);
+    BGK_CHECK_ARG(c.noise_std >= 0.0, "%s: noise_std must not be negative", what);
+    BGK_CHECK_ARG((c.noise != nullptr) == (c.uniforms != nullptr), "%s: noise and uniforms go together", what);
+    BGK_CHECK_ARG(!c.traj_e || c.traj, "%s: traj_e without traj", what);
+    BGK_CHECK_ARG(!c.traj || c.traj_every >= 1, "%s: traj_every %d", what, c.traj_every);
+    if (B == 0) return 0;
+    BGK_CHECK_ARG(c.x && c.e, "%s: null tensor", what);
+    McArgs a{};
+    a.x = c.x; a.B = B; a.row0 = c.row0; a.n = n_particles; a.nd = n_particles * n_dims;
+    a.magic = (uint32_t)(((1ull << 32) + (uint64_t)a.nd - 1) / (uint64_t)a.nd);
+    const int S = a.nd | 1;
+    int rows = MC_THREADS;
+    while ((((rows * S + 31) & ~31) + rows * S) * (int)sizeof(float) > MC_LDS_DYNAMIC) --rows;
+    a.rows = rows; a.tile_b = (rows * S + 31) & ~31;
+    a.p0 = (float)c.p0; a.p1 = (float)c.p1; a.p2 = (float)c.p2; a.p3 = (float)c.p3; a.osc = (float)c.osc_scale;
+    if (c.is_box) bgk_box_params_from_host(c.box_params, &a.box);
+    a.e = c.e; a.e_valid = c.e_valid != 0; a.temperature = (float)c.temperature; a.temperatures = c.temperatures;
+    a.noise_std = (float)c.noise_std; a.n_steps = c.n_steps; a.noise = c.noise; a.uniforms = c.uniforms;
+    a.seed_lo = (uint32_t)c.seed; a.seed_hi = (uint32_t)(c.seed >> 32); a.offset = c.offset;
+    a.traj = c.traj; a.traj_e = c.traj_e; a.traj_every = c.traj_every; a.n_accepted = c.n_accepted; a.accumulate = c.accumulate != 0;
+    const size_t lds = (size_t)(a.tile_b + rows * S) * sizeof(float);
+    const int64_t n_tiles = (B + rows - 1) / rows;
+    const int grid = (int)(n_tiles < MC_MAX_GRID ? n_tiles : MC_MAX_GRID);
+    hipStream_t s = (hipStream_t)c.stream;
+    if (kind == 0) launch_mcmc<0>(n_dims, grid, lds, s, a);
+    else if (kind == 1) launch_mcmc<1>(n_dims, grid, lds, s, a);
+    else if (kind == 2) launch_mcmc<2>(n_dims, grid, lds, s, a);
+    else if (kind == 3) hipLaunchKernelGGL((pair_mcmc_kernel<2, 3>), dim3(grid), dim3(MC_THREADS), lds, s, a);
+    else hipLaunchKernelGGL((pair_mcmc_kernel<2, 4>), dim3(grid), dim3(MC_THREADS), lds, s, a);
+    return bgk_launch_status(what);
+}
+
+}  // namespace
+
 extern "C" int bgk_pair_mcmc(float* x, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
                              double p0, double p1, double p2, double p3, double osc_scale,
                              float* e, int32_t e_valid, double temperature, const float* temperatures,
                              double noise_std, int32_t n_steps, const float* noise, const float* uniforms,
                              uint64_t seed, uint32_t offset, int64_t row0,
                              float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream) {
-    BGK_CHECK_ARG(B >= 0 && row0 >= 0 && n_steps >= 0, "bgk_pair_mcmc: bad batch size / row0 / n_steps");
-    BGK_CHECK_ARG(kind >= 0 && kind <= 2, "bgk_pair_mcmc: kind %d (0 Lennard-Jones, 1 multi-double-well, 2 mean-free normal)", kind);
-    if (!(n_particles >= 2 && n_particles <= MC_MAX_N && n_dims >= 1 && n_dims <= MC_MAX_D)) {
-        bgk_set_error("bgk_pair_mcmc: %d particles in %d dimensions are outside the kernel's envelope (2..%d particles, 1..%d dimensions)",
-                      n_particles, n_dims, MC_MAX_N, MC_MAX_D);
-        return BGK_EUNSUPPORTED;
-    }
-    BGK_CHECK_ARG(temperatures || temperature > 0.0, "bgk_pair_mcmc: the temperature must be positive");
-    BGK_CHECK_ARG(noise_std >= 0.0, "bgk_pair_mcmc: noise_std must not be negative");
-    BGK_CHECK_ARG((noise != nullptr) == (uniforms != nullptr), "bgk_pair_mcmc: noise and uniforms go together");
-    BGK_CHECK_ARG(!traj_e || traj, "bgk_pair_mcmc: traj_e without traj");
-    BGK_CHECK_ARG(!traj || traj_every >= 1, "bgk_pair_mcmc: traj_every %d", traj_every);
-    if (B == 0) return 0;
-    BGK_CHECK_ARG(x && e, "bgk_pair_mcmc: null tensor");
-    McArgs a{};
-    a.x = x; a.B = B; a.row0 = row0; a.n = n_particles; a.nd = n_particles * n_dims;
-    a.magic = (uint32_t)(((1ull << 32) + (uint64_t)a.nd - 1) / (uint64_t)a.nd);
-    const int S = a.nd | 1;
-    int rows = MC_THREADS;
-    while ((((rows * S + 31) & ~31) + rows * S) * (int)sizeof(float) > MC_LDS_DYNAMIC) --rows;
-    a.rows = rows; a.tile_b = (rows * S + 31) & ~31;
-    a.p0 = (float)p0; a.p1 = (float)p1; a.p2 = (float)p2; a.p3 = (float)p3; a.osc = (float)osc_scale;
-    a.e = e; a.e_valid = e_valid != 0; a.temperature = (float)temperature; a.temperatures = temperatures;
-    a.noise_std = (float)noise_std; a.n_steps = n_steps; a.noise = noise; a.uniforms = uniforms;
-    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.offset = offset;
-    a.traj = traj; a.traj_e = traj_e; a.traj_every = traj_every; a.n_accepted = n_accepted; a.accumulate = accumulate != 0;
-    const size_t lds = (size_t)(a.tile_b + rows * S) * sizeof(float);
-    const int64_t n_tiles = (B + rows - 1) / rows;
-    const int grid = (int)(n_tiles < MC_MAX_GRID ? n_tiles : MC_MAX_GRID);
-    hipStream_t s = (hipStream_t)stream;
-    if (kind == 0) launch_mcmc<0>(n_dims, grid, lds, s, a);
-    else if (kind == 1) launch_mcmc<1>(n_dims, grid, lds, s, a);
-    else launch_mcmc<2>(n_dims, grid, lds, s, a);
-    return bgk_launch_status("bgk_pair_mcmc");
+    BgkMcmcCall c{};
+    c.what = "bgk_pair_mcmc";
+    c.x = x; c.B = B; c.n_particles = n_particles; c.n_dims = n_dims; c.kind = kind;
+    c.p0 = p0; c.p1 = p1; c.p2 = p2; c.p3 = p3; c.osc_scale = osc_scale;
+    c.e = e; c.e_valid = e_valid; c.temperature = temperature; c.temperatures = temperatures;
+    c.noise_std = noise_std; c.n_steps = n_steps; c.noise = noise; c.uniforms = uniforms;
+    c.seed = seed; c.offset = offset; c.row0 = row0;
+    c.traj = traj; c.traj_e = traj_e; c.traj_every = traj_every; c.n_accepted = n_accepted; c.accumulate = accumulate;
+    c.stream = stream;
+    return mcmc_run(c);
+}
+
+/* the particle box (kinds 3 / 4 of bgk_pair_terms.h) in the same chain kernel: MCMCStep._step (mcmc.py:86-122) over
+ * RepulsiveParticles._energy / HarmonicParticles._energy (distribution/energy/particles.py:272-277, 376-381); two dimensions */
+extern "C" int bgk_box_mcmc(float* x, int64_t B, int32_t n_particles, int32_t kind, const float* params, int32_t n_params,
+                            float* e, int32_t e_valid, double temperature, const float* temperatures,
+                            double noise_std, int32_t n_steps, const float* noise, const float* uniforms,
+                            uint64_t seed, uint32_t offset, int64_t row0,
+                            float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream) {
+    BgkMcmcCall c{};
+    c.what = "bgk_box_mcmc";
+    c.x = x; c.B = B; c.n_particles = n_particles; c.n_dims = 2; c.kind = kind;
+    c.box_params = params; c.n_box_params = n_params; c.is_box = 1;
+    c.e = e; c.e_valid = e_valid; c.temperature = temperature; c.temperatures = temperatures;
+    c.noise_std = noise_std; c.n_steps = n_steps; c.noise = noise; c.uniforms = uniforms;
+    c.seed = seed; c.offset = offset; c.row0 = row0;
+    c.traj = traj; c.traj_e = traj_e; c.traj_every = traj_every; c.n_accepted = n_accepted; c.accumulate = accumulate;
+    c.stream = stream;
+    return mcmc_run(c);
 }

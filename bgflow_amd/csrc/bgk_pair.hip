@@ -5,6 +5,9 @@
  *   kind 1  MultiDoubleWellPotential (energy/multi_double_well_potential.py:37-43, utils/geometry.py:134-139):
  *           sum_{i<j} [a (d_ij - off)^4 + b (d_ij - off)^2 + c],  d_ij = |x_i - x_j| (no eps)
  *   kind 2  MeanFreeNormalDistribution (distribution/normal.py:267-283): osc_scale 0.5 sum_i |x_i - xbar|^2, osc_scale = 1 / std^2
+ *   kind 3 / 4  the particle box, RepulsiveParticles / HarmonicParticles (distribution/energy/particles.py:51-381), d = 2, through the
+ *           bgk_box_* entries at the end of this file only: a pair term over i < j except the dimer's (0, 1), the dimer's terms and the
+ *           walls' (formulas: bgk_pair_terms.h); parameters in PairArgs::box; no hvp kernel
  * u = e / T.  The reference forms the [B, n, n, d] tensor of distance vectors (or the [B, n, n] cdist matrix) and reads it back
  * several times; here a sample is read once: roofline HBM, 4 (n d + 1) B per sample forward, 4 (2 n d + 1) B backward.
  *
@@ -22,7 +25,9 @@
  *   backward  x tile + gradient tile + 64 row scales: 64 rows while 2 x 64 x S x 4 + 256 <= 65,536 B (S <= 127: 65,280 B),
  *             else 32 rows: 2 x 32 x 193 x 4 + 256 = 49,664 B at n d = 192 (lanes 32..63 only stage and store).
  *   hvp       tiles x, u, g, Hu: the most rows (<= 64) with 4 rows S 4 B <= 65,536 B: 21 rows, 64,848 B at n d = 192; 64 rows at S <= 64
- *             (LJ13: 39,936 B).  g and Hu = (d^2 e / d x^2) u of a sample in one pass over its pairs (bgk_pair_row_hvp). */
+ *             (LJ13: 39,936 B).  g and Hu = (d^2 e / d x^2) u of a sample in one pass over its pairs (bgk_pair_row_hvp).
+ *   the particle box of 38 particles (S = 77): forward 19,712 B, backward 39,680 B at 64 rows; 64 particles (S = 129): 33,024 B and
+ *             33,280 B at 32 rows */
 #include "bgk_common.h"
 #include "bgk_pair_terms.h"
 
@@ -36,6 +41,7 @@ struct PairArgs {
     const float* x; int64_t ldx; int64_t B;
     int n, nd, rows; uint32_t magic;                    /* rows per tile; magic: i / nd by multiply-high for i < 64 * 192 */
     float p0, p1, p2, p3, osc, inv_t;
+    BgkBoxParams box;                                   /* kinds 3 / 4 (the particle box) */
     float* u; const float* dlogp; int drop_nonfinite; float* partial;                     /* forward (+ loss partials [gridDim.x][2]) */
     const float* g_u; const float* g_scalar; float* g_dlogp; float* g_x; int64_t ldg;     /* backward */
     const float* vec; float* hu;                                                          /* Hessian-vector product (contiguous rows) */
@@ -64,7 +70,9 @@ __global__ __launch_bounds__(PR_THREADS) void pair_energy_kernel(PairArgs a) {
         __syncthreads();
         if (tid < rows) {
             const float* xr = s_x + tid * S;
-            const double e = bgk_pair_row_energy<D, KIND>(xr, n, a.p0, a.p1, a.p2, a.p3, rm2, a.osc);   /* bgk_pair_terms.h */
+            double e;                                                                                   /* bgk_pair_terms.h */
+            if constexpr (KIND >= 3) e = bgk_box_row_energy<KIND>(xr, n, a.box);
+            else e = bgk_pair_row_energy<D, KIND>(xr, n, a.p0, a.p1, a.p2, a.p3, rm2, a.osc);
             const float u = (float)e * a.inv_t;
             a.u[b0 + tid] = u;
             if (a.partial) {
@@ -109,7 +117,8 @@ __global__ __launch_bounds__(PR_THREADS) void pair_energy_bwd_kernel(PairArgs a)
             else gr = (!a.drop_nonfinite || __builtin_isfinite(a.u[b] - a.dlogp[b])) ? gs : 0.0f;
             if (a.g_dlogp) a.g_dlogp[b] = -gr;          /* d(sum_i (u_i - dlogp_i)) / d dlogp_i = -1 for the kept samples */
             s_scale[tid] = gr * a.inv_t;
-            bgk_pair_row_gradient<D, KIND>(s_x + tid * S, s_g + tid * S, n, a.p0, a.p1, a.p3, rm2, c12, a.osc);     /* bgk_pair_terms.h */
+            if constexpr (KIND >= 3) bgk_box_row_gradient<KIND>(s_x + tid * S, s_g + tid * S, n, a.box);              /* bgk_pair_terms.h */
+            else bgk_pair_row_gradient<D, KIND>(s_x + tid * S, s_g + tid * S, n, a.p0, a.p1, a.p3, rm2, c12, a.osc);
         }
         __syncthreads();
         for (int i = tid; i < rows * a.nd; i += PR_THREADS) {
@@ -178,12 +187,19 @@ struct BgkPairCall {
     double p0, p1, p2, p3, osc_scale, temperature;
     float* u; const float* dlogp; int32_t drop_nonfinite; float* partial; int32_t nblk; double* loss_sums;     /* forward */
     const float* g_u; const float* g_scalar; const float* u_saved; float* g_dlogp; float* g_x; int64_t ldg;   /* backward */
+    const float* box_params; int32_t n_box_params; int32_t is_box;     /* the bgk_box_* entries: kinds 3 / 4, host parameters */
     void* stream;
 };
 
 int pair_common(const BgkPairCall& c, PairArgs* a) {
     BGK_CHECK_ARG(c.B >= 0 && c.temperature > 0.0, "%s: bad batch size / temperature", c.what);
-    BGK_CHECK_ARG(c.kind >= 0 && c.kind <= 2, "%s: kind %d (0 Lennard-Jones, 1 multi-double-well, 2 mean-free normal)", c.what, c.kind);
+    if (c.is_box) {
+        BGK_CHECK_ARG(c.kind == 3 || c.kind == 4, "%s: kind %d (3 repulsive particles, 4 harmonic particles)", c.what, c.kind);
+        BGK_CHECK_ARG(c.box_params && c.n_box_params == BGK_BOX_N_PARAMS, "%s: params must be %d floats (see bgflow_amd.h)", c.what,
+                      BGK_BOX_N_PARAMS);
+    } else {
+        BGK_CHECK_ARG(c.kind >= 0 && c.kind <= 2, "%s: kind %d (0 Lennard-Jones, 1 multi-double-well, 2 mean-free normal)", c.what, c.kind);
+    }
     if (!(c.n_particles >= 2 && c.n_particles <= PR_MAX_N && c.n_dims >= 1 && c.n_dims <= PR_MAX_D)) {
         bgk_set_error("%s: %d particles in %d dimensions are outside the kernel's envelope (2..%d particles, 1..%d dimensions)", c.what,
                       c.n_particles, c.n_dims, PR_MAX_N, PR_MAX_D);
@@ -194,6 +210,7 @@ int pair_common(const BgkPairCall& c, PairArgs* a) {
     a->p0 = (float)c.p0; a->p1 = (float)c.p1; a->p2 = (float)c.p2; a->p3 = (float)c.p3; a->osc = (float)c.osc_scale;
     a->inv_t = (float)(1.0 / c.temperature);
     a->dlogp = c.dlogp; a->drop_nonfinite = c.drop_nonfinite;
+    if (c.is_box) bgk_box_params_from_host(c.box_params, &a->box);
     return 0;
 }
 
@@ -216,7 +233,9 @@ int pair_forward(const BgkPairCall& c) {
     if (c.loss_sums && grid > c.nblk) grid = c.nblk;
     if (c.kind == 0) launch_fwd<0>(c.n_dims, grid, lds, s, a);
     else if (c.kind == 1) launch_fwd<1>(c.n_dims, grid, lds, s, a);
-    else launch_fwd<2>(c.n_dims, grid, lds, s, a);
+    else if (c.kind == 2) launch_fwd<2>(c.n_dims, grid, lds, s, a);
+    else if (c.kind == 3) hipLaunchKernelGGL((pair_energy_kernel<2, 3>), dim3(grid), dim3(PR_THREADS), lds, s, a);
+    else hipLaunchKernelGGL((pair_energy_kernel<2, 4>), dim3(grid), dim3(PR_THREADS), lds, s, a);
     const int st2 = bgk_launch_status(c.what);
     if (st2 || !c.loss_sums) return st2;
     return bgk_loss_partial_reduce(c.partial, grid, c.loss_sums, c.stream);
@@ -238,7 +257,9 @@ int pair_backward(const BgkPairCall& c) {
     hipStream_t s = (hipStream_t)c.stream;
     if (c.kind == 0) launch_bwd<0>(c.n_dims, grid, lds, s, a);
     else if (c.kind == 1) launch_bwd<1>(c.n_dims, grid, lds, s, a);
-    else launch_bwd<2>(c.n_dims, grid, lds, s, a);
+    else if (c.kind == 2) launch_bwd<2>(c.n_dims, grid, lds, s, a);
+    else if (c.kind == 3) hipLaunchKernelGGL((pair_energy_bwd_kernel<2, 3>), dim3(grid), dim3(PR_THREADS), lds, s, a);
+    else hipLaunchKernelGGL((pair_energy_bwd_kernel<2, 4>), dim3(grid), dim3(PR_THREADS), lds, s, a);
     return bgk_launch_status(c.what);
 }
 
@@ -311,4 +332,43 @@ extern "C" int bgk_pair_energy_hvp(const float* x, int64_t ldx, int64_t B, int32
     c.p0 = p0; c.p1 = p1; c.p2 = p2; c.p3 = p3; c.osc_scale = osc_scale; c.temperature = temperature;
     c.g_x = g_out; c.stream = stream;
     return pair_hvp(c, u, hu_out);
+}
+
+/* The particle box (kinds 3 / 4 of bgk_pair_terms.h) on the same kernels: RepulsiveParticles._energy / HarmonicParticles._energy
+ * (bgflow/distribution/energy/particles.py:99-123, 191-210, 235-254, 272-277, 354-381) and, backward, what autograd makes of them (for the
+ * repulsive kind also force(), particles.py:161-189, 212-233, 256-270, 324-327).  Two dimensions; params: BGK_BOX_N_PARAMS host floats. */
+extern "C" int bgk_box_energy(const float* x, int64_t ldx, int64_t B, int32_t n_particles, int32_t kind, const float* params,
+                              int32_t n_params, double temperature, float* u, void* stream) {
+    BgkPairCall c{};
+    c.what = "bgk_box_energy";
+    c.x = x; c.ldx = ldx; c.B = B; c.n_particles = n_particles; c.n_dims = 2; c.kind = kind;
+    c.box_params = params; c.n_box_params = n_params; c.is_box = 1; c.temperature = temperature;
+    c.u = u; c.stream = stream;
+    return pair_forward(c);
+}
+
+extern "C" int bgk_box_energy_kl_sums(const float* x, int64_t ldx, int64_t B, int32_t n_particles, int32_t kind, const float* params,
+                                      int32_t n_params, double temperature, float* u, const float* dlogp, int32_t drop_nonfinite,
+                                      float* partial, int32_t nblk, double* loss_sums, void* stream) {
+    BGK_CHECK_ARG(loss_sums, "bgk_box_energy_kl_sums: loss_sums is NULL");
+    BgkPairCall c{};
+    c.what = "bgk_box_energy_kl_sums";
+    c.x = x; c.ldx = ldx; c.B = B; c.n_particles = n_particles; c.n_dims = 2; c.kind = kind;
+    c.box_params = params; c.n_box_params = n_params; c.is_box = 1; c.temperature = temperature;
+    c.u = u; c.dlogp = dlogp; c.drop_nonfinite = drop_nonfinite; c.partial = partial; c.nblk = nblk; c.loss_sums = loss_sums;
+    c.stream = stream;
+    return pair_forward(c);
+}
+
+extern "C" int bgk_box_energy_backward(const float* x, int64_t ldx, int64_t B, int32_t n_particles, int32_t kind, const float* params,
+                                       int32_t n_params, double temperature, const float* g_u, const float* g_scalar, const float* u,
+                                       const float* dlogp, int32_t drop_nonfinite, float* g_dlogp, float* g_x, int64_t ldg,
+                                       void* stream) {
+    BgkPairCall c{};
+    c.what = "bgk_box_energy_backward";
+    c.x = x; c.ldx = ldx; c.B = B; c.n_particles = n_particles; c.n_dims = 2; c.kind = kind;
+    c.box_params = params; c.n_box_params = n_params; c.is_box = 1; c.temperature = temperature;
+    c.g_u = g_u; c.g_scalar = g_scalar; c.u_saved = u; c.dlogp = dlogp; c.drop_nonfinite = drop_nonfinite;
+    c.g_dlogp = g_dlogp; c.g_x = g_x; c.ldg = ldg; c.stream = stream;
+    return pair_backward(c);
 }

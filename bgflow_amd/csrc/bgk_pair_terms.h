@@ -8,7 +8,15 @@
  * xr: the sample's row [n D] (LDS or registers' backing memory), read-only.
  * bgk_pair_row_gradient: d e / d x of the same row, as bgk_pair.hip's backward and bgk_langevin.hip's force both add it up.
  * bgk_pair_row_hvp: that gradient and (d^2 e / d x^2) u in one pass over the pairs, for bgk_pair.hip's hvp kernel and bgk_langevin.hip's
- * adjoint sweep. */
+ * adjoint sweep.
+ * The particle box (bgflow/distribution/energy/particles.py: a dimer, particles 0 and 1, in a bath of solvent particles in a 2-d box;
+ * rows [x0, y0, x1, y1, ...]) is two further kinds with a parameter record of their own, BgkBoxParams, and the same discipline:
+ *   KIND 3  RepulsiveParticles   eps sum (rm2 / d2)^6 over the pairs i < j except (0, 1); no epsilon: coincident particles give +inf
+ *   KIND 4  HarmonicParticles    spring sum (sqrt(d2) - rc)^2 over those pairs with d2 < rc^2
+ *   + dimer  dimer_k (x0 + x1)^2 + dimer_k y0^2 + dimer_k y1^2 + slope t - a t^2 + b t^4,  t = 2 (|r0 - r1| - dmid)
+ *   + box    2 box_k delta^2 for every coordinate c and both delta = -(c + half) and delta = c - half, where delta > 0
+ *            (the reference's (sign(delta) + 1) box_k delta^2: the factor is 2, and 0 where delta < 0; delta = 0 adds 0 either way)
+ * bgk_box_row_energy / bgk_box_row_gradient; no Hessian-vector form. */
 #ifndef BGK_PAIR_TERMS_H
 #define BGK_PAIR_TERMS_H
 
@@ -170,6 +178,113 @@ __device__ __forceinline__ void bgk_pair_row_hvp(const float* xr, const float* u
                 if (WITH_G) gw[i * D + k] += osc * (xr[i * D + k] - mean[k]);
                 hw[i * D + k] += osc * (ur[i * D + k] - umean[k]);
             }
+    }
+}
+
+/* the parameters of KIND 3 / 4, by value inside the kernels' argument records (wave-uniform) */
+struct BgkBoxParams {
+    float eps, rm2, spring, rc, rc2;
+    float dimer_k, dimer_slope, dimer_a, dimer_b, dimer_dmid;
+    float box_half, box_k;
+};
+
+/* the host array of the bgk_box_* entries (include/bgflow_amd.h): [eps, rm^2, rc, rc^2, spring_constant, dimer_slope, dimer_a, dimer_b,
+ * dimer_dmid, dimer_k, box_halfsize, box_k]; the caller forms the squares in double, so that they are rounded once */
+constexpr int BGK_BOX_N_PARAMS = 12;
+inline void bgk_box_params_from_host(const float* h, BgkBoxParams* p) {
+    p->eps = h[0]; p->rm2 = h[1]; p->rc = h[2]; p->rc2 = h[3]; p->spring = h[4];
+    p->dimer_slope = h[5]; p->dimer_a = h[6]; p->dimer_b = h[7]; p->dimer_dmid = h[8]; p->dimer_k = h[9];
+    p->box_half = h[10]; p->box_k = h[11];
+}
+
+/* e(x) of the row [2 n] at temperature 1, before the rounding to f32: the pair terms of one i in f32, the row sums, the dimer's terms and
+ * the box terms of one particle in f64 */
+template <int KIND>
+__device__ __forceinline__ double bgk_box_row_energy(const float* xr, int n, const BgkBoxParams& p) {
+    double e = 0.0;
+    for (int i = 0; i + 1 < n; ++i) {
+        const float xi = xr[2 * i], yi = xr[2 * i + 1];
+        float row = 0.0f;
+        for (int j = i == 0 ? 2 : i + 1; j < n; ++j) {      /* (0, 1) is the dimer: no pair term */
+            const float dx = xi - xr[2 * j], dy = yi - xr[2 * j + 1];
+            const float d2 = dx * dx + dy * dy;
+            if (KIND == 3) {
+                const float s = p.rm2 / d2, s3 = s * s * s;
+                row += s3 * s3;
+            } else {
+                const float t = __builtin_sqrtf(d2) - p.rc;
+                row += d2 < p.rc2 ? t * t : 0.0f;
+            }
+        }
+        e += (double)row;
+    }
+    e *= (double)(KIND == 3 ? p.eps : p.spring);
+    {
+        const float x0 = xr[0], y0 = xr[1], x1 = xr[2], y1 = xr[3];
+        const float sx = x0 + x1, dx = x0 - x1, dy = y0 - y1;
+        const float t = 2.0f * (__builtin_sqrtf(dx * dx + dy * dy) - p.dimer_dmid), t2 = t * t;
+        e += (double)(p.dimer_k * (sx * sx));
+        e += (double)(p.dimer_k * (y0 * y0));
+        e += (double)(p.dimer_k * (y1 * y1));
+        e += (double)(p.dimer_slope * t);
+        e -= (double)(p.dimer_a * t2);
+        e += (double)(p.dimer_b * (t2 * t2));
+    }
+    const float k2 = 2.0f * p.box_k;
+    for (int i = 0; i < n; ++i) {
+        float w = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const float c = xr[2 * i + k], lo = -(c + p.box_half), hi = c - p.box_half;
+            w += lo > 0.0f ? k2 * (lo * lo) : 0.0f;
+            w += hi > 0.0f ? k2 * (hi * hi) : 0.0f;
+        }
+        e += (double)w;
+    }
+    return e;
+}
+
+/* d e / d x of that row in bgk_pair_row_gradient's pattern: gw [2 n] is the lane's OWN row of an LDS tile (zeroed here), all in f32.
+ * The harmonic pair gradient at d_ij = 0 is 0 (the double-well kind's convention); the repulsive one at d_ij = 0 and the dimer's at
+ * |r0 - r1| = 0 are what the f32 arithmetic gives (non-finite). */
+template <int KIND>
+__device__ __forceinline__ void bgk_box_row_gradient(const float* xr, float* gw, int n, const BgkBoxParams& p) {
+    for (int c = 0; c < 2 * n; ++c) gw[c] = 0.0f;
+    const float c12 = -12.0f * p.eps / p.rm2, k2s = 2.0f * p.spring;
+    for (int i = 0; i + 1 < n; ++i) {
+        const float xi = xr[2 * i], yi = xr[2 * i + 1];
+        float gx = 0.0f, gy = 0.0f;
+        for (int j = i == 0 ? 2 : i + 1; j < n; ++j) {
+            const float dx = xi - xr[2 * j], dy = yi - xr[2 * j + 1];
+            const float d2 = dx * dx + dy * dy;
+            float cf;                           /* d e_ij / d x_i = cf (x_i - x_j) */
+            if (KIND == 3) {
+                const float s = p.rm2 / d2, s3 = s * s * s;
+                cf = c12 * ((s3 * s3) * s);     /* -12 eps rm2^6 / d2^7 */
+            } else {
+                const float dist = __builtin_sqrtf(d2);
+                cf = (d2 < p.rc2 && dist > 0.0f) ? k2s * (dist - p.rc) / dist : 0.0f;
+            }
+            const float vx = cf * dx, vy = cf * dy;
+            gx += vx; gy += vy;
+            gw[2 * j] -= vx; gw[2 * j + 1] -= vy;
+        }
+        gw[2 * i] += gx; gw[2 * i + 1] += gy;
+    }
+    {
+        const float x0 = xr[0], y0 = xr[1], x1 = xr[2], y1 = xr[3];
+        const float sx = x0 + x1, dx = x0 - x1, dy = y0 - y1;
+        const float r = __builtin_sqrtf(dx * dx + dy * dy), t = 2.0f * (r - p.dimer_dmid);
+        /* d / d r of slope t - a t^2 + b t^4 with d t / d r = 2 */
+        const float f = 2.0f * (p.dimer_slope - 2.0f * p.dimer_a * t + 4.0f * p.dimer_b * (t * t * t)) / r;
+        const float kc = 2.0f * p.dimer_k;
+        gw[0] += kc * sx + f * dx; gw[1] += kc * y0 + f * dy;
+        gw[2] += kc * sx - f * dx; gw[3] += kc * y1 - f * dy;
+    }
+    const float k4 = 4.0f * p.box_k;
+    for (int c = 0; c < 2 * n; ++c) {
+        const float v = xr[c], lo = -(v + p.box_half), hi = v - p.box_half;
+        gw[c] += (hi > 0.0f ? k4 * hi : 0.0f) - (lo > 0.0f ? k4 * lo : 0.0f);
     }
 }
 

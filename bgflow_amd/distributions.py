@@ -294,6 +294,14 @@ class _CutKLSumsFn(torch.autograd.Function):
 PairPlan = collections.namedtuple("PairPlan", "kind n_particles n_dims p0 p1 p2 p3 osc_scale temperature")
 
 
+class BoxPlan(collections.namedtuple("BoxPlan", "kind n_particles params temperature")):
+    """the plan of a particle box (particles.RepulsiveParticles / HarmonicParticles; the bgk_box_* entries): kind 3 / 4, ``params`` the
+    twelve floats of the entries' parameter array.  A type of its own and NOT a PairPlan: the Langevin and Hessian-vector kernels, which
+    take a PairPlan as their licence, do not know these kinds.  Four entries: the callers that fold field plans pass it by as well."""
+    __slots__ = ()
+    n_dims = 2
+
+
 def _own_methods(obj, cls):
     """``obj`` evaluates its energy with the code of ``cls`` (no subclass override of ``energy`` / ``_energy``)"""
     return all(getattr(type(obj), name, None) is getattr(cls, name) for name in ("energy", "_energy"))
@@ -341,7 +349,7 @@ def _kernel_plan(dist, temperature):
     describe = getattr(dist, "_kernel_fields", None)
     if describe is None:
         pair = getattr(dist, "_pair_kernel", None)
-        if pair is not None:             # a particle system over one tensor (particles.py): a plan kind of its own, a PairPlan
+        if pair is not None:             # a particle system over one tensor (particles.py): a plan kind of its own, a PairPlan or a BoxPlan
             owner = next(c for c in type(dist).__mro__ if "_pair_kernel" in c.__dict__)
             if any(getattr(type(dist), name, None) is not getattr(owner, name, None) for name in ("energy", "_energy")):
                 return None
@@ -364,7 +372,7 @@ def kernel_energy(dist, xs, temperature=1.0):
     plan = _kernel_plan(dist, temperature)
     if plan is None:
         return None
-    if isinstance(plan, PairPlan):
+    if isinstance(plan, (PairPlan, BoxPlan)):
         from . import particles
         return particles.pair_energy(plan, xs)
     specs, dims, c_in, c_out, t_eff, *wrap = plan
@@ -382,7 +390,7 @@ def kl_loss_sums(target, xs, dlogp, temperature=1.0, drop_nonfinite=False):
     plan = _kernel_plan(target, temperature)
     if plan is None:
         return None
-    if isinstance(plan, PairPlan):       # a particle system over one tensor: the same pair from bgk_pair_energy_kl_sums
+    if isinstance(plan, (PairPlan, BoxPlan)):    # a particle system over one tensor: the same pair from bgk_pair_energy_kl_sums / bgk_box_energy_kl_sums
         from . import particles
         return particles.pair_kl_loss_sums(plan, xs, dlogp, drop_nonfinite)
     specs, dims, c_in, c_out, t_eff, *wrap = plan

@@ -4,8 +4,8 @@ _iterative_helpers.py) and Metropolis Monte Carlo -- ``GaussianProposal``, ``Lat
 
 The general path is the reference's step in torch ops over ``energy.energy(...)``: any ``Energy``, any proposal, any device and dtype.
 
-The fused path (csrc/bgk_mcmc.hip, entry bgk_pair_mcmc) runs whole chains in one launch: a particle-system target with a ``PairPlan``
-(2..64 particles in 1..3 dimensions), a plain ``GaussianProposal`` with a numeric ``noise_std``, one contiguous f32 HIP samples tensor
+The fused path (csrc/bgk_mcmc.hip, entries bgk_pair_mcmc / bgk_box_mcmc) runs whole chains in one launch: a particle-system target with a
+``PairPlan`` (2..64 particles in 1..3 dimensions) or a ``BoxPlan`` (the particle box: 2..64 particles in 2 dimensions), a plain ``GaussianProposal`` with a numeric ``noise_std``, one contiguous f32 HIP samples tensor
 [B, n d] or [B, n, d], no box vectors, the default samples hook, and a positive number or a tensor of B positive values as
 ``target_temperatures``.  ``MCMCStep.forward`` is then one launch for its ``n_steps``; an ``IterativeSampler`` whose only step is such a
 step (and whose ``extract_sample_hook`` is the default) runs ``stride * n_steps`` steps per iteration inside the launch and has the kernel
@@ -19,7 +19,7 @@ from typing import Sequence
 
 import torch
 
-from .distributions import PairPlan, Sampler, _FusedSampling, _kernel_plan
+from .distributions import BoxPlan, PairPlan, Sampler, _FusedSampling, _kernel_plan
 from .utils import pack_tensor_in_list, pack_tensor_in_tuple, unpack_tensor_tuple
 
 __all__ = ["AbstractSamplerState", "SamplerState", "SamplerStep", "IterativeSampler", "GaussianProposal", "LatentProposal", "MCMCStep",
@@ -143,8 +143,8 @@ class SamplerState(AbstractSamplerState):
 # ---- the kernel launch ------------------------------------------------------------------------------------------------------------
 def pair_mcmc(plan, x, e, e_valid, temperature, noise_std, n_steps, noise=None, uniforms=None, seed=0, offset=0, row0=0,
               traj=None, traj_e=None, traj_every=0, n_accepted=None, accumulate=False):
-    """One launch of bgk_pair_mcmc: ``n_steps`` Metropolis steps of the chains x [B, n d] (f32, contiguous, HIP; updated IN PLACE) on
-    the target of the ``PairPlan``.  e [B]: raw energies (temperature 1), read if ``e_valid``, written for the final state.
+    """One launch of bgk_pair_mcmc (bgk_box_mcmc for a ``BoxPlan``): ``n_steps`` Metropolis steps of the chains x [B, n d] (f32,
+    contiguous, HIP; updated IN PLACE) on the target of the plan.  e [B]: raw energies (temperature 1), read if ``e_valid``, written for the final state.
     ``temperature``: a positive number or an f32 tensor [B].  noise [n_steps, B, n d] and uniforms [n_steps, B], or neither (Philox
     numbers of (seed, offset + step, chain row0 + b)).  traj [n_steps // traj_every, B, n d] / traj_e [n_steps // traj_every, B]: the
     state / energy after every ``traj_every``-th step.  n_accepted [B] (int32): written, or added to with ``accumulate``."""
@@ -166,13 +166,18 @@ def pair_mcmc(plan, x, e, e_valid, temperature, noise_std, n_steps, noise=None, 
             raise ValueError(f"pair_mcmc: expected a contiguous {want} HIP tensor of shape {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
     if traj is not None and traj_every < 1:
         raise ValueError("pair_mcmc: traj_every must be at least 1")
+    if isinstance(plan, BoxPlan):
+        from .particles import _box_params
+        name, target = "bgk_box_mcmc", (plan.n_particles, plan.kind, _box_params(plan), len(plan.params))
+    else:
+        name, target = "bgk_pair_mcmc", (plan.n_particles, plan.n_dims, plan.kind, plan.p0, plan.p1, plan.p2, plan.p3, plan.osc_scale)
     with torch.cuda.device(x.device):
-        st = _lib.lib().bgk_pair_mcmc(_lib.ptr(x), B, plan.n_particles, plan.n_dims, plan.kind, plan.p0, plan.p1, plan.p2, plan.p3,
-                                      plan.osc_scale, _lib.ptr(e), int(bool(e_valid)), 1.0 if temps is not None else float(temperature),
-                                      _lib.ptr(temps), float(noise_std), int(n_steps), _lib.ptr(noise), _lib.ptr(uniforms),
-                                      int(seed) & (2 ** 64 - 1), int(offset) & 0xffffffff, int(row0), _lib.ptr(traj), _lib.ptr(traj_e),
-                                      int(traj_every), _lib.ptr(n_accepted), int(bool(accumulate)), _lib.stream_ptr(x.device))
-    _lib.check(st, "bgk_pair_mcmc")
+        st = getattr(_lib.lib(), name)(_lib.ptr(x), B, *target, _lib.ptr(e), int(bool(e_valid)),
+                                       1.0 if temps is not None else float(temperature),
+                                       _lib.ptr(temps), float(noise_std), int(n_steps), _lib.ptr(noise), _lib.ptr(uniforms),
+                                       int(seed) & (2 ** 64 - 1), int(offset) & 0xffffffff, int(row0), _lib.ptr(traj), _lib.ptr(traj_e),
+                                       int(traj_every), _lib.ptr(n_accepted), int(bool(accumulate)), _lib.stream_ptr(x.device))
+    _lib.check(st, name)
 
 
 def _launch_plan(unit, count, cap):
@@ -340,7 +345,7 @@ class MCMCStep(SamplerStep, _FusedSampling):
         if getattr(data, "box_vectors", None) is not None or len(samples) != 1 or not torch.is_tensor(samples[0]):
             return None
         plan = _kernel_plan(self.target_energy, 1.0)
-        if not isinstance(plan, PairPlan):
+        if not isinstance(plan, (PairPlan, BoxPlan)):
             return None
         x, nd = samples[0], plan.n_particles * plan.n_dims
         if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() in (2, 3) and x.shape[0] > 0):

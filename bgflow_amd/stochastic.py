@@ -37,7 +37,7 @@ import warnings
 
 import torch
 
-from .distributions import Energy, PairPlan, _FusedSampling, _kernel_plan
+from .distributions import BoxPlan, Energy, PairPlan, _FusedSampling, _kernel_plan
 from .flow import Flow
 
 __all__ = ["BrownianFlow", "OverdampedLangevinFlow", "LangevinFlow", "MetropolisMCFlow"]
@@ -74,7 +74,7 @@ def _force(energy_model, x):
     """-dE/dx.  An input that carries a graph: through autograd with ``create_graph`` (a particle target of this package over its torch
     formulas); otherwise ``energy_model.force`` on a detached alias, so that the caller's tensor keeps its ``requires_grad``."""
     if torch.is_grad_enabled() and x.requires_grad:
-        if isinstance(_kernel_plan(energy_model, 1.0), PairPlan):
+        if isinstance(_kernel_plan(energy_model, 1.0), (PairPlan, BoxPlan)):
             e = Energy.energy(energy_model, x)
         else:
             e = energy_model.energy(x)

@@ -766,6 +766,38 @@ int bgk_pair_mcmc(float* x, int64_t B, int32_t n_particles, int32_t n_dims, int3
                   uint64_t seed, uint32_t offset, int64_t row0,
                   float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream);
 
+/* The particle box -- a bistable dimer (particles 0 and 1) in a bath of solvent particles in a 2-d box -- over ONE tensor
+ * x [B, 2 n_particles] (rows [x0, y0, x1, y1, ...]) on the kernels of bgk_pair_energy and bgk_pair_mcmc (csrc/bgk_pair.hip, bgk_mcmc.hip,
+ * bgk_pair_terms.h), replacing the [B, n, n] op chains of bgflow/distribution/energy/particles.py:
+ *   kind 3  RepulsiveParticles._energy (particles.py:272-277) = LJ_energy_torch (99-123) + dimer_energy_torch (191-210) +
+ *           box_energy_torch (235-254):  eps sum (rm^2 / d2_ij)^6 over the pairs i < j except the dimer's (0, 1) -- the reference's
+ *           0.5 sum over both orders under its mask_matrix; no epsilon: coincident particles give +inf, as there
+ *   kind 4  HarmonicParticles._energy (particles.py:376-381) = harmonic_energy_torch (354-374) + the same dimer and box terms:
+ *           spring_constant sum (d_ij - rc)^2 over those pairs with d2_ij < rc^2
+ *   dimer   dimer_k (x0 + x1)^2 + dimer_k y0^2 + dimer_k y1^2 + dimer_slope t - dimer_a t^2 + dimer_b t^4,  t = 2 (|r0 - r1| - dimer_dmid)
+ *   box     (sign(delta) + 1) box_k delta^2 for every coordinate c and both delta = -(c + box_halfsize) and delta = c - box_halfsize
+ * params: n_params = 12 HOST floats [eps, rm^2, rc, rc^2, spring_constant, dimer_slope, dimer_a, dimer_b, dimer_dmid, dimer_k,
+ *   box_halfsize, box_k], read during the call (the caller forms the two squares in double: rounded once).  Other kinds and other
+ *   lengths: -1.  The kinds of bgk_pair_energy are not served here, nor these there.
+ * Everything else -- u = e / temperature, the loss sums, g_u / the loss-sum form of the backward, the chains' random numbers, traj,
+ * n_accepted, row0, the return codes, B == 0 -- is as in the bgk_pair_* entry of the same name.  bgk_box_energy_backward is what autograd
+ * gives for either _energy and, negated with g_u = 1, RepulsiveParticles.force (particles.py:161-189, 212-233, 256-270, 324-327).  The
+ * harmonic pair gradient at d_ij = 0 is 0; the repulsive one there, and the dimer's at |r0 - r1| = 0, are not finite (as in the reference).
+ * Envelope: 2 <= n_particles <= 64; BGK_EUNSUPPORTED beyond. */
+int bgk_box_energy(const float* x, int64_t ldx, int64_t B, int32_t n_particles, int32_t kind, const float* params, int32_t n_params,
+                   double temperature, float* u, void* stream);
+int bgk_box_energy_kl_sums(const float* x, int64_t ldx, int64_t B, int32_t n_particles, int32_t kind, const float* params,
+                           int32_t n_params, double temperature, float* u, const float* dlogp, int32_t drop_nonfinite,
+                           float* partial, int32_t nblk, double* loss_sums, void* stream);
+int bgk_box_energy_backward(const float* x, int64_t ldx, int64_t B, int32_t n_particles, int32_t kind, const float* params,
+                            int32_t n_params, double temperature, const float* g_u, const float* g_scalar, const float* u,
+                            const float* dlogp, int32_t drop_nonfinite, float* g_dlogp, float* g_x, int64_t ldg, void* stream);
+int bgk_box_mcmc(float* x, int64_t B, int32_t n_particles, int32_t kind, const float* params, int32_t n_params,
+                 float* e, int32_t e_valid, double temperature, const float* temperatures,
+                 double noise_std, int32_t n_steps, const float* noise, const float* uniforms,
+                 uint64_t seed, uint32_t offset, int64_t row0,
+                 float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream);
+
 /* Brownian and Langevin dynamics with the path-probability ratio on the targets of bgk_pair_energy, a whole run of steps in one launch
  * (csrc/bgk_langevin.hip), replacing the per-step op chain of BrownianFlow._forward and LangevinFlow._forward (nn/flow/stochastic/
  * langevin.py:32-45, 86-118) with f = -d e / d x at temperature 1, h = stepsize.  v == NULL, Brownian:
