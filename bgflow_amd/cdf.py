@@ -60,6 +60,7 @@ def _reverted_cdf_series(alpha):
 
 
 TAIL_DESC = 20     # floats per channel of the sampling-tail kernel's descriptor (csrc/bgk_tail.hip)
+TAIL_K_MAX = float(np.finfo(np.float32).max)     # largest k = Z / pdf(bound) with a series window; beyond it the bound counts as absent
 
 
 def _tail_descriptor(dist, d):
@@ -75,6 +76,9 @@ def _tail_descriptor(dist, d):
     out = np.zeros((d, TAIL_DESC), np.float64)
     kinds = np.zeros(d, np.int32)
     half_log_2pi = 0.9189385332046727
+    cups = getattr(dist, "_cdf_upper_bound", None)        # per column, read once
+    if cups is not None:
+        cups = np.broadcast_to(torch.as_tensor(cups).detach().cpu().double().reshape(-1).numpy(), (d,))
     for j in range(d):
         kind = int(b[j, 0])
         kinds[j] = kind
@@ -87,14 +91,20 @@ def _tail_descriptor(dist, d):
         out[j, 1], out[j, 2], out[j, 3], out[j, 4] = mu, sigma * np.sqrt(2.0), 2.0 * Z, 2.0 * clo - 1.0
         out[j, 5] = np.log(Z * sigma) + half_log_2pi
         out[j, 6], out[j, 13] = 1.0 / (sigma * np.sqrt(2.0)), sigma
-        out[j, 7] = out[j, 14] = 1e30                                     # no bound: the series window is never entered
+        # no bound, or a bound so far out that k = Z / pdf(bound) is no f32: k = inf, the one sentinel.  The kernel's window test
+        # s = v k < SMAX is then false for every v >= 0 (0 * inf = NaN compares false), so the window is never entered.
+        out[j, 7] = out[j, 14] = np.inf
         if kind == 2:
+            # an infinite upper bound has the cdf value 1, but clo + Z with the f32 Z = fl(1 - clo) may fall short of it: ask the module
+            cup = None if cups is None else float(cups[j])
             for lower, off in ((True, 7), (False, 14)):
                 c = clo if lower else clo + Z
-                if not (1e-300 < c < 1.0 - 1e-16):
+                if not (1e-300 < c < 1.0 - 1e-16) or (not lower and cup is not None and cup >= 1.0):
                     continue
                 x0 = sps.ndtri(c)
                 pdf = np.exp(-0.5 * x0 * x0) / np.sqrt(2.0 * np.pi)
+                if not Z / pdf <= TAIL_K_MAX:
+                    continue
                 out[j, off] = Z / pdf
                 out[j, off + 1:off + 5] = _reverted_cdf_series(x0 if lower else -x0)
                 out[j, 12 if lower else 19] = mu + sigma * x0

@@ -1,7 +1,10 @@
-/* bgk_capi.hip -- library-level entry points (version, error string, deterministic-math probe). */
+/* bgk_capi.hip -- library-level entry points (version, error string, math probe).
+ * bgk_detmath_probe(which): 0 exp, 1 log, 2 softplus, 3 silu, 4 tanh (the deterministic forms of bgk_detmath.h), 5 erf_fast,
+ * 6 erfinv_fast (bgk_erf.h; on the hardware log2 / exp2, so not bit-equal to a host evaluation); any other code copies the input. */
 #include <stdarg.h>
 
 #include "bgk_common.h"
+#include "bgk_erf.h"
 #include "bgk_fused2.h"
 
 extern int bgk_affine_variant;      /* bgk_fused_affine.hip */
@@ -49,6 +52,8 @@ __global__ void detmath_probe_kernel(const float* x, int64_t n, int which, float
         case 2: r = bgk_softplusf(v, 0.69384102162f); break;
         case 3: r = bgk_siluf(v); break;
         case 4: r = bgk_tanhf(v); break;
+        case 5: r = erf_fast(v); break;
+        case 6: r = erfinv_fast(v); break;      /* elements 64 k .. 64 k + 63 share a wave (and its tail-branch ballot) */
         default: r = v;
     }
     out[i] = r;

@@ -2,7 +2,7 @@
  * marginals the builder installs (factory/icmarginals.py:41-77): TruncatedNormalDistribution
  * (distribution/normal.py:215-227), torch.distributions.Normal and (Sloppy)Uniform.
  * One launch replaces ~10 elementwise aten kernels + a row reduction: 4*(2d + 2) algorithmic bytes
- * per sample, HBM-bound.  erf / erfinv: the polynomial forms of bgk_erf.h (Juffa / Giles, < 1 / < 4 ulp; the OCML functions
+ * per sample, HBM-bound.  erf / erfinv: the polynomial forms of bgk_erf.h (Juffa / Giles, 1.5 / 3.0 ulp: tests/test_gpu_domain_maps.py; the OCML functions
  * made this a VALU-bound kernel: 0.30 ms for the 66-wide slot of cfg 5 at 2^20 samples); the per-column logarithms and
  * reciprocals are formed once per workgroup in LDS; row index by multiply-high instead of an integer division.
  *

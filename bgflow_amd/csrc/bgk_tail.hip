@@ -41,7 +41,8 @@ constexpr float SMAX = 0.03f;          /* reverted-series window: s = (distance 
  *   uniform:  [1] low  [2] high - low  [5] log(high - low)
  *   normal / truncated normal:  y = mu + sigma sqrt2 e,  e = erfinv(xs v + xo),  -log_prob = e^2 + cst
  *     [1] mu  [2] sigma sqrt2  [3] xs  [4] xo  [5] cst  [6] 1 / (sigma sqrt2)  [13] sigma
- *     lower bound: [7] k = Z / pdf(alpha) (1e30: none)  [8..11] c2..c5  [12] y0 = mu + sigma alpha
+ *     lower bound: [7] k = Z / pdf(alpha) (inf: no bound, or one too far out for an f32 k; v k < SMAX is then false for every
+ *                  v >= 0, v = 0 included: 0 * inf = NaN)  [8..11] c2..c5  [12] y0 = mu + sigma alpha
  *     upper bound: [14] k  [15..18] c2..c5  [19] y0 = mu + sigma beta */
 
 /* wave-uniform tables (channel descriptors, placement rows, whitening matrices) are read through the CONSTANT address space: loads
@@ -580,7 +581,7 @@ __global__ __launch_bounds__(TW * 64) void icdf_ic2xyz_uni_kernel(TailArgs a) {
  * Arithmetic: the angle is atan2(|r12 x r32|, r12 . r32) instead of acos of the normalised dot product (same value, but accurate
  * for small and near-straight angles, where acos amplifies the rounding of the cosine by 1 / sin a); log|det J| of a row in closed
  * form -(2 ln d + ln sin a) (what the explicit 3 x 3 determinant of the reference evaluates to away from its eps clamps; rows
- * that hit a clamp are recomputed with the reference's explicit arithmetic); erf (N. Juffa's single-precision form, < 1 ulp) and
+ * that hit a clamp are recomputed with the reference's explicit arithmetic); erf (N. Juffa's single-precision form, 1.5 ulp) and
  * atan (Cephes) as branch-free polynomials.  Field-uniform marginals only (desc4); otherwise the block path runs. */
 
 /* atan2(y, x) in (-pi, pi]: atan of min / max on [0, 1] (Cephes atanf: reduction at tan(pi / 8), odd polynomial), octant fix-ups */

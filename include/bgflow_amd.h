@@ -54,7 +54,9 @@ const char* bgk_last_error(void);            /* thread-local, host string */
 int bgk_set_option(int32_t option, int32_t value);
 
 /* Deterministic-math probe: out[i] = f(x[i]) on the device with the same primitives the spline
- * kernels use (which: 0 exp, 1 log, 2 softplus(beta=ln2/(1-1e-3)), 3 silu, 4 tanh).  Test hook. */
+ * kernels use (which: 0 exp, 1 log, 2 softplus(beta=ln2/(1-1e-3)), 3 silu, 4 tanh), or with the erf / erfinv
+ * of the domain maps (5 erf_fast, 6 erfinv_fast; 256-thread blocks: elements 64 k .. 64 k + 63 share a wave).
+ * Test hook. */
 int bgk_detmath_probe(const float* x, int64_t n, int32_t which, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
