@@ -60,6 +60,7 @@ _MAP = {
     "factory.icmarginals": "factory",
     "utils.types": "utils",
     "utils.train": "clipped",
+    "utils.free_energy": "free_energy",
 }
 
 

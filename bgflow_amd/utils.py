@@ -5,6 +5,8 @@ from collections.abc import Iterable
 import numpy as np
 import torch
 
+from .free_energy import bennett_acceptance_ratio       # noqa: F401  (the reference's utils/__init__ re-exports it)
+
 __all__ = ["hash_init_", "synth", "param_state_key", "is_list_or_tuple", "pack_tensor_in_tuple", "unpack_tensor_tuple", "pack_tensor_in_list",
            "as_numpy", "assert_numpy"]
 

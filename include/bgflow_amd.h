@@ -1018,6 +1018,32 @@ int bgk_column_moments_update(const float* x, int64_t ldx, int64_t B, int32_t P,
                               double* state, void* stream);
 int bgk_column_moments_finalize(const double* state, int32_t P, int64_t n_rows, double* out, void* stream);
 
+/* Bennett acceptance ratio: replaces `_bar` / `_bar_zero` / `_one_sided_reweighting` of `utils/free_energy.py:104-197` (~30 torch ops
+ * per evaluation of the BAR function and two host reads per iteration of the root finder).  One call enqueues n_steps STEPS on the
+ * stream; a step is one reduction over both work arrays (block partials, then one workgroup that merges them) and one move of the
+ * solver's state machine, which lives in `record` on the device: bounds from one-sided exponential averaging (:125-138), f at
+ * both bounds, the bracket expansion of :142-147 (at most maximum_iterations times, then status 2), false position as :151-161 until
+ * |D - D_old| <= relative_tolerance |D|, D == D_old, f(D) == 0 (status 0) or maximum_iterations iterations (status 1: the last iterate
+ * is the result, as in the reference); status 3 when neither sign test of :153-158 fires (f is NaN).  Steps after the record is done
+ * are empty launches, so the caller enqueues a chunk, reads the record back and repeats until record[0] == 4.
+ *   forward_work [n_forward], reverse_work [n_reverse]: contiguous f32 (dtype BGK_BAR_F32) or f64 (BGK_BAR_F64) work values, aligned to
+ *     their element size only (16-byte loads where the address allows, scalar head and tail); all arithmetic is f64.
+ *   nblk_forward, nblk_reverse: stage-1 blocks per array, 1 .. 512; partial: workspace of 3 * (nblk_forward + nblk_reverse) doubles.
+ *   record: BGK_BAR_RECORD_DOUBLES doubles, ZERO-FILLED by the caller before the first call of a solve, the same buffer on every later
+ *     call: {phase (0 bounds, 1 f(upper), 2 f(lower), 3 iterate, 4 done), status, upper, lower, f(upper), f(lower), D the next step
+ *     evaluates, D_old, evaluations of f, expansions, iterations, log sum fermi_F, log sum fermi_F^2, log sum fermi_R, log sum fermi_R^2
+ *     of the last evaluation, f of the last evaluation, result D (NaN for status 2 and 3), uncertainty}.  The uncertainty is :170-195
+ *     in log space, sqrt(exp(L2F - 2 L1F) + exp(L2R - 2 L1R) - (nF + nR) / (nF nR)), from the last evaluation (which is at the result).
+ * Deterministic: fixed partition, fixed merge orders, no atomics, no waiting between blocks; NaN / infinity as torch.logsumexp.
+ * Argument checks come before any launch (BGK_EINVAL: null pointer, a size < 1, another dtype code, a misaligned pointer, block counts
+ * out of range, maximum_iterations < 1, n_steps < 0); n_steps == 0 returns 0 without a launch. */
+#define BGK_BAR_F32 0
+#define BGK_BAR_F64 1
+#define BGK_BAR_RECORD_DOUBLES 18
+int bgk_bar_solve_steps(const void* forward_work, int64_t n_forward, const void* reverse_work, int64_t n_reverse, int32_t dtype,
+                        int32_t nblk_forward, int32_t nblk_reverse, double* partial, double* record, int32_t maximum_iterations,
+                        double relative_tolerance, int32_t n_steps, void* stream);
+
 /* One Linear layer (+ bias + activation) of a conditioner network on its own: y = act(x W^T + b).
  * Replaces one `Linear (, activation)` pair of DenseNet._layers (nn/dense.py:30-48) for the networks the one-launch coupling kernels do
  * not take (conditioner_factory.py:76-80 allows any `hidden` tuple: other depths, layers wider than 256; README.md:72-79's [1, 4, 1]
