@@ -11,6 +11,9 @@ matrix cores + transformer epilogue:
           (``bgk_coupling_rqs_dense_deep``, inference); exact-f32 GEMMs for two hidden layers of 128 (``bgk_coupling_rqs_dense``);
   affine  (``fused_affine_coupling``): two / three hidden layers of <= 128 units (``bgk_coupling_affine_dense_h2`` / ``_h3``), any other
           depth from 1 to 8 (``bgk_coupling_affine_dense_deep``).
+This module decides which kernel a conditioner runs on (``_fusable_dense``, the ``*_plan`` functions), caches the packed operands per
+parameter state, launches, and holds the module switches; the operand layouts themselves (the f32 and split-f16 packers, the padded
+stand-in layers, the row tables) are packing.py's.
 state_dict keys match the reference (``_layers.{i}.weight/bias``, ``net._layers...``).
 """
 import ctypes
@@ -21,6 +24,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from .packing import (DEEP_MAX_HIDDEN, T_OPERAND_MAX_IN, _pad_hidden, _src_col_table, _t_operand_bufs, pack_dense_for_affine_deep,
+                      pack_dense_for_affine_h2, pack_dense_for_fused, pack_dense_for_fused_deep, pack_dense_for_fused_h2,
+                      pack_dense_for_fused_h2_device, pack_dense_for_fused_w256)
+from .packing import pack_linear_layer, pack_linear_layer_device, rqs_row_perm  # noqa: F401  (not called here: tests reach them as dense.<name>)
 from .utils import is_list_or_tuple, param_pitch, param_state_key, row_pitch
 
 __all__ = ["DenseNet", "MeanFreeDenseNet", "WrapPeriodic", "WrapDistances"]
@@ -156,47 +163,6 @@ class _ActFn(torch.autograd.Function):
 LAYER_KERNEL = True     # Linear layers of a DenseNet on HIP tensors run on bgk_dense_layer; False: torch.nn.Linear (hipBLASLt)
 
 _LAYER_ACTS = {torch.nn.SiLU: 1, torch.nn.ReLU: 2, torch.nn.Tanh: 3}
-
-
-def pack_linear_layer(weight):
-    """Operands of bgk_dense_layer for ``weight`` [n_out, n_in]: a list of passes (A f16 [G * S * 8, 64, 8], S, c, k0, k1), one per
-    block of <= 256 input columns [k0, k1): the block scaled by a power of two (largest magnitude into [2^14, 2^15)), zero-padded to
-    16 S columns and 128 G rows, per 128-row group in the split-f16 block layout of the coupling kernels (natural k order)."""
-    W = weight.detach().float()
-    n_out, n_in = W.shape
-    G = (n_out + 127) // 128
-    passes = []
-    for k0 in range(0, n_in, 256):
-        k1 = min(n_in, k0 + 256)
-        S = int(_lib.lib().bgk_dense_layer_steps(k1 - k0))
-        Wb = W[:, k0:k1]
-        e = _h2_scale_exp(Wb)
-        Wp = torch.zeros(128 * G, 16 * S, dtype=torch.float32, device=W.device)
-        Wp[:n_out, :k1 - k0] = Wb * 2.0 ** e
-        A = torch.cat([_pack_h2(Wp[g * 128:(g + 1) * 128], None, _h2_k_natural(S)) for g in range(G)], dim=0).contiguous()
-        passes.append((A, S, 2.0 ** -e, k0, k1))
-    return passes
-
-
-def pack_linear_layer_device(weight):
-    """Device-side twin of pack_linear_layer (bgk_pack_linear_layer: no host synchronisation): passes (A, S, cs, k0, k1) with cs the
-    device pair {largest magnitude, unscale factor} of the block"""
-    W = weight.detach()
-    assert W.is_cuda and W.dtype == torch.float32 and W.dim() == 2 and W.stride(1) == 1
-    n_out, n_in = W.shape
-    G = (n_out + 127) // 128
-    passes = []
-    with torch.cuda.device(W.device):
-        for k0 in range(0, n_in, 256):
-            k1 = min(n_in, k0 + 256)
-            S = int(_lib.lib().bgk_dense_layer_steps(k1 - k0))
-            A = torch.empty((G * S * 8, 64, 8), dtype=torch.float16, device=W.device)
-            cs = torch.empty(2, dtype=torch.float32, device=W.device)
-            st = _lib.lib().bgk_pack_linear_layer(W.data_ptr() + 4 * k0, W.stride(0), n_out, k1 - k0, _lib.ptr(A), _lib.ptr(cs),
-                                                  _lib.stream_ptr(W.device))
-            _lib.check(st, "bgk_pack_linear_layer")
-            passes.append((A, S, cs, k0, k1))
-    return passes
 
 
 def _layer_operands(lin, transposed=False):
@@ -379,9 +345,6 @@ class WrapDistances(torch.nn.Module):
         return self.net.forward(torch.cat([x[..., rest], dists], dim=-1))
 
 
-_ACT_CODES = {torch.nn.SiLU: 1, torch.nn.ReLU: 2, torch.nn.Tanh: 3}
-
-
 def _reject(transformer, reason):
     """A coupling whose conditioner LOOKS fusable (a DenseNet, optionally behind WrapPeriodic) leaves the one-launch kernels'
     envelope: say so once per transformer and reason -- the layer-by-layer path (bgk_dense_layer per Linear + the stand-alone transformer
@@ -400,228 +363,54 @@ def _looks_dense(net):
     return type(inner) is DenseNet
 
 
-def _fusable_dense(net):
-    """Return (linears, act_code) if ``net`` is Linear-act-Linear-act-Linear with one supported
-    activation type, else None."""
+def _fusable_dense(net, hidden=(2,)):
+    """Return (linears, act_code) if ``net`` is Linear-(act-Linear) x L with biases and one supported activation type, else None.
+    ``hidden``: the admitted hidden-layer counts L (None: any L >= 1)."""
     if type(net) is not DenseNet:
         return None
     mods = list(net._layers)
-    if len(mods) != 5:
-        return None
-    l0, a0, l1, a1, l2 = mods
-    if not all(isinstance(m, torch.nn.Linear) for m in (l0, l1, l2)):
-        return None
-    if type(a0) is not type(a1) or type(a0) not in _ACT_CODES:
-        return None
-    if any(m.bias is None for m in (l0, l1, l2)):
-        return None
-    return (l0, l1, l2), _ACT_CODES[type(a0)]
-
-
-def _fusable_dense_any(net):
-    """(linears, act_code) for Linear-(act-Linear) x L, L >= 1 hidden layers, biases, one supported activation type; else None"""
-    if type(net) is not DenseNet:
-        return None
-    mods = list(net._layers)
-    if len(mods) < 3 or len(mods) % 2 == 0:
+    if len(mods) < 3 or len(mods) % 2 == 0 or (hidden is not None and len(mods) // 2 not in hidden):
         return None
     lins, acts = mods[0::2], mods[1::2]
     if not all(isinstance(m, torch.nn.Linear) and m.bias is not None for m in lins):
         return None
-    if any(type(a) is not type(acts[0]) for a in acts) or type(acts[0]) not in _ACT_CODES:
+    if any(type(a) is not type(acts[0]) for a in acts) or type(acts[0]) not in _LAYER_ACTS:
         return None
-    return tuple(lins), _ACT_CODES[type(acts[0])]
+    return tuple(lins), _LAYER_ACTS[type(acts[0])]
 
 
-def _fusable_dense_deep(net):
-    """(linears, act_code) for Linear-(act-Linear) x 2 | x 3 with one supported activation type (the affine coupling kernels take
-    two or three hidden layers), else None"""
-    if type(net) is not DenseNet:
+def _periodic_failure(wrap, n_in=None):
+    """Does the WrapPeriodic ``wrap`` around a net of ``n_in`` input features feed it (cos, sin) of ALL n_in / 2 raw inputs, periodic on
+    [0, 1], in natural order -- the one featuriser the fused kernels apply themselves (to columns 0 .. n_in / 2 - 1)?  None if so, else the
+    first condition that fails: "interval", "width" (odd, or no input at all), "indices" (a subset / permutation).  ``n_in`` None (the
+    net is not matched yet): the interval alone is judged."""
+    if not (wrap.left == 0.0 and wrap.right == 1.0):
+        return "interval"
+    if n_in is None:
         return None
-    mods = list(net._layers)
-    if len(mods) not in (5, 7):
+    if n_in < 2 or n_in % 2:
+        return "width"
+    if not np.array_equal(np.asarray(np.arange(n_in // 2)[wrap.indices]), np.arange(n_in // 2)):
+        return "indices"
+    return None
+
+
+def _spline_shape(P, y_dim, nc_slot_host):
+    """(n_bins, circ_mask) of a spline whose conditioner writes P parameter rows for y_dim dims (3 n_bins per dim + one more slope per
+    non-circular dim, nc_slot_host[j] >= 0), or None when P is no such count"""
+    n_nc = int((nc_slot_host >= 0).sum())
+    n_bins = (P - n_nc) // (3 * y_dim)
+    if 3 * n_bins * y_dim + n_nc != P:
         return None
-    lins, acts = mods[0::2], mods[1::2]
-    if not all(isinstance(m, torch.nn.Linear) and m.bias is not None for m in lins):
-        return None
-    if any(type(a) is not type(acts[0]) for a in acts) or type(acts[0]) not in _ACT_CODES:
-        return None
-    return tuple(lins), _ACT_CODES[type(acts[0])]
+    return n_bins, int(sum(1 << j for j in range(y_dim) if nc_slot_host[j] < 0))
 
 
-# ---- MFMA operand packing for bgk_coupling_rqs_dense ------------------------------------------------
-# One k-step of the f32 MFMA (v_mfma_f32_32x32x2_f32, A = weights) over 4 output tiles consumes, per
-# lane l (i = l & 31, h = l >> 5), the four values W[32*m + i][k(step, h)], m = 0..3: stored as one
-# float4 -> a packed layer is [steps + 1][64 lanes][4] floats; the extra last step carries the bias in
-# the lower half-wave (A = bias, B = 1.0) and zeros in the upper one.
-#   layer 0 (input from LDS, natural order):            k(t, h) = 2 t + h
-#   hidden layers (input = accumulator registers):      k(16 kb + r, h) = 32 kb + (r & 3) + 8 (r >> 2) + 4 h
-_LANE_I = torch.arange(64) & 31
-_LANE_H = torch.arange(64) >> 5
-
-
-def _pack_steps(W, bias, k_of_step):
-    """W [128, n_in] (rows = output features), k_of_step [S, 2] (k index for half-wave 0 / 1, -1 = none)"""
-    S = k_of_step.shape[0]
-    dev = W.device
-    rows = (32 * torch.arange(4, device=dev)[None, None, :] + _LANE_I.to(dev)[None, :, None]).expand(S, 64, 4)
-    kk = k_of_step.to(dev)[:, _LANE_H.to(dev)][:, :, None].expand(S, 64, 4)
-    vals = W[rows.reshape(-1), kk.clamp_min(0).reshape(-1)].reshape(S, 64, 4)
-    vals = torch.where(kk >= 0, vals, torch.zeros_like(vals))
-    bstep = torch.zeros(1, 64, 4, dtype=W.dtype, device=dev)
-    bstep[0, :32, :] = bias.reshape(4, 32).t()
-    return torch.cat([vals, bstep], dim=0).contiguous()
-
-
-def _k_natural(n_in):
-    T = ((n_in + 1) // 2 + 3) & ~3          # k-steps padded to a multiple of 4 (zero weights)
-    k = torch.arange(2 * T).reshape(T, 2)
-    return torch.where(k < n_in, k, torch.full_like(k, -1))
-
-
-def _k_hidden():
-    s = torch.arange(64)
-    kb, r = s // 16, s % 16
-    k0 = 32 * kb + (r & 3) + 8 * (r >> 2)
-    return torch.stack([k0, k0 + 4], dim=1)
-
-
-def pack_dense_for_fused(linears, nc_slot_host, d, n_bins):
-    """Pack the three Linear layers of a DenseNet([n_in, 128, 128, P]) for bgk_coupling_rqs_dense.
-    Returns (W0p, W1p, W2p) float32 device tensors."""
-    l0, l1, l2 = linears
-    W0p = _pack_steps(l0.weight.detach().float(), l0.bias.detach().float(), _k_natural(l0.in_features))
-    W1p = _pack_steps(l1.weight.detach().float(), l1.bias.detach().float(), _k_hidden())
-    # last layer: rows (= reference params columns) regrouped per transformed dim by bgk_pack_rqs_columns
-    ncp = _lib.lib().bgk_pack_rqs_columns(d, n_bins, None, None)
-    src = np.empty(ncp, dtype=np.int32)
-    slots = np.ascontiguousarray(nc_slot_host, dtype=np.int32)
-    _lib.lib().bgk_pack_rqs_columns(d, n_bins, slots.ctypes.data, src.ctypes.data)
-    src_t = torch.as_tensor(src.astype(np.int64), device=l2.weight.device)
-    W2 = l2.weight.detach().float()
-    b2 = l2.bias.detach().float()
-    W2r = torch.where(src_t[:, None] >= 0, W2[src_t.clamp_min(0)], torch.zeros((), dtype=W2.dtype, device=W2.device))
-    b2r = torch.where(src_t >= 0, b2[src_t.clamp_min(0)], torch.zeros((), dtype=b2.dtype, device=b2.device))
-    chunks = [_pack_steps(W2r[c * 128:(c + 1) * 128], b2r[c * 128:(c + 1) * 128], _k_hidden()) for c in range(ncp // 128)]
-    return W0p, W1p, torch.cat(chunks, dim=0).contiguous()
-
-
-# ---- split-f16 operand packing for bgk_coupling_rqs_dense_h2 ---------------------------------------
-# v = hi + lo with hi = rne_f16(v), lo = rne_f16(v - hi); weights are first scaled by 2^s (exact) so that
-# max(|W|, |b|) lands in [2^14, 2^15).  One 1 KiB block = 64 lanes x 8 f16; block(s, m, p) = (s*4 + m)*2 + p
-# holds, for lane l = 32 kb + i, W'[32 m + i][k(s, kb, e)], e = 0..7, part p; after the S k16-steps follow 4
-# bias blocks (lanes < 32: {b_hi, b_lo, 0, ...}).  See bgk_fused.hip (coupling_rqs_dense_h2_kernel).
 # module default of the fused kernel's conditioner GEMMs; a transformer's `gemm_mode` attribute overrides it:
 #   "f16x2": split-f16 on the f16 matrix cores (f32-class accuracy, see bgk_fused.hip; ~1.75x the layer throughput)
 #   "f32":   f32-input MFMA = exact k-ordered fma chain, bit-identical to the CPU oracle
 #   "bf16":  single-bf16 weights and GEMM inputs, f32 accumulate (reduced precision: the "bf16" leg of BASELINE config 5;
 #            spline layers only -- affine layers and training run split-f16)
 GEMM_MODE = "f16x2"
-
-
-def _h2_scale_exp(*tensors):
-    m = max(float(t.abs().max()) for t in tensors if t.numel())
-    if not np.isfinite(m) or m <= 0.0:
-        return 0
-    return int(np.clip(np.floor(np.log2(32768.0 / m)), -16, 24))
-
-
-def _h2_split(v):
-    hi = v.to(torch.float16)
-    lo = (v - hi.to(torch.float32)).to(torch.float16)
-    return hi, lo
-
-
-def _h2_k_natural(S):
-    s, kb, e = torch.meshgrid(torch.arange(S), torch.arange(2), torch.arange(8), indexing="ij")
-    return 16 * s + 8 * kb + e
-
-
-def _h2_k_hidden(HT=4):
-    s, kb, e = torch.meshgrid(torch.arange(2 * HT), torch.arange(2), torch.arange(8), indexing="ij")
-    return 32 * (s >> 1) + (e & 3) + 8 * (2 * (s & 1) + (e >> 2)) + 4 * kb
-
-
-def _pack_h2(Ws, bs, kidx, NT=4):
-    """Ws [32 NT, Kdim] scaled f32 weights, bs [32 NT] scaled bias or None, kidx [S, 2, 8] -> f16 tensor of
-    (S * NT * 2 [+ NT]) blocks x 64 lanes x 8."""
-    dev = Ws.device
-    S = kidx.shape[0]
-    lane_i, lane_kb = _LANE_I.to(dev), _LANE_H.to(dev)
-    rows = 32 * torch.arange(NT, device=dev)[:, None] + lane_i[None, :]                 # [NT, 64]
-    k = kidx.to(dev)[:, lane_kb, :]                                                      # [S, 64, 8]
-    vals = Ws[rows[None, :, :, None].expand(S, NT, 64, 8), k[:, None, :, :].expand(S, NT, 64, 8)]
-    hi, lo = _h2_split(vals)
-    blocks = torch.stack([hi, lo], dim=2).reshape(S * NT * 2, 64, 8)                     # [S, NT, 2, 64, 8]
-    if bs is None:
-        return blocks.contiguous()
-    bb = torch.zeros(NT, 64, 8, dtype=torch.float16, device=dev)
-    bhi, blo = _h2_split(bs.reshape(NT, 32))
-    bb[:, :32, 0] = bhi
-    bb[:, :32, 1] = blo
-    return torch.cat([blocks, bb], dim=0).contiguous()
-
-
-def _pad_rows(W, b, R):
-    Wp = torch.zeros(R, W.shape[1], dtype=torch.float32, device=W.device)
-    bp = torch.zeros(R, dtype=torch.float32, device=W.device)
-    Wp[:W.shape[0]] = W
-    bp[:b.shape[0]] = b
-    return Wp, bp
-
-
-def pack_dense_for_affine_h2(linears):
-    """Pack DenseNet([n_in, H, H, d]) (H = 64 | 128, d <= 96) for bgk_coupling_affine_dense_h2, or DenseNet([n_in, H, H, H, d])
-    for bgk_coupling_affine_dense_h3.  Returns (A0, A1, A2 f16 device tensors, (c0, c1, c2)[, A1b, c1b])."""
-    if len(linears) == 4:
-        l0, l1, l1b, l2 = linears
-        A0, A1, A2, cs = pack_dense_for_affine_h2((l0, l1, l2))
-        W, b = l1b.weight.detach().float(), l1b.bias.detach().float()
-        e = _h2_scale_exp(W, b)
-        return A0, A1, A2, cs, _pack_h2(W * 2.0 ** e, b * 2.0 ** e, _h2_k_hidden(l1b.out_features // 32), NT=l1b.out_features // 32), 2.0 ** -e
-    l0, l1, l2 = linears
-    W0, b0 = l0.weight.detach().float(), l0.bias.detach().float()
-    W1, b1 = l1.weight.detach().float(), l1.bias.detach().float()
-    W2, b2 = l2.weight.detach().float(), l2.bias.detach().float()
-    n_in, H, d = l0.in_features, l0.out_features, l2.out_features
-    HT, OT = H // 32, (d + 31) // 32
-    S0 = (n_in + 1 + 15) // 16
-    e0, e1, e2 = _h2_scale_exp(W0, b0), _h2_scale_exp(W1, b1), _h2_scale_exp(W2, b2)
-    W0e = torch.zeros(H, 16 * S0, dtype=torch.float32, device=W0.device)
-    W0e[:, :n_in] = W0
-    W0e[:, n_in] = b0
-    A0 = _pack_h2(W0e * 2.0 ** e0, None, _h2_k_natural(S0), NT=HT)
-    A1 = _pack_h2(W1 * 2.0 ** e1, b1 * 2.0 ** e1, _h2_k_hidden(HT), NT=HT)
-    W2p, b2p = _pad_rows(W2 * 2.0 ** e2, b2 * 2.0 ** e2, 32 * OT)
-    A2 = _pack_h2(W2p, b2p, _h2_k_hidden(HT), NT=OT)
-    return A0, A1, A2, (2.0 ** -e0, 2.0 ** -e1, 2.0 ** -e2)
-
-
-def pack_dense_for_affine_deep(linears):
-    """Pack DenseNet([n_in, H, ..., H, d]) with 1 .. 8 hidden layers (H = 64 | 128, d <= 96) for bgk_coupling_affine_dense_deep: layer 0
-    and the output layer as pack_dense_for_affine_h2, the hidden -> hidden layers back to back.  Returns (A0, A1 | None, A2, c0, [c1 per
-    hidden -> hidden layer], c2)."""
-    l0, l_out, mids = linears[0], linears[-1], linears[1:-1]
-    W0, b0 = l0.weight.detach().float(), l0.bias.detach().float()
-    W2, b2 = l_out.weight.detach().float(), l_out.bias.detach().float()
-    n_in, H, d = l0.in_features, l0.out_features, l_out.out_features
-    HT, OT = H // 32, (d + 31) // 32
-    S0 = (n_in + 1 + 15) // 16
-    e0, e2 = _h2_scale_exp(W0, b0), _h2_scale_exp(W2, b2)
-    W0e = torch.zeros(H, 16 * S0, dtype=torch.float32, device=W0.device)
-    W0e[:, :n_in] = W0
-    W0e[:, n_in] = b0
-    A0 = _pack_h2(W0e * 2.0 ** e0, None, _h2_k_natural(S0), NT=HT)
-    blocks, c1s = [], []
-    for lin in mids:
-        W, b = lin.weight.detach().float(), lin.bias.detach().float()
-        e = _h2_scale_exp(W, b)
-        blocks.append(_pack_h2(W * 2.0 ** e, b * 2.0 ** e, _h2_k_hidden(HT), NT=HT))
-        c1s.append(2.0 ** -e)
-    A1 = torch.cat(blocks, dim=0).contiguous() if blocks else None
-    W2p, b2p = _pad_rows(W2 * 2.0 ** e2, b2 * 2.0 ** e2, 32 * OT)
-    A2 = _pack_h2(W2p, b2p, _h2_k_hidden(HT), NT=OT)
-    return A0, A1, A2, 2.0 ** -e0, c1s, 2.0 ** -e2
 
 
 def _affine_plan(transformer, y_dim):
@@ -639,18 +428,14 @@ def _affine_plan(transformer, y_dim):
         if per:
             inner = n.net
             n_raw = getattr(getattr(inner, "_layers", [None])[0], "in_features", 0) // 2
-            idx = np.arange(n_raw)[n.indices] if n_raw else np.zeros(0, int)
-            if not (n.left == 0.0 and n.right == 1.0) or n_raw == 0 or not np.array_equal(np.asarray(idx), np.arange(n_raw)):
+            if _periodic_failure(n, 2 * n_raw) is not None:       # (an odd width is the envelope check's, below)
                 return None          # only "all conditioner inputs periodic on [0, 1]" is fused
             n = inner
         if periodic is not None and per != periodic:
             return None
         periodic = per
-        spec = _fusable_dense_deep(n)
-        if spec is None:
-            spec = _fusable_dense_any(n)          # any other depth: bgk_coupling_affine_dense_deep
-            if spec is not None and len(spec[0]) - 1 > DEEP_MAX_HIDDEN:
-                spec = None
+        # two / three hidden layers: bgk_coupling_affine_dense_h2 / _h3; any other depth: bgk_coupling_affine_dense_deep
+        spec = _fusable_dense(n, hidden=range(1, DEEP_MAX_HIDDEN + 1))
         if spec is None:
             if type(n) is DenseNet:
                 return _reject(transformer, "the fused affine kernels take DenseNets with 1 .. 8 hidden layers, biases and one of "
@@ -682,27 +467,6 @@ def _affine_plan(transformer, y_dim):
         cache.update(version=version, y_dim=y_dim, hidden=H_run, d_c=n_in // 2 if periodic else n_in, periodic=bool(periodic), depth=depth,
                      anydepth=anydepth, packed=[None if sp is None else (pack(sp[0]), sp[1]) for sp in specs])
     return cache
-
-
-class _PaddedLinear:
-    """weight / bias of a Linear zero-padded to (out_to, in_to): the stand-in the packers read.  Padded hidden units have weight 0
-    and bias 0, so they hold act(0) = 0 (SiLU / ReLU / Tanh) and feed zero columns of the next layer: same function."""
-
-    def __init__(self, lin, out_to, in_to):
-        W, b = lin.weight.detach(), lin.bias.detach()
-        self.weight = torch.zeros((out_to, in_to), dtype=W.dtype, device=W.device)
-        self.weight[:W.shape[0], :W.shape[1]] = W
-        self.bias = torch.zeros((out_to,), dtype=b.dtype, device=b.device)
-        self.bias[:b.shape[0]] = b
-        self.in_features, self.out_features = in_to, out_to
-
-
-def _pad_hidden(linears, H):
-    """the Linear chain with every hidden width zero-padded to H (input and output widths unchanged)"""
-    n = len(linears)
-    return tuple(_PaddedLinear(lin, H if i < n - 1 else lin.out_features, H if i > 0 else lin.in_features)
-                 for i, lin in enumerate(linears))
-
 
 
 def _cond_parts(x):
@@ -810,133 +574,9 @@ def _fused_affine_anydepth(transformer, plan, x, y2, ldy, B, d, out, ldo, dlogp,
     return out, dlogp[:, None]
 
 
-def pack_dense_for_fused_h2(linears, nc_slot_host, d, n_bins, row_order=1):
-    """Pack DenseNet([n_in, 128, 128, P]) for bgk_coupling_rqs_dense_h2.
-    Returns (A0, A1, A2 f16 device tensors, (c0, c1, c2) unscale factors).  ``row_order``: order of the output layer's rows
-    (bgk_pack_rqs_columns_v): 1 = what every kernel reads; 2 = the permutation the split-f16 inference kernel reads with
-    operand_dtype 2 (8 bins; widths / heights of a lane's element in that lane's accumulator registers)."""
-    l0, l1, l2 = linears
-    W0, b0 = l0.weight.detach().float(), l0.bias.detach().float()
-    W1, b1 = l1.weight.detach().float(), l1.bias.detach().float()
-    W2, b2 = l2.weight.detach().float(), l2.bias.detach().float()
-    n_in = l0.in_features
-    S0 = (n_in + 1 + 15) // 16
-    e0, e1, e2 = _h2_scale_exp(W0, b0), _h2_scale_exp(W1, b1), _h2_scale_exp(W2, b2)
-    W0e = torch.zeros(128, 16 * S0, dtype=torch.float32, device=W0.device)
-    W0e[:, :n_in] = W0
-    W0e[:, n_in] = b0                                   # column of the constant-1 feature
-    A0 = _pack_h2(W0e * 2.0 ** e0, None, _h2_k_natural(S0))
-    A1 = _pack_h2(W1 * 2.0 ** e1, b1 * 2.0 ** e1, _h2_k_hidden())
-    src_t = _src_col_table(d, n_bins, nc_slot_host, W2.device, row_order).to(torch.int64)
-    ncp = src_t.numel()
-    W2r = torch.where(src_t[:, None] >= 0, W2[src_t.clamp_min(0)], torch.zeros((), dtype=W2.dtype, device=W2.device)) * 2.0 ** e2
-    b2r = torch.where(src_t >= 0, b2[src_t.clamp_min(0)], torch.zeros((), dtype=b2.dtype, device=b2.device)) * 2.0 ** e2
-    A2 = torch.cat([_pack_h2(W2r[c * 128:(c + 1) * 128], b2r[c * 128:(c + 1) * 128], _h2_k_hidden())
-                    for c in range(ncp // 128)], dim=0).contiguous()
-    return A0, A1, A2, (2.0 ** -e0, 2.0 ** -e1, 2.0 ** -e2)
-
-
-def pack_dense_for_fused_w256(linears, nc_slot_host, d, n_bins):
-    """Pack DenseNet([n_in, 256, 256, P]) for the width-256 kernel behind bgk_coupling_rqs_dense_h2 (H0 = H1 = 256;
-    bgk_fused.hip::coupling_rqs_dense_w256_kernel): every GEMM produces 128 output rows at a time, so layer 0 and layer 1 are packed as
-    two 128-row halves (rows 0..127, then 128..255), each in the width-128 block layout with 16 k16-steps over the 256 hidden inputs
-    (k order = the accumulator layout of 8 tiles), the parameter chunks likewise.  Returns (A0, A1, A2 f16 device tensors, (c0, c1, c2))."""
-    l0, l1, l2 = linears
-    W0, b0 = l0.weight.detach().float(), l0.bias.detach().float()
-    W1, b1 = l1.weight.detach().float(), l1.bias.detach().float()
-    W2, b2 = l2.weight.detach().float(), l2.bias.detach().float()
-    assert W0.shape[0] == 256 and W1.shape == (256, 256) and W2.shape[1] == 256
-    n_in = l0.in_features
-    S0 = (n_in + 1 + 15) // 16
-    e0, e1, e2 = _h2_scale_exp(W0, b0), _h2_scale_exp(W1, b1), _h2_scale_exp(W2, b2)
-    W0e = torch.zeros(256, 16 * S0, dtype=torch.float32, device=W0.device)
-    W0e[:, :n_in] = W0
-    W0e[:, n_in] = b0                                   # column of the constant-1 feature
-    kh = _h2_k_hidden(8)
-    A0 = torch.cat([_pack_h2(W0e[g * 128:(g + 1) * 128] * 2.0 ** e0, None, _h2_k_natural(S0)) for g in range(2)], dim=0).contiguous()
-    A1 = torch.cat([_pack_h2(W1[g * 128:(g + 1) * 128] * 2.0 ** e1, b1[g * 128:(g + 1) * 128] * 2.0 ** e1, kh) for g in range(2)],
-                   dim=0).contiguous()
-    src_t = _src_col_table(d, n_bins, nc_slot_host, W2.device).to(torch.int64)
-    W2r = torch.where(src_t[:, None] >= 0, W2[src_t.clamp_min(0)], torch.zeros((), dtype=W2.dtype, device=W2.device)) * 2.0 ** e2
-    b2r = torch.where(src_t >= 0, b2[src_t.clamp_min(0)], torch.zeros((), dtype=b2.dtype, device=b2.device)) * 2.0 ** e2
-    A2 = torch.cat([_pack_h2(W2r[c * 128:(c + 1) * 128], b2r[c * 128:(c + 1) * 128], kh)
-                    for c in range(src_t.numel() // 128)], dim=0).contiguous()
-    return A0, A1, A2, (2.0 ** -e0, 2.0 ** -e1, 2.0 ** -e2)
-
-
-DEEP_MAX_HIDDEN = 8     # hidden layers bgk_coupling_rqs_dense_deep takes (DEEP_MAX_HH + 1 in bgk_fused.hip)
-
-
-def pack_dense_for_fused_deep(linears, nc_slot_host, d, n_bins):
-    """Pack DenseNet([n_in, 128, ..., 128, P]) with 1 .. 8 hidden layers for bgk_coupling_rqs_dense_deep: layer 0 and the parameter chunks
-    as pack_dense_for_fused_h2, the hidden -> hidden layers back to back in A1.  Returns (A0, A1 | None, A2, c0, [c1 per layer], c2)."""
-    l0, l_out, mids = linears[0], linears[-1], linears[1:-1]
-    W0, b0 = l0.weight.detach().float(), l0.bias.detach().float()
-    W2, b2 = l_out.weight.detach().float(), l_out.bias.detach().float()
-    n_in = l0.in_features
-    S0 = (n_in + 1 + 15) // 16
-    e0, e2 = _h2_scale_exp(W0, b0), _h2_scale_exp(W2, b2)
-    W0e = torch.zeros(128, 16 * S0, dtype=torch.float32, device=W0.device)
-    W0e[:, :n_in] = W0
-    W0e[:, n_in] = b0                                   # column of the constant-1 feature
-    A0 = _pack_h2(W0e * 2.0 ** e0, None, _h2_k_natural(S0))
-    blocks, c1s = [], []
-    for lin in mids:
-        W, b = lin.weight.detach().float(), lin.bias.detach().float()
-        e = _h2_scale_exp(W, b)
-        blocks.append(_pack_h2(W * 2.0 ** e, b * 2.0 ** e, _h2_k_hidden()))
-        c1s.append(2.0 ** -e)
-    A1 = torch.cat(blocks, dim=0).contiguous() if blocks else None
-    src_t = _src_col_table(d, n_bins, nc_slot_host, W2.device).to(torch.int64)
-    W2r = torch.where(src_t[:, None] >= 0, W2[src_t.clamp_min(0)], torch.zeros((), dtype=W2.dtype, device=W2.device)) * 2.0 ** e2
-    b2r = torch.where(src_t >= 0, b2[src_t.clamp_min(0)], torch.zeros((), dtype=b2.dtype, device=b2.device)) * 2.0 ** e2
-    A2 = torch.cat([_pack_h2(W2r[c * 128:(c + 1) * 128], b2r[c * 128:(c + 1) * 128], _h2_k_hidden())
-                    for c in range(src_t.numel() // 128)], dim=0).contiguous()
-    return A0, A1, A2, 2.0 ** -e0, c1s, 2.0 ** -e2
-
-
-def pack_dense_for_fused_h2_device(linears, src_col_dev, n_chunks, bufs=None, bf16=False):
-    """Device-side twin of pack_dense_for_fused_h2 (bgk_pack_dense_h2): returns (A0, A1, A2, cs) with cs the
-    device scale table {2^s, 2^-s} x 3.  ``bufs`` = previous result to overwrite in place."""
-    l0, l1, l2 = linears
-    dev = l0.weight.device
-    n_in = l0.in_features
-    S0 = (n_in + 1 + 15) // 16
-    if bufs is None:
-        A0 = torch.empty((S0 * 8, 64, 8), dtype=torch.float16, device=dev)
-        A1 = torch.empty((8 * 8 + 4, 64, 8), dtype=torch.float16, device=dev)
-        A2 = torch.empty((n_chunks * (8 * 8 + 4), 64, 8), dtype=torch.float16, device=dev)
-        cs = torch.empty(6, dtype=torch.float32, device=dev)
-    else:
-        A0, A1, A2, cs = bufs
-    ws = [t.detach().contiguous() for lin in linears for t in (lin.weight, lin.bias)]
-    assert all(w.dtype == torch.float32 for w in ws)
-    with torch.cuda.device(dev):
-        st = _lib.lib().bgk_pack_dense_h2(
-            _lib.ptr(ws[0]), _lib.ptr(ws[1]), n_in, 128, _lib.ptr(ws[2]), _lib.ptr(ws[3]), _lib.ptr(ws[4]), _lib.ptr(ws[5]),
-            l2.out_features, _lib.ptr(src_col_dev), n_chunks, 4, int(bf16), _lib.ptr(A0), _lib.ptr(A1), _lib.ptr(A2), _lib.ptr(cs),
-            _lib.stream_ptr(dev))
-    _lib.check(st, "bgk_pack_dense_h2")
-    return A0, A1, A2, cs
-
-
-T_OPERAND_MAX_IN = 96     # widest conditioner input bgk_pack_dense_h2_t / bgk_dense_backward_dx take (three 32-feature output tiles)
-
 BATCHED_REPACK = True     # training.FlatAdam.step re-packs the operands of every fused training layer in three launches
 
 _TRAIN_PLANS = weakref.WeakSet()      # transformers whose fused plan ran a training forward on device-packed split-f16 operands
-
-
-def _t_operand_bufs(bufs, P, n_in, dev):
-    """transposed-weight operands T0..T2 of bgk_dense_backward_dx for a conditioner [n_in, 128, 128, P] (allocated once per plan)"""
-    FT, S2 = (n_in + 31) // 32, ((P + 15) // 16 + 3) // 4 * 4      # T2: whole groups of 4 k-steps (zero blocks behind ceil(P / 16))
-    key = (P, n_in, str(dev))
-    if bufs.get("key") != key:
-        bufs.clear()
-        bufs.update(key=key, T0=torch.empty((8 * FT * 2 + FT, 64, 8), dtype=torch.float16, device=dev),
-                    T1=torch.empty((8 * 8 + 4, 64, 8), dtype=torch.float16, device=dev),
-                    T2=torch.empty((S2 * 8 + 4, 64, 8), dtype=torch.float16, device=dev))
-    return bufs["T0"], bufs["T1"], bufs["T2"]
 
 
 def repack_training_plans(param_ids=None):
@@ -1003,25 +643,6 @@ def repack_training_plans(param_ids=None):
     return done
 
 
-def _src_col_table(d, n_bins, nc_slot_host, device, row_order=1):
-    """packed row -> source row of the output layer (-1 = padding) in row order ``row_order`` (bgk_pack_rqs_columns_v)"""
-    ncp = _lib.lib().bgk_pack_rqs_columns_v(d, n_bins, None, row_order, None, None)
-    if ncp <= 0:
-        raise ValueError(f"no row order {row_order} for {n_bins} bins")
-    src = np.empty(ncp, dtype=np.int32)
-    slots = np.ascontiguousarray(nc_slot_host, dtype=np.int32)
-    _lib.lib().bgk_pack_rqs_columns_v(d, n_bins, slots.ctypes.data, row_order, src.ctypes.data, None)
-    return torch.as_tensor(src, device=device)
-
-
-def rqs_row_perm(row_order):
-    """[128] int32: position within a 128-row chunk of row order ``row_order`` -> row of order 1 within the chunk (-1 = unused)"""
-    perm = np.empty(128, dtype=np.int32)
-    if _lib.lib().bgk_pack_rqs_columns_v(1, 8, None, row_order, None, perm.ctypes.data) <= 0:
-        raise ValueError(f"no row order {row_order}")
-    return perm
-
-
 REGISTER_PARAMS = True     # split-f16 inference (8 bins, width 128) on operands in row order 2; False: the order-1 operands (same bits)
 
 
@@ -1051,7 +672,7 @@ def _fused_plan(transformer, y_dim, nc_slot_host):
     net = transformer._params_net
     periodic = False
     if type(net) is WrapPeriodic:
-        if not (net.left == 0.0 and net.right == 1.0):
+        if _periodic_failure(net) == "interval":
             return _reject(transformer, "WrapPeriodic on an interval other than [0, 1]") if _looks_dense(net) else None
         inner = net.net
         periodic = True
@@ -1059,7 +680,7 @@ def _fused_plan(transformer, y_dim, nc_slot_host):
         inner = net
     spec = _fusable_dense(inner)
     if spec is None:
-        deep = _fusable_dense_any(inner)
+        deep = _fusable_dense(inner, hidden=None)
         if deep is not None and len(deep[0]) - 1 <= DEEP_MAX_HIDDEN and mode == "f16x2" \
                 and all(lin.out_features <= 128 for lin in deep[0][:-1]):
             return _deep_plan(transformer, net, deep, periodic, y_dim, nc_slot_host)
@@ -1078,21 +699,19 @@ def _fused_plan(transformer, y_dim, nc_slot_host):
     padded = (l0.out_features, l1.out_features) != (H_run, H_run)
     if y_dim > 64:
         return _reject(transformer, f"{y_dim} transformed dims: at most 64 are fused")
-    n_nc = int((nc_slot_host >= 0).sum())
-    P = l2.out_features
-    n_bins = (P - n_nc) // (3 * y_dim)
-    if 3 * n_bins * y_dim + n_nc != P:
+    shape = _spline_shape(l2.out_features, y_dim, nc_slot_host)
+    if shape is None:
         return None
+    n_bins, circ_mask = shape
     if n_bins != 8 and not (n_bins in (4, 12, 16, 32) and mode == "f16x2"):
         # K = 4 | 12 | 16 | 32: split-f16 form only (first-generation kernel); anything else: generic path
         return _reject(transformer, f"{n_bins} bins in gemm_mode '{mode}': fused for 8 bins, and for 4 / 12 / 16 / 32 bins in mode 'f16x2'"
                                     + ("; more than 64 bins run on device torch ops" if n_bins > 64 else ""))
     d_c = l0.in_features // 2 if periodic else l0.in_features
-    if periodic:
-        idx = np.arange(d_c)[net.indices] if not isinstance(net.indices, slice) or net.indices != slice(None) else np.arange(d_c)
-        if len(idx) != d_c or 2 * d_c != l0.in_features or not np.array_equal(np.asarray(idx), np.arange(d_c)):
-            # only "all conditioner inputs periodic, in natural order" is fused (the kernel featurises columns 0..d_c-1)
-            return _reject(transformer, "WrapPeriodic over a subset / permutation of the conditioner inputs")
+    # only "all conditioner inputs periodic, in natural order" is fused (the kernel featurises columns 0..d_c-1); a net without
+    # inputs is left to the kernel entry's own argument check
+    if periodic and l0.in_features and _periodic_failure(net, l0.in_features) is not None:
+        return _reject(transformer, "WrapPeriodic over a subset / permutation of the conditioner inputs")
     params = [p for lin in (l0, l1, l2) for p in (lin.weight, lin.bias)]
     version = tuple(param_state_key(p) for p in params)
     cache = transformer._fused_cache
@@ -1103,7 +722,7 @@ def _fused_plan(transformer, y_dim, nc_slot_host):
         stale = True
     if stale:
         common = dict(version=version, y_dim=y_dim, mode=mode, device=dev, act=act, periodic=periodic, d_c=d_c, n_bins=n_bins,
-                      padded=padded, hidden=H_run, circ_mask=int(sum(1 << j for j in range(y_dim) if nc_slot_host[j] < 0)))
+                      padded=padded, hidden=H_run, circ_mask=circ_mask)
         if padded:
             l0, l1, l2 = _pad_hidden((l0, l1, l2), H_run)
         if mode == "bf16" and dev.type != "cuda":
@@ -1133,19 +752,16 @@ def _deep_plan(transformer, net, spec, periodic, y_dim, nc_slot_host):
     lins, act = spec
     if y_dim > 64:
         return _reject(transformer, f"{y_dim} transformed dims: at most 64 are fused")
-    n_nc = int((nc_slot_host >= 0).sum())
-    P = lins[-1].out_features
-    n_bins = (P - n_nc) // (3 * y_dim)
-    if 3 * n_bins * y_dim + n_nc != P:
+    shape = _spline_shape(lins[-1].out_features, y_dim, nc_slot_host)
+    if shape is None:
         return None
+    n_bins, circ_mask = shape
     if n_bins not in (4, 8, 12, 16, 32):
         return _reject(transformer, f"{n_bins} bins: the one-launch kernels take 4 / 8 / 12 / 16 / 32")
     l0 = lins[0]
     d_c = l0.in_features // 2 if periodic else l0.in_features
-    if periodic:
-        idx = np.arange(d_c)[net.indices] if not isinstance(net.indices, slice) or net.indices != slice(None) else np.arange(d_c)
-        if len(idx) != d_c or 2 * d_c != l0.in_features or not np.array_equal(np.asarray(idx), np.arange(d_c)):
-            return _reject(transformer, "WrapPeriodic over a subset / permutation of the conditioner inputs")
+    if periodic and l0.in_features and _periodic_failure(net, l0.in_features) is not None:
+        return _reject(transformer, "WrapPeriodic over a subset / permutation of the conditioner inputs")
     version = tuple(param_state_key(p) for lin in lins for p in (lin.weight, lin.bias))
     cache = transformer._fused_cache
     dev = l0.weight.device
@@ -1155,8 +771,7 @@ def _deep_plan(transformer, net, spec, periodic, y_dim, nc_slot_host):
         padded = any(lin.out_features != 128 for lin in lins[:-1])
         run = _pad_hidden(lins, 128) if padded else lins
         cache.update(version=version, y_dim=y_dim, mode="f16x2", device=dev, act=act, periodic=periodic, d_c=d_c, n_bins=n_bins,
-                     padded=padded, hidden=128, deep=len(lins) - 1, cs=None,
-                     circ_mask=int(sum(1 << j for j in range(y_dim) if nc_slot_host[j] < 0)),
+                     padded=padded, hidden=128, deep=len(lins) - 1, cs=None, circ_mask=circ_mask,
                      packed=pack_dense_for_fused_deep(run, nc_slot_host, y_dim, n_bins))
     return cache
 
@@ -1752,12 +1367,8 @@ def _affine_train_net(net):
     if spec is None:
         return None
     (l0, l1, l2), act = spec
-    if per:
-        n_raw = l0.in_features // 2
-        if not (net.left == 0.0 and net.right == 1.0) or n_raw == 0 or 2 * n_raw != l0.in_features:
-            return None
-        if not np.array_equal(np.asarray(np.arange(n_raw)[net.indices]), np.arange(n_raw)):
-            return None
+    if per and _periodic_failure(net, l0.in_features) is not None:
+        return None
     if l0.out_features > 128 or l1.out_features > 128 or l1.in_features != l0.out_features or l2.in_features != l1.out_features:
         return None
     return (l0, l1, l2), act, per

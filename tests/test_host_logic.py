@@ -274,7 +274,7 @@ def _emulate_h2_gemm(blocks, NT, S, bvals):
 def test_split_f16_packing_layout():
     """the host-side operand packing of the split-f16 kernels reproduces W x + b when the B operand is fed in the MFMA
     accumulator layout (hidden layers) / natural order (layer 0) -- no GPU needed"""
-    from bgflow_amd import dense
+    from bgflow_amd import packing as dense          # the layout helpers live in packing.py
     rng = np.random.default_rng(0)
     # hidden layer, HT = 4 input tiles (K = 128), NT = 2 output tiles
     W = torch.tensor(rng.normal(size=(64, 128)) * 0.3, dtype=torch.float32)
