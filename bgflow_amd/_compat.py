@@ -50,6 +50,8 @@ _MAP = {
     "distribution.sampling.mcmc": "sampling",
     "distribution.sampling.base": "distributions",
     "distribution.sampling.dataset": "training",
+    "distribution.sampling._mcmc": "permutation",
+    "distribution.sampling._mcmc.permutation": "permutation",
     "nn.training": "training",
     "nn.training.trainers": "training",
     "factory.tensor_info": "factory",

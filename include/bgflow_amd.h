@@ -1044,6 +1044,30 @@ int bgk_bar_solve_steps(const void* forward_work, int64_t n_forward, const void*
                         int32_t nblk_forward, int32_t nblk_reverse, double* partial, double* record, int32_t maximum_iterations,
                         double relative_tolerance, int32_t n_steps, void* stream);
 
+/* Permutation reduction: replaces the per-sample loop of `HungarianMapper.map` / `.is_permuted`
+ * (`distribution/sampling/_mcmc/permutation.py:38-54`, `:56-73`: a squared-distance cost matrix per sample and scipy's
+ * linear_sum_assignment on the host).  For every sample b the m identical particles (1 <= m <= 64, d = 1 .. 3 dimensions) are relabelled
+ * so that the sum over i of |xref[i] - x[b, sigma(i)]|^2 is smallest: a linear sum assignment per sample, solved by shortest augmenting
+ * paths with potentials, one wavefront per sample (lane j = column j), the cost C[i][j] formed in registers in f32 (difference, square,
+ * sum over k = 0 .. d-1, each op rounded) -- no cost matrix in memory.  Ties of the column search go to the lowest column, so the
+ * permutation depends on the sample alone (not on B, the launch or the run).  Every loop has a fixed trip count bound (m rows, at most
+ * m search steps and m unwinding steps per row) whatever the values are.
+ *   x [B, ldx], ldx >= n d: the samples, particle q at columns q d .. q d + d - 1; aligned to 4 bytes only (a column slice of a wider
+ *     tensor works).  xref [n d]: the reference configuration (device).  B == 0: a no-op.  n d <= 4096.
+ *   identical_host: HOST array of the m identical particles' indices, strictly increasing, each in [0, n); it travels in the kernel's
+ *     arguments (no device copy).  Row i of the problem is reference particle identical[i], column j sample particle identical[j].
+ *   Outputs, each may be NULL (not written):
+ *     y [B, ldy], ldy >= n d, not overlapping x: the sample with slot identical[i] holding sample particle identical[sigma(i)]; every
+ *       other column copied unchanged
+ *     perm [B, m] int32: sigma;  cost [B] f32: sum_i C[i][sigma(i)] (summed in a fixed order);
+ *     status [B] int32: 0 solved, 1 = a non-finite coordinate among the sample's identical particles or the reference's (decided before
+ *       the solver runs; sigma is then the identity, cost the identity's);  permuted [B] int32: 1 where sigma is not the identity.
+ * BGK_EINVAL (text in bgk_last_error) before any launch: null x / xref / identical_host, B < 0, m outside 1 .. 64, d outside 1 .. 3,
+ * n < m, n d > 4096, indices not strictly increasing or outside [0, n), a stride below n d, a pointer not aligned to 4 bytes. */
+int bgk_assign_particles(const float* x, int64_t ldx, int64_t B, int32_t n, int32_t d, const float* xref,
+                         const int32_t* identical_host, int32_t m, float* y, int64_t ldy, int32_t* perm, float* cost,
+                         int32_t* status, int32_t* permuted, void* stream);
+
 /* One Linear layer (+ bias + activation) of a conditioner network on its own: y = act(x W^T + b).
  * Replaces one `Linear (, activation)` pair of DenseNet._layers (nn/dense.py:30-48) for the networks the one-launch coupling kernels do
  * not take (conditioner_factory.py:76-80 allows any `hidden` tuple: other depths, layers wider than 256; README.md:72-79's [1, 4, 1]
