@@ -1365,7 +1365,7 @@ extern "C" int bgk_ic_ic2xyz_backward(const float* bonds, const float* angles, c
         hipLaunchKernelGGL(ic_ic2xyz_bwd_fix_kernel, dim3(ts == 64 ? 64 : 256), dim3(ts), shm, st, f);
         return bgk_launch_status(what);
     };
-    if (fix_ws && enforce_boundaries) {
+    if (fix_ws) {                                                  /* (also without clamps: the caller reads an empty list, not a stale count) */
         const hipError_t e = hipMemsetAsync(fix_ws, 0, sizeof(int32_t), st);
         if (e != hipSuccess) { bgk_set_error("%s: %s", what, hipGetErrorString(e)); return (int)e; }
     }

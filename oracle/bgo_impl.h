@@ -622,8 +622,8 @@ void FN(bgo_ic_ic2xyz)(const REAL* bonds, const REAL* angles, const REAL* torsio
  * against the reference to 1e-15 by the golden tests.
  *   fwd:  x3 [B,9] = (x0,x1,x2)  ->  out [B,9] = (x0[3], d01, d12, a012, alpha, beta, gamma), dlogp
  *   inv:  the reverse.  normalize: a012/pi, (alpha,gamma + pi)/2pi; beta stays in [-1,1]. */
-void FN(bgo_refsys)(const REAL* in, int64_t B, int inverse, int normalize, REAL eps, int enforce,
-                    REAL* out, REAL* dlogp)
+static void FN(bgo_refsys_impl)(const REAL* in, int64_t B, int inverse, int normalize, REAL eps, int enforce,
+                                int f32_quarter_turn, REAL* out, REAL* dlogp)
 {
     const REAL PI = (REAL)3.14159265358979323846;
 #pragma omp parallel for schedule(static)
@@ -680,7 +680,11 @@ void FN(bgo_refsys)(const REAL* in, int64_t B, int inverse, int normalize, REAL 
             FN(v3cross)(v1, v2, nv); FN(v3cross)(v1, nv, nn);
             REAL nvn = FN(v3norm)(nv); if (enforce && nvn < eps) nvn = eps;
             REAL nnn = FN(v3norm)(nn); if (enforce && nnn < eps) nnn = eps;
-            REAL tq = (REAL)0.5 * PI, st = R_SIN(tq), ct = R_COS(tq), sa = R_SIN(a012), ca = R_COS(a012);
+            /* the third atom's torsion is a quarter turn.  The reference builds it as torch.Tensor([[0.5 * np.pi]]) -- an f32 tensor --
+             * before it casts it to the input's precision (ic_helper.py:463): its f64 run places the atom with pi/2 rounded to f32
+             * (cos = -4.4e-8, 1e-8 nm in x, and its inverse is no exact inverse of its forward).  ``f32_quarter_turn`` restates that, so
+             * that the f64 flavour meets the reference's f64 to round-off; without it the quarter turn is exact. */
+            REAL tq = f32_quarter_turn ? (REAL)(float)(0.5 * 3.14159265358979323846) : (REAL)0.5 * PI, st = R_SIN(tq), ct = R_COS(tq), sa = R_SIN(a012), ca = R_COS(a012);
             REAL v3[3] = { nv[0]/nvn*(-st) + nn[0]/nnn*ct, nv[1]/nvn*(-st) + nn[1]/nnn*ct, nv[2]/nvn*(-st) + nn[2]/nnn*ct };
             REAL v3n = FN(v3norm)(v3); if (enforce && v3n < eps) v3n = eps;
             REAL v1n = FN(v3norm)(v1); if (enforce && v1n < eps) v1n = eps;
@@ -703,6 +707,17 @@ void FN(bgo_refsys)(const REAL* in, int64_t B, int inverse, int normalize, REAL 
             dlogp[b] = dl;
         }
     }
+}
+
+void FN(bgo_refsys)(const REAL* in, int64_t B, int inverse, int normalize, REAL eps, int enforce, REAL* out, REAL* dlogp)
+{
+    FN(bgo_refsys_impl)(in, B, inverse, normalize, eps, enforce, 0, out, dlogp);
+}
+
+/* the same with the inverse's quarter turn rounded to f32 like the reference's (see bgo_refsys_impl) */
+void FN(bgo_refsys_f32turn)(const REAL* in, int64_t B, int inverse, int normalize, REAL eps, int enforce, REAL* out, REAL* dlogp)
+{
+    FN(bgo_refsys_impl)(in, B, inverse, normalize, eps, enforce, 1, out, dlogp);
 }
 
 /* Backward (VJP) of bgo_ic_ic2xyz for first-order losses.  The reference differentiates

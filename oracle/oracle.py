@@ -328,16 +328,18 @@ def ic_ic2xyz_backward(bonds, angles, torsions, x, g_x, g_dlogp, z_matrix, fixed
     return gb, ga, gt, gf
 
 
-def refsys(v, inverse=False, normalize_angles=True, eps=1e-7, enforce_boundaries=True, dtype=np.float32):
+def refsys(v, inverse=False, normalize_angles=True, eps=1e-7, enforce_boundaries=True, dtype=np.float32, f32_quarter_turn=False):
     """ReferenceSystemTransformation (crd_transform/ic.py:128-265) on packed 9-vectors:
-    forward (x0,x1,x2) -> (x0, d01, d12, a012, alpha, beta, gamma); inverse the reverse.  Returns (out [B,9], dlogp [B,1])."""
+    forward (x0,x1,x2) -> (x0, d01, d12, a012, alpha, beta, gamma); inverse the reverse.  Returns (out [B,9], dlogp [B,1]).
+    ``f32_quarter_turn``: place the third atom of the inverse with pi/2 rounded to f32 as the reference does in either precision
+    (bgo_impl.h); no difference in f32."""
     sfx, cr = _suffix(dtype)
     v = _np(v, dtype)
     B = v.shape[0]
     out = np.empty((B, 9), dtype)
     dl = np.empty((B,), dtype)
-    getattr(lib(), "bgo_refsys" + sfx)(_ptr(v), _c_i64(B), _c_int(int(inverse)), _c_int(int(normalize_angles)), cr(eps),
-                                       _c_int(int(enforce_boundaries)), _ptr(out), _ptr(dl))
+    fn = getattr(lib(), ("bgo_refsys_f32turn" if f32_quarter_turn else "bgo_refsys") + sfx)
+    fn(_ptr(v), _c_i64(B), _c_int(int(inverse)), _c_int(int(normalize_angles)), cr(eps), _c_int(int(enforce_boundaries)), _ptr(out), _ptr(dl))
     return out, dl[:, None]
 
 
@@ -360,12 +362,12 @@ def global_ic_forward(x, z_matrix, normalize_angles=True, eps=1e-7, enforce_boun
 
 
 def global_ic_inverse(bonds, angles, torsions, x0, R, z_matrix, normalize_angles=True, eps=1e-7,
-                      enforce_boundaries=True, dtype=np.float32):
+                      enforce_boundaries=True, dtype=np.float32, f32_quarter_turn=False):
     """GlobalInternalCoordinateTransformation._inverse (ic.py:674-716)"""
     init, zrel = slice_initial_atoms(z_matrix)
     bonds, angles = _np(bonds, dtype), _np(angles, dtype)
     v = np.concatenate([_np(x0, dtype).reshape(-1, 3), bonds[:, 0:2], angles[:, 0:1], _np(R, dtype)], axis=1)
-    xinit, dl_ref = refsys(v, True, normalize_angles, eps, enforce_boundaries, dtype)
+    xinit, dl_ref = refsys(v, True, normalize_angles, eps, enforce_boundaries, dtype, f32_quarter_turn)
     x, dl_rel = ic_ic2xyz(bonds[:, 2:], angles[:, 1:], torsions, xinit, zrel, init, normalize_angles, eps,
                           enforce_boundaries, dtype=dtype)
     return x, dl_rel + dl_ref

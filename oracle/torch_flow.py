@@ -12,6 +12,9 @@ the time it takes is what the reference would spend here):
   dense / periodic    DenseNet.forward (nn/dense.py:47-48), WrapPeriodic.forward (nn/periodic.py:30-37)
   cdf_block           CDFTransform (nn/flow/cdf.py:28-46) over TruncatedNormalDistribution (distribution/normal.py:215-227),
                       torch Normal / uniform marginals (factory/icmarginals.py:41-77)
+  ic2xyz_torch        RelativeInternalCoordinateTransformation / MixedCoordinateTransformation._inverse (crd_transform/ic.py:435-513)
+  xyz2ic_torch        their _forward (ic.py:386-433), written from the formulas; both with all three constructor switches and
+                      differentiable -- tests/test_host_ic_switches.py pins them to the reference per element, gradients included
 """
 import numpy as np
 import torch
@@ -177,11 +180,18 @@ def cdf_block(block, x, inverse):
     return y, -logp(y).sum(dim=-1, keepdim=True)
 
 
+def _clamp_min(rel):
+    """the transformation's norm clamp: ``v.clamp_min(eps)`` under enforce_boundaries, the identity without"""
+    eps = float(rel._eps)
+    return (lambda v: v.clamp_min(eps)) if rel._enforce_boundaries else (lambda v: v)
+
+
 def ic2xyz_torch(ic, bonds, angles, torsions, zfix):
     """IC -> xyz with torch ops, differentiable by autograd: the op chain of RelativeInternalCoordinateTransformation._inverse /
     MixedCoordinateTransformation._inverse (nn/flow/crd_transform/ic.py:435-513, 862-884; ic2xyz_deriv ic_helper.py:372-452;
     blackening pca.py:85-93), one vectorised step per dependency block of the Z-matrix like the reference.  Used by the CPU
-    KL-step baseline (the C oracle has no autograd)."""
+    KL-step baseline (the C oracle has no autograd).  All three switches of the transformation are honoured: ``normalize_angles``,
+    ``eps`` and ``enforce_boundaries`` (off: no norm is clamped)."""
     rel = getattr(ic, "_rel_ic", ic)
     B, n = bonds.shape[0], bonds.shape[1]
     place = torch.as_tensor(np.asarray(rel._tables._host["place"]), dtype=torch.long)
@@ -193,7 +203,7 @@ def ic2xyz_torch(ic, bonds, angles, torsions, zfix):
         dl = dl - w.jacobian_xz.to(zfix)
     else:
         xf = zfix
-    eps = float(rel._eps)
+    clamp = _clamp_min(rel)
     if rel._normalize_angles:
         angles = angles * np.pi
         torsions = torsions * (2 * np.pi) - np.pi
@@ -210,12 +220,12 @@ def ic2xyz_torch(ic, bonds, angles, torsions, zfix):
         v1, v2 = p1 - p2, p1 - p3
         nv = torch.cross(v1, v2, dim=-1)
         nn = torch.cross(v1, nv, dim=-1)
-        nh = nv / nv.norm(dim=-1, keepdim=True).clamp_min(eps)
-        nnh = nn / nn.norm(dim=-1, keepdim=True).clamp_min(eps)
+        nh = nv / clamp(nv.norm(dim=-1, keepdim=True))
+        nnh = nn / clamp(nn.norm(dim=-1, keepdim=True))
         v3 = -torch.sin(t) * nh + torch.cos(t) * nnh
-        v3n = v3.norm(dim=-1, keepdim=True).clamp_min(eps)
+        v3n = clamp(v3.norm(dim=-1, keepdim=True))
         v3h = v3 / v3n
-        v1h = v1 / v1.norm(dim=-1, keepdim=True).clamp_min(eps)
+        v1h = v1 / clamp(v1.norm(dim=-1, keepdim=True))
         new = p1 + v3h * d * torch.sin(a) - v1h * d * torch.cos(a)
         Jd = v3h * torch.sin(a) - v1h * torch.cos(a)
         Ja = v3h * d * torch.cos(a) + v1h * d * torch.sin(a)
@@ -229,10 +239,72 @@ def ic2xyz_torch(ic, bonds, angles, torsions, zfix):
     return pos.reshape(B, -1), dl
 
 
+def xyz2ic_torch(ic, x):
+    """xyz -> IC with torch ops, differentiable by autograd, written from the formulas of the transformation (bond length, bond angle
+    and dihedral of each Z-matrix row (a, b, c, d) with their derivatives w.r.t. atom a; log|det J| per row from the 3x3 matrix of those
+    derivatives; crd_transform/ic.py:386-433, 838-860).  Returns (bonds, angles, torsions, fixed, dlogp [B,1]); ``ic`` is a Relative or
+    Mixed transformation of bgflow_amd, all three switches honoured:
+      bond      d = |x_b - x_a|,  dd/da = -(x_b - x_a) / d
+      angle     u = (x_a - x_b) / |x_a - x_b|, s = (x_c - x_b) / |x_c - x_b|, c = u . s, a = acos(c);
+                dc/da = (s - u (u . s)) / |x_a - x_b|, da/da = -dc/da / sqrt(1 - c^2)
+      dihedral  with h = (x_c - x_b) / |x_c - x_b|, v and w the parts of x_a - x_b and x_d - x_c not along h:
+                X = v . w, Y = (h x v) . w, t = atan2(Y, X);  dt/da = [(-Y) P w + X P (w x h)] / (X^2 + Y^2),  P = 1 - h h^T
+    Under enforce_boundaries every norm and X^2 + Y^2 is clamped from below at eps and c to [-1 + eps, 1 - eps] (the derivative formulas
+    keep their form, as in the reference, and autograd sees clamp's derivative)."""
+    rel = getattr(ic, "_rel_ic", ic)
+    B = x.shape[0]
+    p = x.reshape(B, -1, 3)
+    z = torch.as_tensor(np.asarray(rel._tables._host["zmat"]), dtype=torch.long)
+    fixed = torch.as_tensor(np.asarray(rel._tables._host["fixed"]), dtype=torch.long)
+    n = z.shape[0]
+    clamp, eps, enforce = _clamp_min(rel), float(rel._eps), bool(rel._enforce_boundaries)
+    xa, xb, xc, xd = (p[:, z[:, k]] for k in range(4))
+    dot = lambda a, b: (a * b).sum(-1, keepdim=True)      # noqa: E731
+    # bond
+    r = xb - xa
+    d = clamp(r.norm(dim=-1, keepdim=True))
+    Jd = -r / d
+    # angle
+    rab, rcb = xa - xb, xc - xb
+    nab = clamp(rab.norm(dim=-1, keepdim=True))
+    u, sv = rab / nab, rcb / clamp(rcb.norm(dim=-1, keepdim=True))
+    c = dot(u, sv)
+    Jc = (sv - u * dot(u, sv)) / nab
+    if enforce:
+        c = c.clamp(-1.0 + eps, 1.0 - eps)
+    ang = torch.acos(c)
+    Ja = -Jc / torch.sqrt(1.0 - c.pow(2))
+    # dihedral
+    b0, b1, b2 = xa - xb, xc - xb, xd - xc
+    h = b1 / clamp(b1.norm(dim=-1, keepdim=True))
+    v = b0 - dot(b0, h) * h
+    w = b2 - dot(b2, h) * h
+    X, Y = dot(v, w), dot(torch.cross(h, v, dim=-1), w)
+    tor = torch.atan2(Y, X)
+    q = clamp(X.pow(2) + Y.pow(2))
+    wP = w - dot(w, h) * h
+    wxh = torch.cross(w, h, dim=-1)
+    Jt = (-Y / q) * wP + (X / q) * (wxh - dot(wxh, h) * h)
+    det = (torch.cross(Jd, Ja, dim=-1) * Jt).sum(-1)
+    dl = torch.log(det.abs()).sum(-1, keepdim=True)
+    bonds, angles, torsions = d[..., 0], ang[..., 0], tor[..., 0]
+    if rel._normalize_angles:
+        angles = angles / np.pi
+        torsions = (torsions + np.pi) / (2 * np.pi)
+        dl = dl - n * (np.log(np.pi) + np.log(2 * np.pi))
+    xf = p[:, fixed].reshape(B, -1)
+    if hasattr(ic, "_whiten"):
+        wh = ic._whiten
+        xf = (xf - wh.X0mean.to(xf)) @ wh.Twhiten.to(xf)
+        dl = dl + wh.jacobian_xz.to(xf)
+    return bonds, angles, torsions, xf, dl
+
+
 def run_block(block, xs, inverse, grad=False):
     """xs: list of torch CPU tensors -> (list, dlogp [B,1])"""
     if grad and not inverse and _name(block) in ("MixedCoordinateTransformation", "RelativeInternalCoordinateTransformation"):
-        raise NotImplementedError("differentiable xyz -> IC is not restated (the KL step only needs IC -> xyz)")
+        *outs, dl = xyz2ic_torch(block, *xs)
+        return list(outs), dl
     if grad and inverse and _name(block) in ("MixedCoordinateTransformation", "RelativeInternalCoordinateTransformation"):
         x, dl = ic2xyz_torch(block, *xs)
         return [x], dl
