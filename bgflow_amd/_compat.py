@@ -50,8 +50,9 @@ _MAP = {
     "distribution.sampling.mcmc": "sampling",
     "distribution.sampling.base": "distributions",
     "distribution.sampling.dataset": "training",
-    "distribution.sampling._mcmc": "permutation",
+    "distribution.sampling._mcmc": ("permutation", "analysis"),
     "distribution.sampling._mcmc.permutation": "permutation",
+    "distribution.sampling._mcmc.analysis": "analysis",
     "nn.training": "training",
     "nn.training.trainers": "training",
     "factory.tensor_info": "factory",

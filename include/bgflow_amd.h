@@ -1068,6 +1068,38 @@ int bgk_assign_particles(const float* x, int64_t ldx, int64_t B, int32_t n, int3
                          const int32_t* identical_host, int32_t m, float* y, int64_t ldy, int32_t* perm, float* cost,
                          int32_t* status, int32_t* permuted, void* stream);
 
+/* Bootstrap histograms: replaces the resampling loop of `free_energy_bootstrap` (`distribution/sampling/_mcmc/analysis.py:105-123`: per
+ * replicate an np.random.choice, two gathers and a weighted np.histogram on the host).  out[s, b] = sum of the weights of the draws of
+ * replicate s whose sample falls into bin b, for n_replicates replicates numbered replicate0 .. replicate0 + n_replicates - 1.
+ * Stage 1, once per call: every sample becomes one record {bin, weight} in `records` (8 bytes for f32 input: int32 bin, f32 weight; 16
+ * bytes for f64: int64 bin, f64 weight).  The bin is np.histogram(x, bins=edges)'s on the f64 edges (x widened to f64, the guess
+ * (x - e[0]) nb / (e[nb] - e[0]) corrected by f64 comparisons with the edges; half-open bins, the last one closed at e[nb]); values
+ * outside [e[0], e[nb]], NaN and +-inf get bin -1 and are counted in n_ignored[0]; without `w` the weight is 1; a sample in range whose
+ * weight is NaN, infinite or negative gets bin -1 and is counted in n_ignored[1] (numpy would carry a NaN weight into every later bin
+ * through its cumulative sum).  Stage 2, grid n_replicates x n_chunks: the source index of draw j of a replicate is
+ *     indices[s, j]  (int64 [n_replicates, n], n draws; an index outside [0, n) is skipped), or
+ *     segments[s] + j for j < segments[s + 1] - segments[s]  (int64 [n_replicates + 1]: the plain histogram of each segment), or
+ *     mulhi64(r, n) with r = 64 bits of Philox4x32-10 at counter (k low, k high, replicate, offset), k = j / 2 the 64-bit call index,
+ *     key = seed; words (o0, o1) = (low, high) serve the even draw of a call, (o2, o3) the odd one (n draws).
+ * The draws of a replicate depend on (seed, offset, its absolute number, n) alone -- not on n_chunks, the grid or the split of the
+ * replicates over calls; the multiply-high keeps an index's non-uniformity below n / 2^64.  Every block keeps f64 histograms in LDS
+ * (LDS f64 adds) and writes partial[s, c, :] (workspace of n_replicates * n_chunks * nb doubles); a last kernel sums the chunks in
+ * ascending order into out [n_replicates, nb].  No global float atomics, no waiting between blocks.
+ * Reproducibility: unweighted sums (sums of 1.0) are exact and bitwise reproducible; weighted sums depend on the arrival order of the
+ * LDS adds in their last bits, |sum - exact| <= m 2^-52 exact for a bin that received m draws.
+ * d, w: contiguous f32 (dtype BGK_HIST_F32) or f64 (BGK_HIST_F64), one code for both, aligned to their element; w, indices, segments,
+ * n_ignored may be NULL; edges: nb + 1 ascending f64 ON THE DEVICE; n_ignored: int64 [2] on the device, zeroed by the call.
+ * Envelope: 1 <= nb <= 4096 (BGK_EUNSUPPORTED beyond), 1 <= n_chunks <= 512, n >= 1, replicate0 >= 0, replicate0 + n_replicates <=
+ * 2^32, n_replicates * n_chunks < 2^31.  Argument checks come before any launch (BGK_EINVAL, text in bgk_last_error: null d / edges /
+ * records / partial / out, n < 1, another dtype code, nb < 1, n_chunks out of range, a bad replicate range, both indices and segments,
+ * a pointer not aligned to its element); n_replicates == 0 returns 0 without a launch. */
+#define BGK_HIST_F32 0
+#define BGK_HIST_F64 1
+int bgk_bootstrap_histogram(const void* d, const void* w, int64_t n, int32_t dtype, const double* edges, int32_t nb,
+                            int64_t n_replicates, int64_t replicate0, const int64_t* indices, const int64_t* segments, uint64_t seed,
+                            uint32_t offset, int32_t n_chunks, void* records, double* partial, double* out, int64_t* n_ignored,
+                            void* stream);
+
 /* One Linear layer (+ bias + activation) of a conditioner network on its own: y = act(x W^T + b).
  * Replaces one `Linear (, activation)` pair of DenseNet._layers (nn/dense.py:30-48) for the networks the one-launch coupling kernels do
  * not take (conditioner_factory.py:76-80 allows any `hidden` tuple: other depths, layers wider than 256; README.md:72-79's [1, 4, 1]
