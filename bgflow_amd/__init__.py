@@ -26,7 +26,8 @@ from .clipped import *       # noqa: F401,F403
 from .free_energy import *   # noqa: F401,F403
 from .permutation import *   # noqa: F401,F403
 from .analysis import free_energy_bootstrap, bootstrap_histogram   # noqa: F401
-from . import analysis, clipped, configs, dp, dynamics, factory, free_energy, particles, permutation, sampling, stochastic, training, utils      # noqa: F401
+from .umbrella import *      # noqa: F401,F403
+from . import analysis, clipped, configs, dp, dynamics, factory, free_energy, particles, permutation, sampling, stochastic, training, umbrella, utils      # noqa: F401
 
 __version__ = "0.1.0"
 

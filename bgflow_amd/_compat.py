@@ -50,9 +50,11 @@ _MAP = {
     "distribution.sampling.mcmc": "sampling",
     "distribution.sampling.base": "distributions",
     "distribution.sampling.dataset": "training",
-    "distribution.sampling._mcmc": ("permutation", "analysis"),
+    "distribution.sampling._mcmc": ("permutation", "analysis", "umbrella"),
     "distribution.sampling._mcmc.permutation": "permutation",
     "distribution.sampling._mcmc.analysis": "analysis",
+    "distribution.sampling._mcmc.umbrella_sampling": "umbrella",
+    "distribution.sampling._mcmc.metropolis": "umbrella",
     "nn.training": "training",
     "nn.training.trainers": "training",
     "factory.tensor_info": "factory",

@@ -26,8 +26,8 @@ Deviations from the reference:
 * a NaN weight drops its sample (tensor paths); numpy carries it into every later bin through its cumulative sum.
 * a tuple of arrays or tensors is bootstrapped by trajectory like a list; the reference takes a list only.
 * the tensor paths emit no divide-by-zero warning for empty bins, which are +inf as in numpy.
-* ``free_energy_bootstrap_2BGs``, ``UmbrellaSampling``, ``MetropolisGauss`` and the latent samplers are not part of this package
-  (DESIGN.md section 7)."""
+* ``free_energy_bootstrap_2BGs`` and the latent samplers are not part of this package; ``UmbrellaSampling`` and
+  ``MetropolisGauss`` live in ``bgflow_amd/umbrella.py``, whose ``mbar_weights`` are ``weights`` for the functions here."""
 import warnings
 
 import numpy as np

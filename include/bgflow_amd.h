@@ -1100,6 +1100,44 @@ int bgk_bootstrap_histogram(const void* d, const void* w, int64_t n, int32_t dty
                             uint32_t offset, int32_t n_chunks, void* records, double* partial, double* out, int64_t* n_ignored,
                             void* stream);
 
+/* Binless WHAM / MBAR over K harmonic umbrella windows on one scalar reaction coordinate: replaces what `UmbrellaSampling.mbar`
+ * (`distribution/sampling/_mcmc/umbrella_sampling.py:202-218`) hands to pyemma.thermo.estimate_umbrella_sampling(..., estimator="mbar"),
+ * a package the reference needs and this one does not.  Window k has the centre m_k, the reduced force constant kappa_k = k_k /
+ * temperature and N_k >= 1 samples; its bias is b_k(r) = kappa_k (r - m_k)^2, the reference's `bias_energy` (:44-45; pyemma's convention
+ * carries a factor 1/2, hence the 2.0 of :211, which is no part of this ABI).  The unknowns are the window free energies f [K].  One call
+ * enqueues n_steps ITERATIONS on the stream; an iteration is one reduction over all samples (block partials, then one workgroup that
+ * merges them) and one move of the solver, whose state lives in `f` and `record` on the device:
+ *     D_n  = log sum_l N_l exp(f_l - b_l(r_n))            for every sample n of every window
+ *     W_nk = N_k exp(f_k - b_k(r_n) - D_n)                in [0, 1] by construction: S_k = sum_n W_nk is a plain f64 sum
+ *     f_k <- f_k - (log S_k - log N_k), then every f_k minus the new f_0;   err = max_k |f_k_new - f_k_old|
+ * until err <= tolerance (status 0) or maximum_iterations iterations (status 1: the last iterate is the result); a NaN err is status 3
+ * (a NaN or infinite sample gets there).  Iterations after the record is done are empty launches, so the caller enqueues a chunk, reads
+ * the record back and repeats until record[0] == 1.  The bias is formed from r_n on the fly: no [K, N] array exists.
+ *   rc [n]: the samples of ALL windows, contiguous f32 (dtype BGK_MBAR_F32) or f64 (BGK_MBAR_F64), aligned to their element size only
+ *     (16-byte loads where the address allows, scalar head and tail); which window a sample came from does not enter; all arithmetic is
+ *     f64.  n = sum_k N_k >= K.
+ *   table [K, 3] f64 ON THE DEVICE: {m_k, kappa_k, log N_k} per window; duplicated centres are legal (forward_backward=True, :85-86).
+ *   n_blocks: stage-1 blocks, 1 .. 512; partial: workspace of n_blocks * K doubles.
+ *   f [K] f64 on the device: the start vector on the first call (zeros, or any guess), the iterate afterwards.
+ *   record: BGK_MBAR_RECORD_DOUBLES doubles, ZERO-FILLED by the caller before the first call of a solve, the same buffer on every later
+ *     call: {phase (0 iterate, 1 done), status, iterations done, err of the last iteration, K, n, 0, 0} (the last two pad the record to 64
+ *     bytes and are never written).
+ * Deterministic: the partition and every merge order are fixed by (pointer alignment, n, n_blocks); no atomics, no waiting between
+ * blocks; the same call gives the same bits.  Envelope: 1 <= K <= 256 (BGK_EUNSUPPORTED beyond).  Argument checks come before any launch
+ * (BGK_EINVAL, text in bgk_last_error: null pointer, n < 1, K < 1, n < K, another dtype code, a misaligned pointer, n_blocks out of
+ * range, maximum_iterations < 1, a negative or NaN tolerance, n_steps < 0); n_steps == 0 returns 0 without a launch.
+ *
+ * bgk_mbar_log_weights: one pass that writes out[n] = -D_n (f64 [n]) at the given f: the log weights that reweight every sample to the
+ * unbiased ensemble, up to one constant (the normalised stationary weights that :222 reads from pyemma are softmax(out)).  Same rc,
+ * dtype, table, K and checks as above. */
+#define BGK_MBAR_F32 0
+#define BGK_MBAR_F64 1
+#define BGK_MBAR_RECORD_DOUBLES 8
+int bgk_mbar_solve_steps(const void* rc, int64_t n, int32_t dtype, const double* table, int32_t K, int32_t n_blocks, double* partial,
+                         double* f, double* record, int32_t maximum_iterations, double tolerance, int32_t n_steps, void* stream);
+int bgk_mbar_log_weights(const void* rc, int64_t n, int32_t dtype, const double* table, int32_t K, const double* f, double* out,
+                         void* stream);
+
 /* One Linear layer (+ bias + activation) of a conditioner network on its own: y = act(x W^T + b).
  * Replaces one `Linear (, activation)` pair of DenseNet._layers (nn/dense.py:30-48) for the networks the one-launch coupling kernels do
  * not take (conditioner_factory.py:76-80 allows any `hidden` tuple: other depths, layers wider than 256; README.md:72-79's [1, 4, 1]
