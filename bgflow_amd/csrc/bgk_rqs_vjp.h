@@ -116,14 +116,32 @@ __device__ __forceinline__ BgkVjpBin bgk_rqs_vjp_bin(const BgkRqsCfg& c, int inv
     if (!inverse) {
         float dx = x - ch_i;
         float qa = dx * S + H_i * (delta - d0), qb = H_i * d0 - dx * S, qc = -delta * dx;
-        theta = (2.0f * qc) * bgk_vjp_rcp(-qb - __builtin_amdgcn_sqrtf(qb * qb - 4.0f * qa * qc));
+        /* For an input INSIDE its bin (0 <= dx <= H) the root lies in [0, 1]; f32 round-off takes it past an end where the bin is steep
+         * (delta = H / W of several hundred: a bin of minimal width under saturated parameters) and the input sits on the bin's end -- a
+         * clamped out-of-domain input, a knot: the discriminant, H^2 d1^2 there, cancels to 0 or below, theta = 1 + 1e-5, and behind it
+         * Q_th rounds to 0 (1 / Q_th: inf) and M = d1 + O(theta - 1) changes sign.  At theta = 1 exactly every term has its analytic
+         * value (Q_th = d1 / delta, M = d1): an input ON the bin's upper end (where every input clamped from above lands) takes it
+         * without the solve -- 1 - 1e-7 out of a 1-ulp reciprocal is as far from it as 1 + 1e-5 (dx = 0, the lower end, gives theta = 0
+         * through qc = 0 already).  Round-off only: an input OUTSIDE its bin (clamped to [left, right] but searched in [bottom, top],
+         * when the two differ: the first / last bin's rational function is extrapolated, as the forward kernels do) keeps the root the
+         * formula gives.  Selects, not min / max: a NaN input stays NaN. */
+        const bool inside = (dx >= 0.0f) & (dx <= H_i);
+        float disc = qb * qb - 4.0f * qa * qc;
+        disc = (inside & (disc < 0.0f)) ? 0.0f : disc;
+        theta = (2.0f * qc) * bgk_vjp_rcp(-qb - __builtin_amdgcn_sqrtf(disc));
+        theta = (inside & (theta < 0.0f)) ? 0.0f : ((inside & (theta > 1.0f)) ? 1.0f : theta);
+        theta = dx == H_i ? 1.0f : theta;
     } else {
         theta = (x - cw_i) * iW;
     }
     const float t = theta * (1.0f - theta), tp = 1.0f - 2.0f * theta, omt = 1.0f - theta;
     const float N = delta * theta * theta + d0 * t, den = delta + S * t;
     const float iden = bgk_vjp_rcp(den), iden2 = iden * iden;
-    const float Q = N * iden;
+    /* N == den on the bin's upper end (theta = 1: both are delta): the quotient is 1 there, not the 1 +- 6e-8 of a 1-ulp reciprocal.
+     * The cotangent of the knot below the bin is G_ch - G_H = A_th inv (Q - 1) (forward direction) -- exactly 0 on the end, where the
+     * output no longer depends on that knot -- and A_th inv is ~1e7 under parameters of scale 4: the rounding of Q alone put 0.96
+     * into height gradients whose row's largest true entry is 0.009 (every input clamped from above, tests/test_gpu_rqs_vjp_edges.py). */
+    const float Q = N == den ? 1.0f : N * iden;
     const float N_th = 2.0f * delta * theta + d0 * tp, den_th = S * tp;
     const float Q_th = (N_th * den - N * den_th) * iden2;
     const float Q_de = (theta * theta * den - N * (1.0f - 2.0f * t)) * iden2;
@@ -388,7 +406,13 @@ __device__ __forceinline__ float bgk_walk_grad(const BgkSoftmaxSet& q, int K, fl
                                                float G_c, float G_s, float* g) {
     const float gA = (idx >= 1) ? (G_c - G_s) : 0.0f, gB = (idx + 1 <= K - 1) ? G_s : 0.0f;
     const float w = sc * span;
-    const float dot = w * (gA * kp.below + gB * (kp.below + kp.p_bin));
+    /* sum_j p_j gp_j from the two values gp takes, ROUNDED as in the loop below (the register routine sums p_j * gp_j over the same
+     * rounded gp_j): under saturated parameters nearly all of the mass sits in one bin and gp - dot cancels to ~(1 - p) gp; the
+     * round-off of gp = w (gA + gB) -- G_s cancels in gA + gB, leaving an error of ulp(G_s) -- then cancels with it.  Formed from gA
+     * and gB separately (w (gA below + gB (below + p_bin))) the dot carried its own, uncorrelated round-off of that size: the walked
+     * form's median row error at parameter scale 12 was 4 - 6 x what it is since, the oracle's own (tests/test_gpu_rqs_vjp_edges.py). */
+    const float gp_lo = w * (gA + gB), gp_at = w * (0.0f + gB);
+    const float dot = gp_lo * kp.below + gp_at * kp.p_bin;
     float amax = 0.0f;
     for (int m = 0; m < K; ++m) {
         const float gp = w * ((m < idx ? gA : 0.0f) + (m <= idx ? gB : 0.0f));

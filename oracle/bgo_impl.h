@@ -225,7 +225,15 @@ void FN(bgo_rqs_backward)(const REAL* y, int64_t ldy, const REAL* params, int64_
             if (!bgflow_inverse) {
                 REAL dx = x - ch_i;
                 REAL a = dx * S + H_i * (delta - d0), bb = H_i * d0 - dx * S, c = -delta * dx;
-                theta = ((REAL)2 * c) / (-bb - R_SQRT(bb * bb - (REAL)4 * a * c));
+                /* an input inside its bin has its root in [0, 1]: kept there against round-off, 1 on the bin's upper end; an input
+                 * outside its bin is extrapolated as in the forward (bgk_rqs_vjp.h::bgk_rqs_vjp_bin; a NaN stays a NaN) */
+                const int inside = (dx >= (REAL)0) && (dx <= H_i);
+                REAL disc = bb * bb - (REAL)4 * a * c;
+                if (inside && disc < (REAL)0) disc = (REAL)0;
+                theta = ((REAL)2 * c) / (-bb - R_SQRT(disc));
+                if (inside && theta < (REAL)0) theta = (REAL)0;
+                if (inside && theta > (REAL)1) theta = (REAL)1;
+                if (dx == H_i) theta = (REAL)1;
             } else {
                 theta = (x - cw_i) / W_i;
             }
