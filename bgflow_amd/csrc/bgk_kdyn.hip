@@ -12,8 +12,8 @@
  * read once, and a whole RK4 / Euler integration (4 Nt or Nt evaluations) keeps the sample's state in LDS: x is read once, y and dlogp are
  * written once.
  *
- * Like bgk_pair.hip: one wave per workgroup, a tile of rows staged coalesced through LDS with the odd row stride S = (n d) | 1, ONE LANE PER
- * SAMPLE, the unordered pairs i < j in ascending order (F_ij = F_ji: half the exponentials of an ordered-pair loop), the contribution to
+ * Like bgk_pair.hip, by the rules of bgk_pair_tile.h: one wave per workgroup, a tile of rows staged coalesced through LDS at the odd row
+ * stride S, ONE LANE PER SAMPLE, the unordered pairs i < j in ascending order (F_ij = F_ji: half the exponentials of an ordered-pair loop), the contribution to
  * particle i in registers over the j loop and the one to particle j read-modify-written in the lane's own LDS row: no atomics, deterministic.
  * The divergence adds the terms of one i in f32 and the row sums in f64.  exp is the accurate one (dkern is a difference of close terms); when
  * every g_k underflows, s = 0 and A = Bq = 0 give F = c, dF = 0 -- no 0 / 0.
@@ -27,19 +27,19 @@
  *   g_w / g_c: per lane (LDS row / register) over the block's tiles, summed over the lanes in a fixed order into partial [grid, K + 1], finished
  *   in f64 in a fixed order by kdyn_finish_kernel.
  *
- * Envelope 2 <= n <= 64, 1 <= d <= 3, K <= 64, O <= 16.  Dynamic LDS <= 63,488 B (64 KiB less the static tables); rows per tile =
+ * Envelope: bgk_pair_tile.h's, and K <= 64, O <= 16.  Dynamic LDS <= 63,488 B (64 KiB less the static tables); rows per tile =
  * min(64, 63,488 / bytes per row), lanes beyond the rows only stage, store and take part in the time contraction:
  *   eval       2 S floats per row             n d = 192: 1,544 B, 41 rows      LJ13 (S = 39): 312 B, 64 rows
  *   backward   3 S + 2 (K | 1) floats         n d = 192, K = 64: 2,836 B, 22 rows
  *   integrate  4 S floats (x, stage input, force, RK4 sum)   n d = 192: 3,088 B, 20 rows;  LJ13: 624 B, 64 rows (39,936 B) */
 #include "bgk_common.h"
+#include "bgk_pair_tile.h"
 
 namespace {
 
-constexpr int KD_THREADS = 64;
-constexpr int KD_MAX_N = 64, KD_MAX_D = 3, KD_MAX_K = 64, KD_MAX_O = 16;
+constexpr int KD_MAX_K = 64, KD_MAX_O = 16;
 constexpr int KD_LDS_DYNAMIC = 63488;
-constexpr int KD_MAX_GRID = 256 * 16, KD_MAX_BWD_GRID = 1024;
+constexpr int KD_MAX_BWD_GRID = 1024;
 
 /* the per-kernel table of a launch: three float rows (768 B), not float4 (1,024 B) -- with the 64 B of tau the integration's LJ13 tile
  * (39,936 B dynamic) then stays below 40 KiB in all, so that four workgroups fit the 160 KiB of a CU */
@@ -54,20 +54,6 @@ struct KdArgs {
     const float* g_forces; const float* g_div; float* g_x; float* partial;      /* backward */
     double t_max; int n_steps, method, inverse; float* y; float* dlogp;         /* integrate */
 };
-
-__device__ __forceinline__ void kd_stage(const KdArgs& a, const float* src, int64_t b0, int rows, int S, float* dst) {
-    for (int i = threadIdx.x; i < rows * a.nd; i += KD_THREADS) {
-        const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * a.nd;
-        dst[r * S + c] = src[(b0 + r) * a.nd + c];
-    }
-}
-
-__device__ __forceinline__ void kd_store(const KdArgs& a, float* dst, int64_t b0, int rows, int S, const float* src) {
-    for (int i = threadIdx.x; i < rows * a.nd; i += KD_THREADS) {
-        const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * a.nd;
-        dst[(b0 + r) * a.nd + c] = src[r * S + c];
-    }
-}
 
 /* all 64 lanes: s_par = (mu_k, exp(nlg_k)^2, w_k(t)) for k < K; returns c(t) in every lane.  Barriers inside: the callers reach it
  * in uniform control flow. */
@@ -140,7 +126,7 @@ __device__ __forceinline__ float kd_eval_row(const float* xr, float* fr, int n, 
 }
 
 template <int D>
-__global__ __launch_bounds__(KD_THREADS) void kdyn_eval_kernel(KdArgs a) {
+__global__ __launch_bounds__(BGK_TILE_THREADS) void kdyn_eval_kernel(KdArgs a) {
     extern __shared__ float s_mem[];
     __shared__ KdPar s_par;
     __shared__ float s_tau[KD_MAX_O];
@@ -152,20 +138,20 @@ __global__ __launch_bounds__(KD_THREADS) void kdyn_eval_kernel(KdArgs a) {
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t b0 = tile * a.rows;
         const int rows = (int)((a.B - b0) < a.rows ? (a.B - b0) : a.rows);
-        kd_stage(a, a.x, b0, rows, S, s_x);
+        tile_stage(a.x, b0, rows, a.nd, a.magic, s_x);
         __syncthreads();
         if (tid < rows) {
             if (a.div) a.div[b0 + tid] = kd_eval_row<D, true>(s_x + tid * S, s_f + tid * S, a.n, a.K, s_par, c);
             else kd_eval_row<D, false>(s_x + tid * S, s_f + tid * S, a.n, a.K, s_par, c);
         }
         __syncthreads();
-        kd_store(a, a.forces, b0, rows, S, s_f);
+        tile_store(a.forces, b0, rows, a.nd, a.magic, s_f);
         __syncthreads();
     }
 }
 
 template <int D>
-__global__ __launch_bounds__(KD_THREADS) void kdyn_integrate_kernel(KdArgs a) {
+__global__ __launch_bounds__(BGK_TILE_THREADS) void kdyn_integrate_kernel(KdArgs a) {
     extern __shared__ float s_mem[];
     __shared__ KdPar s_par;
     __shared__ float s_tau[KD_MAX_O];
@@ -181,7 +167,7 @@ __global__ __launch_bounds__(KD_THREADS) void kdyn_integrate_kernel(KdArgs a) {
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t b0 = tile * a.rows;
         const int rows = (int)((a.B - b0) < a.rows ? (a.B - b0) : a.rows);
-        kd_stage(a, a.x, b0, rows, S, s_mem);
+        tile_stage(a.x, b0, rows, nd, a.magic, s_mem);
         float lp = 0.0f, lacc = 0.0f;
         for (int step = 0; step < a.n_steps; ++step) {
             for (int st = 0; st < n_stages; ++st) {
@@ -208,17 +194,17 @@ __global__ __launch_bounds__(KD_THREADS) void kdyn_integrate_kernel(KdArgs a) {
         }
         if (tid < rows) a.dlogp[b0 + tid] = lp;
         __syncthreads();
-        kd_store(a, a.y, b0, rows, S, s_mem);
+        tile_store(a.y, b0, rows, nd, a.magic, s_mem);
         __syncthreads();
     }
 }
 
 template <int D>
-__global__ __launch_bounds__(KD_THREADS) void kdyn_eval_bwd_kernel(KdArgs a) {
+__global__ __launch_bounds__(BGK_TILE_THREADS) void kdyn_eval_bwd_kernel(KdArgs a) {
     extern __shared__ float s_mem[];
     __shared__ KdPar s_par;
     __shared__ float s_tau[KD_MAX_O];
-    __shared__ float s_red[KD_THREADS];
+    __shared__ float s_red[BGK_TILE_THREADS];
     const int tid = threadIdx.x, S = a.nd | 1, K = a.K, KS = a.K | 1, n = a.n;
     float* s_x = s_mem;
     float* s_gf = s_x + a.rows * S;
@@ -232,8 +218,8 @@ __global__ __launch_bounds__(KD_THREADS) void kdyn_eval_bwd_kernel(KdArgs a) {
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t b0 = tile * a.rows;
         const int rows = (int)((a.B - b0) < a.rows ? (a.B - b0) : a.rows);
-        kd_stage(a, a.x, b0, rows, S, s_x);
-        kd_stage(a, a.g_forces, b0, rows, S, s_gf);
+        tile_stage(a.x, b0, rows, a.nd, a.magic, s_x);
+        tile_stage(a.g_forces, b0, rows, a.nd, a.magic, s_gf);
         __syncthreads();
         if (tid < rows) {
             const float* xr = s_x + tid * S;
@@ -288,7 +274,7 @@ __global__ __launch_bounds__(KD_THREADS) void kdyn_eval_bwd_kernel(KdArgs a) {
             }
         }
         __syncthreads();
-        kd_store(a, a.g_x, b0, rows, S, s_gx);
+        tile_store(a.g_x, b0, rows, a.nd, a.magic, s_gx);
         __syncthreads();
     }
     /* block partials in a fixed order over the lanes */
@@ -300,24 +286,24 @@ __global__ __launch_bounds__(KD_THREADS) void kdyn_eval_bwd_kernel(KdArgs a) {
         for (int l = 0; l < a.rows; ++l) v += s_gw[l * KS + tid];
         out[tid] = v;
     }
-    if (tid == KD_THREADS - 1) {
+    if (tid == BGK_TILE_THREADS - 1) {
         float v = 0.0f;
-        for (int l = 0; l < KD_THREADS; ++l) v += s_red[l];
+        for (int l = 0; l < BGK_TILE_THREADS; ++l) v += s_red[l];
         out[K] = v;
     }
 }
 
 /* out[k] = sum over the blocks' partials [nblk, K + 1] in f64, a fixed order: block k of the grid, 64 strided sums, then lane 0 */
-__global__ __launch_bounds__(KD_THREADS) void kdyn_finish_kernel(const float* partial, int nblk, int K1, float* out) {
-    __shared__ double s_sum[KD_THREADS];
+__global__ __launch_bounds__(BGK_TILE_THREADS) void kdyn_finish_kernel(const float* partial, int nblk, int K1, float* out) {
+    __shared__ double s_sum[BGK_TILE_THREADS];
     const int k = blockIdx.x;
     double v = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += KD_THREADS) v += (double)partial[(int64_t)b * K1 + k];
+    for (int b = threadIdx.x; b < nblk; b += BGK_TILE_THREADS) v += (double)partial[(int64_t)b * K1 + k];
     s_sum[threadIdx.x] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
         double t = 0.0;
-        for (int l = 0; l < KD_THREADS; ++l) t += s_sum[l];
+        for (int l = 0; l < BGK_TILE_THREADS; ++l) t += s_sum[l];
         out[k] = (float)t;
     }
 }
@@ -331,36 +317,23 @@ struct BgkKdynCall {
 
 int kd_common(const BgkKdynCall& c, KdArgs* a) {
     BGK_CHECK_ARG(c.B >= 0, "%s: bad batch size", c.what);
-    if (!(c.n_particles >= 2 && c.n_particles <= KD_MAX_N && c.n_dims >= 1 && c.n_dims <= KD_MAX_D && c.n_kernels >= 1 &&
+    if (!(c.n_particles >= 2 && c.n_particles <= BGK_TILE_MAX_N && c.n_dims >= 1 && c.n_dims <= BGK_TILE_MAX_D && c.n_kernels >= 1 &&
           c.n_kernels <= KD_MAX_K && c.n_out >= 1 && c.n_out <= KD_MAX_O)) {
         bgk_set_error("%s: %d particles in %d dimensions with %d distance and %d time kernels are outside the kernel's envelope "
                       "(2..%d particles, 1..%d dimensions, 1..%d and 1..%d kernels)", c.what, c.n_particles, c.n_dims, c.n_kernels, c.n_out,
-                      KD_MAX_N, KD_MAX_D, KD_MAX_K, KD_MAX_O);
+                      BGK_TILE_MAX_N, BGK_TILE_MAX_D, KD_MAX_K, KD_MAX_O);
         return BGK_EUNSUPPORTED;
     }
     BGK_CHECK_ARG(c.mus && c.neg_log_gammas && c.weights && c.bias && c.importance, "%s: null parameter tensor", c.what);
     BGK_CHECK_ARG((c.mus_time != nullptr) == (c.neg_log_gammas_time != nullptr), "%s: mus_time and neg_log_gammas_time go together", c.what);
     BGK_CHECK_ARG(c.mus_time || c.n_out == 1, "%s: without time kernels n_out is 1", c.what);
     a->x = c.x; a->B = c.B; a->n = c.n_particles; a->nd = c.n_particles * c.n_dims; a->K = c.n_kernels; a->O = c.n_out;
-    a->magic = (uint32_t)(((1ull << 32) + (uint64_t)a->nd - 1) / (uint64_t)a->nd);
+    a->magic = tile_magic(a->nd);
     a->mus = c.mus; a->nlg = c.neg_log_gammas; a->W = c.weights; a->bias = c.bias; a->imp = c.importance;
     a->mus_t = c.mus_time; a->nlg_t = c.neg_log_gammas_time;
-    const int per_row = c.floats_per_row * (int)sizeof(float);
-    a->rows = KD_LDS_DYNAMIC / per_row < KD_THREADS ? KD_LDS_DYNAMIC / per_row : KD_THREADS;
+    a->rows = rows_within(KD_LDS_DYNAMIC, c.floats_per_row * (int)sizeof(float));
     return 0;
 }
-
-int kd_grid(const KdArgs& a, int cap) {
-    const int64_t n_tiles = (a.B + a.rows - 1) / a.rows;
-    return (int)(n_tiles < cap ? n_tiles : cap);
-}
-
-#define KD_LAUNCH(kernel, d, grid, lds, s, a)                                                                    \
-    do {                                                                                                         \
-        if ((d) == 1) hipLaunchKernelGGL((kernel<1>), dim3(grid), dim3(KD_THREADS), lds, s, a);                  \
-        else if ((d) == 2) hipLaunchKernelGGL((kernel<2>), dim3(grid), dim3(KD_THREADS), lds, s, a);             \
-        else hipLaunchKernelGGL((kernel<3>), dim3(grid), dim3(KD_THREADS), lds, s, a);                           \
-    } while (0)
 
 }  // namespace
 
@@ -377,7 +350,7 @@ extern "C" int bgk_kdyn_eval(const float* x, int64_t B, int32_t n_particles, int
     BGK_CHECK_ARG(x && forces, "bgk_kdyn_eval: null tensor");
     a.t = t; a.forces = forces; a.div = divergence;
     const size_t lds = (size_t)a.rows * c.floats_per_row * sizeof(float);
-    KD_LAUNCH(kdyn_eval_kernel, n_dims, kd_grid(a, KD_MAX_GRID), lds, (hipStream_t)stream, a);
+    tile_dispatch_d(n_dims, [&](auto D) { tile_launch(kdyn_eval_kernel<D()>, tile_grid(B, a.rows), lds, (hipStream_t)stream, a); });
     return bgk_launch_status(c.what);
 }
 
@@ -400,11 +373,11 @@ extern "C" int bgk_kdyn_eval_backward(const float* x, int64_t B, int32_t n_parti
     BGK_CHECK_ARG(x && g_forces && g_x, "bgk_kdyn_eval_backward: null tensor");
     a.t = t; a.g_forces = g_forces; a.g_div = g_div; a.g_x = g_x; a.partial = partial;
     const size_t lds = (size_t)a.rows * c.floats_per_row * sizeof(float);
-    const int grid = kd_grid(a, nblk < KD_MAX_BWD_GRID ? nblk : KD_MAX_BWD_GRID);
-    KD_LAUNCH(kdyn_eval_bwd_kernel, n_dims, grid, lds, s, a);
+    const int grid = tile_grid(B, a.rows, nblk < KD_MAX_BWD_GRID ? nblk : KD_MAX_BWD_GRID);
+    tile_dispatch_d(n_dims, [&](auto D) { tile_launch(kdyn_eval_bwd_kernel<D()>, grid, lds, s, a); });
     const int st2 = bgk_launch_status(c.what);
     if (st2) return st2;
-    hipLaunchKernelGGL(kdyn_finish_kernel, dim3(n_kernels + 1), dim3(KD_THREADS), 0, s, partial, grid, n_kernels + 1, g_wc);
+    hipLaunchKernelGGL(kdyn_finish_kernel, dim3(n_kernels + 1), dim3(BGK_TILE_THREADS), 0, s, partial, grid, n_kernels + 1, g_wc);
     return bgk_launch_status(c.what);
 }
 
@@ -422,6 +395,6 @@ extern "C" int bgk_kdyn_integrate(const float* x, int64_t B, int32_t n_particles
     BGK_CHECK_ARG(x && y && dlogp, "bgk_kdyn_integrate: null tensor");
     a.t_max = t_max; a.n_steps = n_steps; a.method = method; a.inverse = inverse != 0; a.y = y; a.dlogp = dlogp;
     const size_t lds = (size_t)a.rows * c.floats_per_row * sizeof(float);
-    KD_LAUNCH(kdyn_integrate_kernel, n_dims, kd_grid(a, KD_MAX_GRID), lds, (hipStream_t)stream, a);
+    tile_dispatch_d(n_dims, [&](auto D) { tile_launch(kdyn_integrate_kernel<D()>, tile_grid(B, a.rows), lds, (hipStream_t)stream, a); });
     return bgk_launch_status(c.what);
 }

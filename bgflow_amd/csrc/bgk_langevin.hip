@@ -8,9 +8,9 @@
  * In stock ops a step is a randn (two), two force calls (autograd through the energy) and about ten elementwise ops and reductions over a
  * state of n d <= 192 floats per sample; here the state never leaves LDS between the first and the last step.
  *
- * Like bgk_mcmc.hip: one wave per workgroup, ONE LANE PER SAMPLE, a tile of rows staged coalesced through LDS with the odd row stride
- * S = (n d) | 1 (lane r reads word r S + k: distinct banks within a 32-lane group), the steps in lockstep across the wave, the final q / v
- * as coalesced tile stores, no atomics, a fixed summation order.  The scalars (h, sqrt(2 h), c1, ...) are formed in f64 on the host and
+ * Like bgk_mcmc.hip, by the rules of bgk_pair_tile.h: one wave per workgroup, ONE LANE PER SAMPLE, a tile of rows staged coalesced through
+ * LDS at the odd row stride S, the steps in lockstep across the wave, the final q / v as coalesced tile stores, no atomics, a fixed
+ * summation order.  The scalars (h, sqrt(2 h), c1, ...) are formed in f64 on the host and
  * rounded to f32 once, as torch does with a python number that meets an f32 tensor.
  *
  * Force: bgk_pair_row_gradient of bgk_pair_terms.h -- the code of pair_energy_bwd_kernel -- into the lane's own row of a force tile; the
@@ -59,22 +59,18 @@
  *                 n d = 192 (S = 193)       LJ13, n d = 39 (S = 39)     DW4, n d = 8 (S = 9)
  *   backward      16 rows, 61,760 B         64 rows, 49,920 B           64 rows, 11,520 B
  *
- * Envelope 2 <= n <= 64, 1 <= d <= 3. */
+ * Envelope: bgk_pair_tile.h. */
 #include "bgk_common.h"
 #include "bgk_pair_terms.h"
 #include "bgk_philox.h"
 
 namespace {
 
-constexpr int LG_THREADS = 64;
-constexpr int LG_MAX_N = 64, LG_MAX_D = 3;
 constexpr int LG_LDS_DYNAMIC = 63488;
-constexpr int LG_MAX_GRID = 256 * 16;
 
 struct LgArgs {
     float* q; float* v; int64_t B, row0;
-    int n, nd, rows; uint32_t magic;
-    float p0, p1, p2, p3, osc;
+    BgkPairTarget t; int rows;
     float h, sq2h, c1, c2, gm, fac1, fac2; int n_steps;
     const float* w1; const float* w2;
     uint32_t seed_lo, seed_hi, offset;
@@ -96,17 +92,16 @@ __device__ __forceinline__ void lg_normal4(const float* row, int nd, int cb, uin
 }
 
 template <int D, int KIND, bool LANGEVIN, bool RECORD>
-__global__ __launch_bounds__(LG_THREADS) void pair_langevin_kernel(LgArgs a) {
+__global__ __launch_bounds__(BGK_TILE_THREADS) void pair_langevin_kernel(LgArgs a) {
     extern __shared__ float s_mem[];
-    const int tid = threadIdx.x, n = a.n, nd = a.nd, S = a.nd | 1;
+    const int tid = threadIdx.x, nd = a.t.nd, S = nd | 1;
     const int T = a.rows * S;                                          /* words of one tile */
-    const float rm2 = a.p1 * a.p1, c12 = -12.0f * a.p0 / rm2;
     const int64_t n_tiles = (a.B + a.rows - 1) / a.rows;
     for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
         const int64_t b0 = t * a.rows;
         const int rows = (int)((a.B - b0) < a.rows ? (a.B - b0) : a.rows);
-        for (int i = tid; i < rows * nd; i += LG_THREADS) {
-            const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * nd;
+        for (int i = tid; i < rows * nd; i += BGK_TILE_THREADS) {     /* tile_stage of q and v in one pass: one row split for both */
+            const int r = (int)__umulhi((unsigned)i, a.t.magic), c = i - r * nd;
             s_mem[r * S + c] = a.q[(b0 + r) * nd + c];
             if (LANGEVIN) s_mem[T + r * S + c] = a.v[(b0 + r) * nd + c];
         }
@@ -118,8 +113,7 @@ __global__ __launch_bounds__(LG_THREADS) void pair_langevin_kernel(LgArgs a) {
         /* tile offsets, uniform over the wave.  Brownian: A, B, Fa, Fb; Langevin: Q (0), V (T), F, G, and T at 4 T */
         int ox = 0, oy = T, of = 2 * T, og = 3 * T;
         double dw = 0.0;
-        if (active)
-            bgk_pair_row_gradient<D, KIND>(s_mem + ox + tid * S, s_mem + of + tid * S, n, a.p0, a.p1, a.p3, rm2, c12, a.osc);
+        if (active) bgk_pair_row_gradient<D, KIND>(s_mem + ox + tid * S, s_mem + of + tid * S, a.t);
         for (int step = 0; step < a.n_steps; ++step) {
             if (active) {
                 const uint32_t off = a.offset + (uint32_t)step;
@@ -144,7 +138,7 @@ __global__ __launch_bounds__(LG_THREADS) void pair_langevin_kernel(LgArgs a) {
                             }
                         }
                     }
-                    bgk_pair_row_gradient<D, KIND>(xb, gg, n, a.p0, a.p1, a.p3, rm2, c12, a.osc);
+                    bgk_pair_row_gradient<D, KIND>(xb, gg, a.t);
                     for (int c = 0; c < nd; ++c) {
                         const float wb = (xa[c] - a.h * (-gg[c])) / a.sq2h, w = gf[c];
                         sum += (double)(w * w - wb * wb);
@@ -167,7 +161,7 @@ __global__ __launch_bounds__(LG_THREADS) void pair_langevin_kernel(LgArgs a) {
                             }
                         }
                     }
-                    bgk_pair_row_gradient<D, KIND>(qr, gg, n, a.p0, a.p1, a.p3, rm2, c12, a.osc);
+                    bgk_pair_row_gradient<D, KIND>(qr, gg, a.t);
                     for (int cb = 0; 4 * cb < nd; ++cb) {
                         float w[4];
                         lg_normal4(n2, nd, cb, r_lo, r_hi, 1u, off, a.seed_lo, a.seed_hi, w);
@@ -189,8 +183,8 @@ __global__ __launch_bounds__(LG_THREADS) void pair_langevin_kernel(LgArgs a) {
                 __syncthreads();
                 const int64_t f0 = ((int64_t)step * a.B + b0) * nd;
                 const int oq = LANGEVIN ? 0 : oy;
-                for (int i = tid; i < rows * nd; i += LG_THREADS) {
-                    const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * nd;
+                for (int i = tid; i < rows * nd; i += BGK_TILE_THREADS) {
+                    const int r = (int)__umulhi((unsigned)i, a.t.magic), c = i - r * nd;
                     a.traj_q[f0 + i] = s_mem[oq + r * S + c];
                     if (LANGEVIN) a.traj_v[f0 + i] = s_mem[T + r * S + c];
                 }
@@ -200,8 +194,8 @@ __global__ __launch_bounds__(LG_THREADS) void pair_langevin_kernel(LgArgs a) {
             const int sf = of; of = og; og = sf;
         }
         __syncthreads();
-        for (int i = tid; i < rows * nd; i += LG_THREADS) {
-            const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * nd;
+        for (int i = tid; i < rows * nd; i += BGK_TILE_THREADS) {     /* tile_store of q and v in one pass */
+            const int r = (int)__umulhi((unsigned)i, a.t.magic), c = i - r * nd;
             a.q[(b0 + r) * nd + c] = s_mem[ox + r * S + c];
             if (LANGEVIN) a.v[(b0 + r) * nd + c] = s_mem[T + r * S + c];
         }
@@ -210,51 +204,22 @@ __global__ __launch_bounds__(LG_THREADS) void pair_langevin_kernel(LgArgs a) {
     }
 }
 
-template <int KIND, bool LANGEVIN, bool RECORD>
-void launch_langevin_d(int d, int grid, size_t lds, hipStream_t s, const LgArgs& a) {
-    if (d == 1) hipLaunchKernelGGL((pair_langevin_kernel<1, KIND, LANGEVIN, RECORD>), dim3(grid), dim3(LG_THREADS), lds, s, a);
-    else if (d == 2) hipLaunchKernelGGL((pair_langevin_kernel<2, KIND, LANGEVIN, RECORD>), dim3(grid), dim3(LG_THREADS), lds, s, a);
-    else hipLaunchKernelGGL((pair_langevin_kernel<3, KIND, LANGEVIN, RECORD>), dim3(grid), dim3(LG_THREADS), lds, s, a);
-}
-
-template <int KIND>
-void launch_langevin(bool langevin, bool record, int d, int grid, size_t lds, hipStream_t s, const LgArgs& a) {
-    if (langevin) { if (record) launch_langevin_d<KIND, true, true>(d, grid, lds, s, a); else launch_langevin_d<KIND, true, false>(d, grid, lds, s, a); }
-    else { if (record) launch_langevin_d<KIND, false, true>(d, grid, lds, s, a); else launch_langevin_d<KIND, false, false>(d, grid, lds, s, a); }
-}
-
 /* ---- the adjoint sweep over a recorded segment (header: "Backward") ---- */
 struct LbArgs {
     const float* q0; const float* v0; const float* traj_q; const float* traj_v; int64_t B, row0;
-    int n, nd, rows; uint32_t magic;
-    float p0, p1, p2, p3, osc;
+    BgkPairTarget t; int rows;
     float h, sq2h, c1, c2, omg, fac2; int n_steps;
     const float* w1; const float* w2;
     uint32_t seed_lo, seed_hi, offset;
     const float* g_dW; float* gq; float* gv; float* carry; int first;
 };
 
-/* rows [b0, b0 + rows) of a contiguous [B, n d] tensor into / out of a tile (row stride S), every lane of the wave */
-__device__ __forceinline__ void lb_stage(const LbArgs& a, const float* src, int64_t b0, int rows, int S, float* tile) {
-    for (int i = threadIdx.x; i < rows * a.nd; i += LG_THREADS) {
-        const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * a.nd;
-        tile[r * S + c] = src[b0 * a.nd + i];
-    }
-}
-
-__device__ __forceinline__ void lb_store(const LbArgs& a, float* dst, int64_t b0, int rows, int S, const float* tile) {
-    for (int i = threadIdx.x; i < rows * a.nd; i += LG_THREADS) {
-        const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * a.nd;
-        dst[b0 * a.nd + i] = tile[r * S + c];
-    }
-}
-
 template <int D, int KIND, bool LANGEVIN>
-__global__ __launch_bounds__(LG_THREADS) void pair_langevin_bwd_kernel(LbArgs a) {
+__global__ __launch_bounds__(BGK_TILE_THREADS) void pair_langevin_bwd_kernel(LbArgs a) {
     extern __shared__ float s_mem[];
-    const int tid = threadIdx.x, n = a.n, nd = a.nd, S = a.nd | 1;
+    const int tid = threadIdx.x, nd = a.t.nd, S = nd | 1;
     const int T = a.rows * S;
-    const float rm2 = a.p1 * a.p1, c12 = -12.0f * a.p0 / rm2;
+    const uint32_t magic = a.t.magic;
     const int64_t n_tiles = (a.B + a.rows - 1) / a.rows;
     const int64_t frame = a.B * (int64_t)nd;
     float* s_x = s_mem;                 /* the state q_j; Langevin: then v_(j-1) */
@@ -265,9 +230,9 @@ __global__ __launch_bounds__(LG_THREADS) void pair_langevin_bwd_kernel(LbArgs a)
     for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
         const int64_t b0 = t * a.rows;
         const int rows = (int)((a.B - b0) < a.rows ? (a.B - b0) : a.rows);
-        lb_stage(a, a.gq, b0, rows, S, s_gq);
-        lb_stage(a, a.carry, b0, rows, S, s_gc);
-        if (LANGEVIN) lb_stage(a, a.gv, b0, rows, S, s_gv);
+        tile_stage(a.gq, b0, rows, nd, magic, s_gq);
+        tile_stage(a.carry, b0, rows, nd, magic, s_gc);
+        if (LANGEVIN) tile_stage(a.gv, b0, rows, nd, magic, s_gv);
         const bool active = tid < rows;
         const int64_t b = b0 + (active ? tid : 0);
         const uint64_t grow = (uint64_t)(a.row0 + b);
@@ -280,10 +245,10 @@ __global__ __launch_bounds__(LG_THREADS) void pair_langevin_bwd_kernel(LbArgs a)
         float* gc = s_gc + tid * S;
         for (int j = a.n_steps; j >= (a.first ? 0 : 1); --j) {       /* state j of the segment: 0 the state before it, j > 0 frame j - 1 */
             __syncthreads();
-            lb_stage(a, j > 0 ? a.traj_q + (int64_t)(j - 1) * frame : a.q0, b0, rows, S, s_x);
+            tile_stage(j > 0 ? a.traj_q + (int64_t)(j - 1) * frame : a.q0, b0, rows, nd, magic, s_x);
             if (j > 0) {
-                if (LANGEVIN) lb_stage(a, a.traj_v + (int64_t)(j - 1) * frame, b0, rows, S, s_y);
-                else lb_stage(a, j > 1 ? a.traj_q + (int64_t)(j - 2) * frame : a.q0, b0, rows, S, s_y);
+                if (LANGEVIN) tile_stage(a.traj_v + (int64_t)(j - 1) * frame, b0, rows, nd, magic, s_y);
+                else tile_stage(j > 1 ? a.traj_q + (int64_t)(j - 2) * frame : a.q0, b0, rows, nd, magic, s_y);
             }
             __syncthreads();
             const uint32_t off = a.offset + (uint32_t)(j - 1);         /* the step that led to state j */
@@ -292,14 +257,14 @@ __global__ __launch_bounds__(LG_THREADS) void pair_langevin_bwd_kernel(LbArgs a)
             if (active) {
                 if (!LANGEVIN) {
                     if (j > 0) {
-                        bgk_pair_row_gradient<D, KIND>(xr, gv, n, a.p0, a.p1, a.p3, rm2, c12, a.osc);
+                        bgk_pair_row_gradient<D, KIND>(xr, gv, a.t);
                         for (int c = 0; c < nd; ++c) {
                             const float wb = ((yr[c] - xr[c]) - a.h * (-gv[c])) / a.sq2h;     /* the forward's w_ of step j - 1 */
                             const float am = -(gamma * wb) / a.sq2h;                          /* a_(j-1) */
                             gv[c] = am; gc[c] = gc[c] - am;
                         }
                     }
-                    bgk_pair_row_hvp<D, KIND, false>(xr, gc, nullptr, yr, n, a.p0, a.p1, a.p3, rm2, c12, a.osc);
+                    bgk_pair_row_hvp<D, KIND, false>(xr, gc, nullptr, yr, a.t);
                     for (int c = 0; c < nd; ++c) {
                         const float am = j > 0 ? gv[c] : 0.0f;
                         const float lam = (gq[c] - am) - a.h * yr[c];
@@ -322,13 +287,13 @@ __global__ __launch_bounds__(LG_THREADS) void pair_langevin_bwd_kernel(LbArgs a)
                     } else {
                         for (int c = 0; c < nd; ++c) gc[c] = a.c1 * gc[c];
                     }
-                    bgk_pair_row_hvp<D, KIND, false>(xr, gc, nullptr, yr, n, a.p0, a.p1, a.p3, rm2, c12, a.osc);
+                    bgk_pair_row_hvp<D, KIND, false>(xr, gc, nullptr, yr, a.t);
                     for (int c = 0; c < nd; ++c) gq[c] -= yr[c];
                 }
             }
             if (LANGEVIN && j > 0) {
                 __syncthreads();
-                lb_stage(a, j > 1 ? a.traj_v + (int64_t)(j - 2) * frame : a.v0, b0, rows, S, s_x);
+                tile_stage(j > 1 ? a.traj_v + (int64_t)(j - 2) * frame : a.v0, b0, rows, nd, magic, s_x);
                 __syncthreads();
                 if (active) {
                     for (int cb = 0; 4 * cb < nd; ++cb) {
@@ -347,82 +312,64 @@ __global__ __launch_bounds__(LG_THREADS) void pair_langevin_bwd_kernel(LbArgs a)
             }
         }
         __syncthreads();
-        lb_store(a, a.gq, b0, rows, S, s_gq);
-        lb_store(a, a.carry, b0, rows, S, s_gc);
-        if (LANGEVIN) lb_store(a, a.gv, b0, rows, S, s_gv);
+        tile_store(a.gq, b0, rows, nd, magic, s_gq);
+        tile_store(a.carry, b0, rows, nd, magic, s_gc);
+        if (LANGEVIN) tile_store(a.gv, b0, rows, nd, magic, s_gv);
         __syncthreads();
     }
 }
 
-template <int KIND, bool LANGEVIN>
-void launch_langevin_bwd_d(int d, int grid, size_t lds, hipStream_t s, const LbArgs& a) {
-    if (d == 1) hipLaunchKernelGGL((pair_langevin_bwd_kernel<1, KIND, LANGEVIN>), dim3(grid), dim3(LG_THREADS), lds, s, a);
-    else if (d == 2) hipLaunchKernelGGL((pair_langevin_bwd_kernel<2, KIND, LANGEVIN>), dim3(grid), dim3(LG_THREADS), lds, s, a);
-    else hipLaunchKernelGGL((pair_langevin_bwd_kernel<3, KIND, LANGEVIN>), dim3(grid), dim3(LG_THREADS), lds, s, a);
-}
+/* what the three entries share, in their order: the target as the entry names it (bgk_pair_spec), the integrator and the noise */
+struct BgkLangevinCall {
+    BgkPairSpec spec;
+    int64_t B;
+    double stepsize, mass, gamma, kT; int32_t n_steps;
+    const float* w1; const float* w2; uint64_t seed; uint32_t offset; int64_t row0;
+    void* stream;
+};
 
-template <int KIND>
-void launch_langevin_bwd(bool langevin, int d, int grid, size_t lds, hipStream_t s, const LbArgs& a) {
-    if (langevin) launch_langevin_bwd_d<KIND, true>(d, grid, lds, s, a);
-    else launch_langevin_bwd_d<KIND, false>(d, grid, lds, s, a);
-}
-
-/* the checks every entry shares */
-int langevin_check(const char* what, int64_t B, int64_t row0, int32_t n_steps, int32_t n_particles, int32_t n_dims, int32_t kind,
-                   double stepsize, double mass, double gamma, double kT, const float* w1, const float* w2, bool langevin) {
-    BGK_CHECK_ARG(B >= 0 && row0 >= 0 && n_steps >= 0, "%s: bad batch size / row0 / n_steps", what);
-    BGK_CHECK_ARG(kind >= 0 && kind <= 2, "%s: kind %d (0 Lennard-Jones, 1 multi-double-well, 2 mean-free normal)", what, kind);
-    if (!(n_particles >= 2 && n_particles <= LG_MAX_N && n_dims >= 1 && n_dims <= LG_MAX_D)) {
-        bgk_set_error("%s: %d particles in %d dimensions are outside the kernel's envelope (2..%d particles, 1..%d dimensions)", what,
-                      n_particles, n_dims, LG_MAX_N, LG_MAX_D);
-        return BGK_EUNSUPPORTED;
-    }
-    BGK_CHECK_ARG(stepsize > 0.0 && stepsize < INFINITY, "%s: the step size must be positive and finite", what);
-    BGK_CHECK_ARG(mass > 0.0 && gamma >= 0.0 && kT > 0.0, "%s: mass and kT must be positive, gamma not negative", what);
-    BGK_CHECK_ARG(!w2 || (w1 && langevin), "%s: w2 goes with w1 and with velocities", what);
-    BGK_CHECK_ARG(!(langevin && w1) || w2, "%s: with velocities w1 and w2 go together", what);
+/* the checks every entry shares; fills *t */
+int langevin_check(const BgkLangevinCall& c, bool langevin, BgkPairTarget* t) {
+    const char* what = c.spec.what;
+    BGK_CHECK_ARG(c.B >= 0 && c.row0 >= 0 && c.n_steps >= 0, "%s: bad batch size / row0 / n_steps", what);
+    const int st = bgk_pair_target(c.spec, t);
+    if (st) return st;
+    BGK_CHECK_ARG(c.stepsize > 0.0 && c.stepsize < INFINITY, "%s: the step size must be positive and finite", what);
+    BGK_CHECK_ARG(c.mass > 0.0 && c.gamma >= 0.0 && c.kT > 0.0, "%s: mass and kT must be positive, gamma not negative", what);
+    BGK_CHECK_ARG(!c.w2 || (c.w1 && langevin), "%s: w2 goes with w1 and with velocities", what);
+    BGK_CHECK_ARG(!(langevin && c.w1) || c.w2, "%s: with velocities w1 and w2 go together", what);
     return 0;
 }
 
-int langevin_rows(int nd, int tiles) {
-    int rows = LG_THREADS;
-    while (tiles * rows * (nd | 1) * (int)sizeof(float) > LG_LDS_DYNAMIC) --rows;
-    return rows;
-}
-
-int langevin_forward(const char* what, float* q, float* v, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
-                     double p0, double p1, double p2, double p3, double osc_scale,
-                     double stepsize, double mass, double gamma, double kT, int32_t n_steps,
-                     const float* w1, const float* w2, uint64_t seed, uint32_t offset, int64_t row0,
-                     float* dW, int32_t accumulate, float* traj_q, float* traj_v, void* stream) {
-    const bool langevin = v != nullptr;
-    const int st = langevin_check(what, B, row0, n_steps, n_particles, n_dims, kind, stepsize, mass, gamma, kT, w1, w2, langevin);
-    if (st) return st;
-    if (B == 0) return 0;
-    BGK_CHECK_ARG(q && dW, "%s: null tensor", what);
+/* v: Langevin, else Brownian; traj_q (traj_v): the recording kernel */
+int langevin_forward(const BgkLangevinCall& c, float* q, float* v, float* dW, int32_t accumulate, float* traj_q, float* traj_v) {
+    const char* what = c.spec.what;
+    const bool langevin = v != nullptr, record = traj_q != nullptr;
     LgArgs a{};
-    a.q = q; a.v = v; a.B = B; a.row0 = row0; a.n = n_particles; a.nd = n_particles * n_dims;
-    a.magic = (uint32_t)(((1ull << 32) + (uint64_t)a.nd - 1) / (uint64_t)a.nd);
-    const int S = a.nd | 1, tiles = langevin ? 5 : 4;
-    const int rows = langevin_rows(a.nd, tiles);
-    a.rows = rows;
-    a.p0 = (float)p0; a.p1 = (float)p1; a.p2 = (float)p2; a.p3 = (float)p3; a.osc = (float)osc_scale;
-    const double gm = gamma * mass;
-    a.h = (float)stepsize; a.sq2h = (float)sqrt(2.0 * stepsize);
-    a.c1 = (float)(stepsize / (2.0 * mass)); a.c2 = (float)(1.0 / (1.0 + gamma * stepsize / 2.0)); a.gm = (float)gm;
-    a.fac1 = (float)sqrt(4.0 * gm * kT / stepsize); a.fac2 = (float)sqrt(gm * stepsize / kT);
-    a.n_steps = n_steps; a.w1 = w1; a.w2 = w2;
-    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.offset = offset;
+    const int st = langevin_check(c, langevin, &a.t);
+    if (st) return st;
+    if (c.B == 0) return 0;
+    BGK_CHECK_ARG(q && dW, "%s: null tensor", what);
+    a.q = q; a.v = v; a.B = c.B; a.row0 = c.row0;
+    const int bytes_per_row = (langevin ? 5 : 4) * (a.t.nd | 1) * (int)sizeof(float);
+    a.rows = rows_within(LG_LDS_DYNAMIC, bytes_per_row);
+    const double gm = c.gamma * c.mass;
+    a.h = (float)c.stepsize; a.sq2h = (float)sqrt(2.0 * c.stepsize);
+    a.c1 = (float)(c.stepsize / (2.0 * c.mass)); a.c2 = (float)(1.0 / (1.0 + c.gamma * c.stepsize / 2.0)); a.gm = (float)gm;
+    a.fac1 = (float)sqrt(4.0 * gm * c.kT / c.stepsize); a.fac2 = (float)sqrt(gm * c.stepsize / c.kT);
+    a.n_steps = c.n_steps; a.w1 = c.w1; a.w2 = c.w2;
+    a.seed_lo = (uint32_t)c.seed; a.seed_hi = (uint32_t)(c.seed >> 32); a.offset = c.offset;
     a.dW = dW; a.accumulate = accumulate != 0;
     a.traj_q = traj_q; a.traj_v = traj_v;
-    const size_t lds = (size_t)tiles * rows * S * sizeof(float);
-    const int64_t n_tiles = (B + rows - 1) / rows;
-    const int grid = (int)(n_tiles < LG_MAX_GRID ? n_tiles : LG_MAX_GRID);
-    hipStream_t s = (hipStream_t)stream;
-    const bool record = traj_q != nullptr;
-    if (kind == 0) launch_langevin<0>(langevin, record, n_dims, grid, lds, s, a);
-    else if (kind == 1) launch_langevin<1>(langevin, record, n_dims, grid, lds, s, a);
-    else launch_langevin<2>(langevin, record, n_dims, grid, lds, s, a);
+    const size_t lds = (size_t)a.rows * bytes_per_row;
+    const int grid = tile_grid(c.B, a.rows);
+    hipStream_t s = (hipStream_t)c.stream;
+    tile_dispatch<false>(c.spec.kind, c.spec.n_dims, [&](auto D, auto K) {
+        if (langevin && record) tile_launch(pair_langevin_kernel<D(), K(), true, true>, grid, lds, s, a);
+        else if (langevin) tile_launch(pair_langevin_kernel<D(), K(), true, false>, grid, lds, s, a);
+        else if (record) tile_launch(pair_langevin_kernel<D(), K(), false, true>, grid, lds, s, a);
+        else tile_launch(pair_langevin_kernel<D(), K(), false, false>, grid, lds, s, a);
+    });
     return bgk_launch_status(what);
 }
 
@@ -433,8 +380,9 @@ extern "C" int bgk_pair_langevin(float* q, float* v, int64_t B, int32_t n_partic
                                  double stepsize, double mass, double gamma, double kT, int32_t n_steps,
                                  const float* w1, const float* w2, uint64_t seed, uint32_t offset, int64_t row0,
                                  float* dW, int32_t accumulate, void* stream) {
-    return langevin_forward("bgk_pair_langevin", q, v, B, n_particles, n_dims, kind, p0, p1, p2, p3, osc_scale, stepsize, mass, gamma, kT,
-                            n_steps, w1, w2, seed, offset, row0, dW, accumulate, nullptr, nullptr, stream);
+    const BgkPairSpec spec = bgk_pair_spec("bgk_pair_langevin", n_particles, n_dims, kind, p0, p1, p2, p3, osc_scale);
+    return langevin_forward({spec, B, stepsize, mass, gamma, kT, n_steps, w1, w2, seed, offset, row0, stream}, q, v, dW, accumulate,
+                            nullptr, nullptr);
 }
 
 extern "C" int bgk_pair_langevin_record(float* q, float* v, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
@@ -444,8 +392,9 @@ extern "C" int bgk_pair_langevin_record(float* q, float* v, int64_t B, int32_t n
                                         float* dW, int32_t accumulate, float* traj_q, float* traj_v, void* stream) {
     BGK_CHECK_ARG(B == 0 || (traj_q && (traj_v != nullptr) == (v != nullptr)),
                   "bgk_pair_langevin_record: traj_q [n_steps, B, n d], and traj_v exactly with velocities");
-    return langevin_forward("bgk_pair_langevin_record", q, v, B, n_particles, n_dims, kind, p0, p1, p2, p3, osc_scale, stepsize, mass, gamma,
-                            kT, n_steps, w1, w2, seed, offset, row0, dW, accumulate, traj_q, traj_v, stream);
+    const BgkPairSpec spec = bgk_pair_spec("bgk_pair_langevin_record", n_particles, n_dims, kind, p0, p1, p2, p3, osc_scale);
+    return langevin_forward({spec, B, stepsize, mass, gamma, kT, n_steps, w1, w2, seed, offset, row0, stream}, q, v, dW, accumulate,
+                            traj_q, traj_v);
 }
 
 extern "C" int bgk_pair_langevin_backward(const float* q0, const float* v0, const float* traj_q, const float* traj_v, int64_t B,
@@ -455,19 +404,18 @@ extern "C" int bgk_pair_langevin_backward(const float* q0, const float* v0, cons
                                           const float* w1, const float* w2, uint64_t seed, uint32_t offset, int64_t row0,
                                           const float* g_dW, float* gq, float* gv, float* carry, int32_t first, void* stream) {
     const char* what = "bgk_pair_langevin_backward";
+    const BgkLangevinCall c{bgk_pair_spec(what, n_particles, n_dims, kind, p0, p1, p2, p3, osc_scale), B, stepsize, mass, gamma, kT, n_steps,
+                            w1, w2, seed, offset, row0, stream};
     const bool langevin = v0 != nullptr;
-    const int st = langevin_check(what, B, row0, n_steps, n_particles, n_dims, kind, stepsize, mass, gamma, kT, w1, w2, langevin);
+    LbArgs a{};
+    const int st = langevin_check(c, langevin, &a.t);
     if (st) return st;
     if (B == 0) return 0;
     BGK_CHECK_ARG(q0 && g_dW && gq && carry && (traj_q || n_steps == 0), "%s: null tensor", what);
     BGK_CHECK_ARG(langevin ? ((traj_v || n_steps == 0) && gv) : (!traj_v && !gv), "%s: traj_v and gv exactly with velocities", what);
-    LbArgs a{};
-    a.q0 = q0; a.v0 = v0; a.traj_q = traj_q; a.traj_v = traj_v; a.B = B; a.row0 = row0; a.n = n_particles; a.nd = n_particles * n_dims;
-    a.magic = (uint32_t)(((1ull << 32) + (uint64_t)a.nd - 1) / (uint64_t)a.nd);
-    const int S = a.nd | 1, tiles = 5;
-    const int rows = langevin_rows(a.nd, tiles);
-    a.rows = rows;
-    a.p0 = (float)p0; a.p1 = (float)p1; a.p2 = (float)p2; a.p3 = (float)p3; a.osc = (float)osc_scale;
+    a.q0 = q0; a.v0 = v0; a.traj_q = traj_q; a.traj_v = traj_v; a.B = B; a.row0 = row0;
+    const int bytes_per_row = 5 * (a.t.nd | 1) * (int)sizeof(float);
+    a.rows = rows_within(LG_LDS_DYNAMIC, bytes_per_row);
     const double c1 = stepsize / (2.0 * mass), gm = gamma * mass;
     a.h = (float)stepsize; a.sq2h = (float)sqrt(2.0 * stepsize);
     a.c1 = (float)c1; a.c2 = (float)(1.0 / (1.0 + gamma * stepsize / 2.0)); a.omg = (float)(1.0 - c1 * gm);
@@ -475,12 +423,12 @@ extern "C" int bgk_pair_langevin_backward(const float* q0, const float* v0, cons
     a.n_steps = n_steps; a.w1 = w1; a.w2 = w2;
     a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.offset = offset;
     a.g_dW = g_dW; a.gq = gq; a.gv = gv; a.carry = carry; a.first = first != 0;
-    const size_t lds = (size_t)tiles * rows * S * sizeof(float);
-    const int64_t n_tiles = (B + rows - 1) / rows;
-    const int grid = (int)(n_tiles < LG_MAX_GRID ? n_tiles : LG_MAX_GRID);
+    const size_t lds = (size_t)a.rows * bytes_per_row;
+    const int grid = tile_grid(B, a.rows);
     hipStream_t s = (hipStream_t)stream;
-    if (kind == 0) launch_langevin_bwd<0>(langevin, n_dims, grid, lds, s, a);
-    else if (kind == 1) launch_langevin_bwd<1>(langevin, n_dims, grid, lds, s, a);
-    else launch_langevin_bwd<2>(langevin, n_dims, grid, lds, s, a);
+    tile_dispatch<false>(kind, n_dims, [&](auto D, auto K) {
+        if (langevin) tile_launch(pair_langevin_bwd_kernel<D(), K(), true>, grid, lds, s, a);
+        else tile_launch(pair_langevin_bwd_kernel<D(), K(), false>, grid, lds, s, a);
+    });
     return bgk_launch_status(what);
 }

@@ -6,13 +6,13 @@
  *   launches (randn_like, add, the energy's op chain, rand_like, log, min, compare, two where) over a state of n d <= 192 floats per chain;
  *   here the state of a chain never leaves LDS between recorded frames.
  *
- * Like bgk_pair.hip / bgk_kdyn.hip: one wave per workgroup, ONE LANE PER CHAIN, a tile of rows staged coalesced through LDS with the odd
- * row stride S = (n d) | 1 (lane r reads word r S + k: distinct banks within a 32-lane group).  Two LDS tiles, A and B: a lane's current
- * row is in one, its proposal is written into the other, and accepting is a per-lane flip of which is which -- no copy.  B starts a
+ * By the rules of bgk_pair_tile.h: one wave per workgroup, ONE LANE PER CHAIN, a tile of rows staged coalesced through LDS at the odd
+ * row stride S.  Two LDS tiles, A and B: a lane's current row is in one, its proposal is written into the other, and accepting is a
+ * per-lane flip of which is which -- no copy.  B starts a
  * multiple of 32 words behind A, so lanes whose current rows sit in different tiles still hit distinct banks.  The steps run in lockstep
  * across the wave (the accept flag only selects); a recorded frame leaves as one coalesced tile store through a per-row tile flag in LDS.
  *
- * Energy: bgk_pair_row_energy of bgk_pair_terms.h -- the code of pair_energy_kernel, so e is, bit for bit, what bgk_pair_energy returns for
+ * Energy: bgk_row_energy of bgk_pair_terms.h -- the call of pair_energy_kernel, so e is, bit for bit, what bgk_pair_energy returns for
  * the row at temperature 1.  min(0, .) is dropped: log r < 0, so v >= log r and min(0, v) >= log r decide alike.  A proposal whose energy
  * is NaN or +inf is rejected by the comparison itself, as in the reference.
  *
@@ -22,7 +22,7 @@
  * (seed, step, global chain, column): the same bits whatever the tiling, the grid, row0 sharding or the split of a run into launches, and
  * the bits bgk_philox_fields writes for (seed, offset + step) with fields [normal n d, uniform 1].
  *
- * Envelope 2 <= n <= 64, 1 <= d <= 3.  Dynamic LDS <= 63,488 B: rows per tile = the most (<= 64) with (round32(rows S) + rows S) 4 B within
+ * Envelope: bgk_pair_tile.h.  Dynamic LDS <= 63,488 B: rows per tile = the most (<= 64) with (round32(rows S) + rows S) 4 B within
  * it; lanes beyond the rows only stage and store:
  *   n d = 192 (S = 193): 41 rows, 63,396 B       LJ13 (S = 39): 64 rows, 19,968 B       DW4 (S = 9): 64 rows, 4,608 B
  *   the particle box of 38 particles (S = 77): 64 rows, 39,424 B       of 64 particles (S = 129): 61 rows, 62,964 B */
@@ -32,16 +32,11 @@
 
 namespace {
 
-constexpr int MC_THREADS = 64;
-constexpr int MC_MAX_N = 64, MC_MAX_D = 3;
 constexpr int MC_LDS_DYNAMIC = 63488;
-constexpr int MC_MAX_GRID = 256 * 16;
 
 struct McArgs {
     float* x; int64_t B, row0;
-    int n, nd, rows, tile_b; uint32_t magic;            /* tile_b: word offset of the second tile, a multiple of 32 */
-    float p0, p1, p2, p3, osc;
-    BgkBoxParams box;                                   /* kinds 3 / 4 (the particle box) */
+    BgkPairTarget t; int rows, tile_b;                  /* tile_b: word offset of the second tile, a multiple of 32 */
     float* e; int e_valid;
     float temperature; const float* temperatures;
     float noise_std; int n_steps;
@@ -51,27 +46,25 @@ struct McArgs {
     int* n_accepted; int accumulate;
 };
 
-/* e(row) at temperature 1: the call of pair_energy_kernel */
-template <int D, int KIND>
-__device__ __forceinline__ float mc_row_energy(const float* xr, int n, const McArgs& a, float rm2) {
-    if constexpr (KIND >= 3) return (float)bgk_box_row_energy<KIND>(xr, n, a.box);
-    else return (float)bgk_pair_row_energy<D, KIND>(xr, n, a.p0, a.p1, a.p2, a.p3, rm2, a.osc);
+/* tile_store of every row's CURRENT state: s_sel[r] says which of the two tiles holds it; dst: the tile's first row in contiguous rows */
+__device__ __forceinline__ void mc_store_current(const McArgs& a, float* dst, int rows, const int* s_sel, const float* s_mem) {
+    const int nd = a.t.nd, S = nd | 1;
+    for (int i = threadIdx.x; i < rows * nd; i += BGK_TILE_THREADS) {
+        const int r = (int)__umulhi((unsigned)i, a.t.magic), c = i - r * nd;
+        dst[i] = s_mem[(s_sel[r] ? a.tile_b : 0) + r * S + c];
+    }
 }
 
 template <int D, int KIND>
-__global__ __launch_bounds__(MC_THREADS) void pair_mcmc_kernel(McArgs a) {
+__global__ __launch_bounds__(BGK_TILE_THREADS) void pair_mcmc_kernel(McArgs a) {
     extern __shared__ float s_mem[];
-    __shared__ int s_sel[MC_THREADS];                   /* which tile holds row r's current state */
-    const int tid = threadIdx.x, n = a.n, nd = a.nd, S = a.nd | 1;
-    const float rm2 = a.p1 * a.p1;
+    __shared__ int s_sel[BGK_TILE_THREADS];             /* which tile holds row r's current state */
+    const int tid = threadIdx.x, nd = a.t.nd, S = nd | 1;
     const int64_t n_tiles = (a.B + a.rows - 1) / a.rows;
     for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
         const int64_t b0 = t * a.rows;
         const int rows = (int)((a.B - b0) < a.rows ? (a.B - b0) : a.rows);
-        for (int i = tid; i < rows * nd; i += MC_THREADS) {
-            const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * nd;
-            s_mem[r * S + c] = a.x[(b0 + r) * nd + c];
-        }
+        tile_stage(a.x, b0, rows, nd, a.t.magic, s_mem);
         __syncthreads();
         const bool active = tid < rows;
         const int64_t b = b0 + (active ? tid : 0);
@@ -81,7 +74,7 @@ __global__ __launch_bounds__(MC_THREADS) void pair_mcmc_kernel(McArgs a) {
         float e = 0.0f, temp = 1.0f;
         if (active) {
             temp = a.temperatures ? a.temperatures[b] : a.temperature;
-            e = a.e_valid ? a.e[b] : mc_row_energy<D, KIND>(s_mem + tid * S, n, a, rm2);
+            e = a.e_valid ? a.e[b] : (float)bgk_row_energy<D, KIND>(s_mem + tid * S, a.t);
         }
         int frame = 0, since = 0;
         for (int step = 0; step < a.n_steps; ++step) {
@@ -109,7 +102,7 @@ __global__ __launch_bounds__(MC_THREADS) void pair_mcmc_kernel(McArgs a) {
                     philox4x32_10(r_lo, r_hi, 1u << 20, off, a.seed_lo, a.seed_hi, o);
                     r = u01(o[0]);
                 }
-                const float ep = mc_row_energy<D, KIND>(xp, n, a, rm2);
+                const float ep = (float)bgk_row_energy<D, KIND>(xp, a.t);      /* at temperature 1: the call of pair_energy_kernel */
                 const bool accept = -(ep - e) / temp >= bgk_logf(r);      /* false for a NaN on either side */
                 cur = accept ? cur ^ 1 : cur;
                 e = accept ? ep : e;
@@ -119,11 +112,7 @@ __global__ __launch_bounds__(MC_THREADS) void pair_mcmc_kernel(McArgs a) {
                 since = 0;
                 s_sel[tid] = cur;
                 __syncthreads();
-                float* dst = a.traj + ((int64_t)frame * a.B + b0) * nd;
-                for (int i = tid; i < rows * nd; i += MC_THREADS) {
-                    const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * nd;
-                    dst[i] = s_mem[(s_sel[r] ? a.tile_b : 0) + r * S + c];
-                }
+                mc_store_current(a, a.traj + ((int64_t)frame * a.B + b0) * nd, rows, s_sel, s_mem);
                 if (active && a.traj_e) a.traj_e[(int64_t)frame * a.B + b] = e;
                 ++frame;
                 __syncthreads();                        /* the next proposals overwrite rows this store reads */
@@ -131,10 +120,7 @@ __global__ __launch_bounds__(MC_THREADS) void pair_mcmc_kernel(McArgs a) {
         }
         s_sel[tid] = cur;
         __syncthreads();
-        for (int i = tid; i < rows * nd; i += MC_THREADS) {
-            const int r = (int)__umulhi((unsigned)i, a.magic), c = i - r * nd;
-            a.x[(b0 + r) * nd + c] = s_mem[(s_sel[r] ? a.tile_b : 0) + r * S + c];
-        }
+        mc_store_current(a, a.x + b0 * nd, rows, s_sel, s_mem);
         if (active) {
             a.e[b] = e;
             if (a.n_accepted) a.n_accepted[b] = a.accumulate ? a.n_accepted[b] + acc : acc;
@@ -143,23 +129,10 @@ __global__ __launch_bounds__(MC_THREADS) void pair_mcmc_kernel(McArgs a) {
     }
 }
 
-template <int KIND>
-void launch_mcmc(int d, int grid, size_t lds, hipStream_t s, const McArgs& a) {
-    if (d == 1) hipLaunchKernelGGL((pair_mcmc_kernel<1, KIND>), dim3(grid), dim3(MC_THREADS), lds, s, a);
-    else if (d == 2) hipLaunchKernelGGL((pair_mcmc_kernel<2, KIND>), dim3(grid), dim3(MC_THREADS), lds, s, a);
-    else hipLaunchKernelGGL((pair_mcmc_kernel<3, KIND>), dim3(grid), dim3(MC_THREADS), lds, s, a);
-}
-
-}  // namespace
-
-namespace {
-
-/* one call of either entry; is_box: the particle box, kinds 3 / 4 with a host parameter array instead of p0..p3, osc_scale */
+/* one call of either entry: the target as the entry names it (bgk_pair_spec / bgk_box_spec), then the entries' common arguments in order */
 struct BgkMcmcCall {
-    const char* what;
-    float* x; int64_t B; int32_t n_particles, n_dims, kind;
-    double p0, p1, p2, p3, osc_scale;
-    const float* box_params; int32_t n_box_params; int32_t is_box;
+    BgkPairSpec spec;
+    float* x; int64_t B;
     float* e; int32_t e_valid; double temperature; const float* temperatures;
     double noise_std; int32_t n_steps; const float* noise; const float* uniforms;
     uint64_t seed; uint32_t offset; int64_t row0;
@@ -168,51 +141,31 @@ struct BgkMcmcCall {
 };
 
 int mcmc_run(const BgkMcmcCall& c) {
-    const char* what = c.what;
-    const int64_t B = c.B;
-    const int32_t n_particles = c.n_particles, n_dims = c.n_dims, kind = c.kind;
-    BGK_CHECK_ARG(B >= 0 && c.row0 >= 0 && c.n_steps >= 0, "%s: bad batch size / row0 / n_steps", what);
-    if (c.is_box) {
-        BGK_CHECK_ARG(kind == 3 || kind == 4, "%s: kind %d (3 repulsive particles, 4 harmonic particles)", what, kind);
-        BGK_CHECK_ARG(c.box_params && c.n_box_params == BGK_BOX_N_PARAMS, "%s: params must be %d floats (see bgflow_amd.h)", what,
-                      BGK_BOX_N_PARAMS);
-    } else {
-        BGK_CHECK_ARG(kind >= 0 && kind <= 2, "%s: kind %d (0 Lennard-Jones, 1 multi-double-well, 2 mean-free normal)", what, kind);
-    }
-    if (!(n_particles >= 2 && n_particles <= MC_MAX_N && n_dims >= 1 && n_dims <= MC_MAX_D)) {
-        bgk_set_error("%s: %d particles in %d dimensions are outside the kernel's envelope (2..%d particles, 1..%d dimensions)", what,
-                      n_particles, n_dims, MC_MAX_N, MC_MAX_D);
-        return BGK_EUNSUPPORTED;
-    }
+    const char* what = c.spec.what;
+    McArgs a{};
+    BGK_CHECK_ARG(c.B >= 0 && c.row0 >= 0 && c.n_steps >= 0, "%s: bad batch size / row0 / n_steps", what);
+    const int st = bgk_pair_target(c.spec, &a.t);
+    if (st) return st;
     BGK_CHECK_ARG(c.temperatures || c.temperature > 0.0, "%s: the temperature must be positive", what);
     BGK_CHECK_ARG(c.noise_std >= 0.0, "%s: noise_std must not be negative", what);
     BGK_CHECK_ARG((c.noise != nullptr) == (c.uniforms != nullptr), "%s: noise and uniforms go together", what);
     BGK_CHECK_ARG(!c.traj_e || c.traj, "%s: traj_e without traj", what);
     BGK_CHECK_ARG(!c.traj || c.traj_every >= 1, "%s: traj_every %d", what, c.traj_every);
-    if (B == 0) return 0;
+    if (c.B == 0) return 0;
     BGK_CHECK_ARG(c.x && c.e, "%s: null tensor", what);
-    McArgs a{};
-    a.x = c.x; a.B = B; a.row0 = c.row0; a.n = n_particles; a.nd = n_particles * n_dims;
-    a.magic = (uint32_t)(((1ull << 32) + (uint64_t)a.nd - 1) / (uint64_t)a.nd);
-    const int S = a.nd | 1;
-    int rows = MC_THREADS;
-    while ((((rows * S + 31) & ~31) + rows * S) * (int)sizeof(float) > MC_LDS_DYNAMIC) --rows;
+    a.x = c.x; a.B = c.B; a.row0 = c.row0;
+    const int S = a.t.nd | 1;
+    int rows = rows_within(MC_LDS_DYNAMIC, 2 * S * (int)sizeof(float));
+    while ((((rows * S + 31) & ~31) + rows * S) * (int)sizeof(float) > MC_LDS_DYNAMIC) --rows;     /* the second tile starts at round32 */
     a.rows = rows; a.tile_b = (rows * S + 31) & ~31;
-    a.p0 = (float)c.p0; a.p1 = (float)c.p1; a.p2 = (float)c.p2; a.p3 = (float)c.p3; a.osc = (float)c.osc_scale;
-    if (c.is_box) bgk_box_params_from_host(c.box_params, &a.box);
     a.e = c.e; a.e_valid = c.e_valid != 0; a.temperature = (float)c.temperature; a.temperatures = c.temperatures;
     a.noise_std = (float)c.noise_std; a.n_steps = c.n_steps; a.noise = c.noise; a.uniforms = c.uniforms;
     a.seed_lo = (uint32_t)c.seed; a.seed_hi = (uint32_t)(c.seed >> 32); a.offset = c.offset;
     a.traj = c.traj; a.traj_e = c.traj_e; a.traj_every = c.traj_every; a.n_accepted = c.n_accepted; a.accumulate = c.accumulate != 0;
     const size_t lds = (size_t)(a.tile_b + rows * S) * sizeof(float);
-    const int64_t n_tiles = (B + rows - 1) / rows;
-    const int grid = (int)(n_tiles < MC_MAX_GRID ? n_tiles : MC_MAX_GRID);
+    const int grid = tile_grid(c.B, rows);
     hipStream_t s = (hipStream_t)c.stream;
-    if (kind == 0) launch_mcmc<0>(n_dims, grid, lds, s, a);
-    else if (kind == 1) launch_mcmc<1>(n_dims, grid, lds, s, a);
-    else if (kind == 2) launch_mcmc<2>(n_dims, grid, lds, s, a);
-    else if (kind == 3) hipLaunchKernelGGL((pair_mcmc_kernel<2, 3>), dim3(grid), dim3(MC_THREADS), lds, s, a);
-    else hipLaunchKernelGGL((pair_mcmc_kernel<2, 4>), dim3(grid), dim3(MC_THREADS), lds, s, a);
+    tile_dispatch<true>(c.spec.kind, c.spec.n_dims, [&](auto D, auto K) { tile_launch(pair_mcmc_kernel<D(), K()>, grid, lds, s, a); });
     return bgk_launch_status(what);
 }
 
@@ -224,16 +177,9 @@ extern "C" int bgk_pair_mcmc(float* x, int64_t B, int32_t n_particles, int32_t n
                              double noise_std, int32_t n_steps, const float* noise, const float* uniforms,
                              uint64_t seed, uint32_t offset, int64_t row0,
                              float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream) {
-    BgkMcmcCall c{};
-    c.what = "bgk_pair_mcmc";
-    c.x = x; c.B = B; c.n_particles = n_particles; c.n_dims = n_dims; c.kind = kind;
-    c.p0 = p0; c.p1 = p1; c.p2 = p2; c.p3 = p3; c.osc_scale = osc_scale;
-    c.e = e; c.e_valid = e_valid; c.temperature = temperature; c.temperatures = temperatures;
-    c.noise_std = noise_std; c.n_steps = n_steps; c.noise = noise; c.uniforms = uniforms;
-    c.seed = seed; c.offset = offset; c.row0 = row0;
-    c.traj = traj; c.traj_e = traj_e; c.traj_every = traj_every; c.n_accepted = n_accepted; c.accumulate = accumulate;
-    c.stream = stream;
-    return mcmc_run(c);
+    return mcmc_run({bgk_pair_spec("bgk_pair_mcmc", n_particles, n_dims, kind, p0, p1, p2, p3, osc_scale), x, B,
+                     e, e_valid, temperature, temperatures, noise_std, n_steps, noise, uniforms, seed, offset, row0,
+                     traj, traj_e, traj_every, n_accepted, accumulate, stream});
 }
 
 /* the particle box (kinds 3 / 4 of bgk_pair_terms.h) in the same chain kernel: MCMCStep._step (mcmc.py:86-122) over
@@ -243,14 +189,7 @@ extern "C" int bgk_box_mcmc(float* x, int64_t B, int32_t n_particles, int32_t ki
                             double noise_std, int32_t n_steps, const float* noise, const float* uniforms,
                             uint64_t seed, uint32_t offset, int64_t row0,
                             float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream) {
-    BgkMcmcCall c{};
-    c.what = "bgk_box_mcmc";
-    c.x = x; c.B = B; c.n_particles = n_particles; c.n_dims = 2; c.kind = kind;
-    c.box_params = params; c.n_box_params = n_params; c.is_box = 1;
-    c.e = e; c.e_valid = e_valid; c.temperature = temperature; c.temperatures = temperatures;
-    c.noise_std = noise_std; c.n_steps = n_steps; c.noise = noise; c.uniforms = uniforms;
-    c.seed = seed; c.offset = offset; c.row0 = row0;
-    c.traj = traj; c.traj_e = traj_e; c.traj_every = traj_every; c.n_accepted = n_accepted; c.accumulate = accumulate;
-    c.stream = stream;
-    return mcmc_run(c);
+    return mcmc_run({bgk_box_spec("bgk_box_mcmc", n_particles, kind, params, n_params), x, B,
+                     e, e_valid, temperature, temperatures, noise_std, n_steps, noise, uniforms, seed, offset, row0,
+                     traj, traj_e, traj_every, n_accepted, accumulate, stream});
 }

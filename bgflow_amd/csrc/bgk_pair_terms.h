@@ -1,7 +1,9 @@
 /* bgk_pair_terms.h -- the energy of ONE particle-system sample, as bgk_pair.hip's forward and bgk_mcmc.hip's chain step both add it up:
  * the pairs i < j in ascending (i, j) order, the terms of one i in f32, the n - 1 row sums and the centroid term in f64.  One source, so
  * the two kernels give the same bits for the same row (the library is built with -ffp-contract=off: the same sequence of IEEE ops).
- *   KIND 0  Lennard-Jones        p0 = eps, rm2 = rm^2:  eps sum [(rm2 / (d2 + 1e-6))^6 - 2 (rm2 / (d2 + 1e-6))^3]
+ * The parameters come in the target record, BgkPairTarget of bgk_pair_tile.h (tg: n, p0..p3, osc; box for KIND 3 / 4); rm2 = p1 p1 and
+ * c12 = -12 p0 / rm2 are formed from it here, on the device, in f32.
+ *   KIND 0  Lennard-Jones        p0 = eps, p1 = rm, rm2 = rm^2:  eps sum [(rm2 / (d2 + 1e-6))^6 - 2 (rm2 / (d2 + 1e-6))^3]
  *   KIND 1  multi-double-well    p0 = a, p1 = b, p2 = c, p3 = offset:  sum [a t^4 + b t^2 + c], t = sqrt(d2) - offset
  *   KIND 2  mean-free normal     no pair term
  *   + osc 0.5 sum_i |x_i - xbar|^2 when osc != 0
@@ -10,15 +12,18 @@
  * bgk_pair_row_hvp: that gradient and (d^2 e / d x^2) u in one pass over the pairs, for bgk_pair.hip's hvp kernel and bgk_langevin.hip's
  * adjoint sweep.
  * The particle box (bgflow/distribution/energy/particles.py: a dimer, particles 0 and 1, in a bath of solvent particles in a 2-d box;
- * rows [x0, y0, x1, y1, ...]) is two further kinds with a parameter record of their own, BgkBoxParams, and the same discipline:
+ * rows [x0, y0, x1, y1, ...]) is two further kinds with a parameter record of their own, BgkBoxParams (tg.box), and the same discipline:
  *   KIND 3  RepulsiveParticles   eps sum (rm2 / d2)^6 over the pairs i < j except (0, 1); no epsilon: coincident particles give +inf
  *   KIND 4  HarmonicParticles    spring sum (sqrt(d2) - rc)^2 over those pairs with d2 < rc^2
  *   + dimer  dimer_k (x0 + x1)^2 + dimer_k y0^2 + dimer_k y1^2 + slope t - a t^2 + b t^4,  t = 2 (|r0 - r1| - dmid)
  *   + box    2 box_k delta^2 for every coordinate c and both delta = -(c + half) and delta = c - half, where delta > 0
  *            (the reference's (sign(delta) + 1) box_k delta^2: the factor is 2, and 0 where delta < 0; delta = 0 adds 0 either way)
- * bgk_box_row_energy / bgk_box_row_gradient; no Hessian-vector form. */
+ * bgk_box_row_energy / bgk_box_row_gradient; no Hessian-vector form.  The kernels call bgk_row_energy / bgk_row_gradient (at the end),
+ * which pick the pair or the box form by KIND. */
 #ifndef BGK_PAIR_TERMS_H
 #define BGK_PAIR_TERMS_H
+
+#include "bgk_pair_tile.h"     /* BgkPairTarget, BgkBoxParams */
 
 /* 0.5 sum_i |x_i - xbar|^2 of the row (f64 sum of f32 squares); xbar[k] left in `mean` */
 template <int D>
@@ -42,7 +47,9 @@ __device__ __forceinline__ double bgk_pair_centroid_term(const float* xr, int n,
 
 /* e(x) of the row at temperature 1, before the rounding to f32 */
 template <int D, int KIND>
-__device__ __forceinline__ double bgk_pair_row_energy(const float* xr, int n, float p0, float p1, float p2, float p3, float rm2, float osc) {
+__device__ __forceinline__ double bgk_pair_row_energy(const float* xr, const BgkPairTarget& tg) {
+    const int n = tg.n;
+    const float p0 = tg.p0, p1 = tg.p1, p2 = tg.p2, p3 = tg.p3, osc = tg.osc, rm2 = p1 * p1;
     double e = 0.0;
     if (KIND != 2) {
         for (int i = 0; i + 1 < n; ++i) {
@@ -74,8 +81,9 @@ __device__ __forceinline__ double bgk_pair_row_energy(const float* xr, int n, fl
  * OWN row of an LDS tile (zeroed here; g_i in registers over the j loop, g_j read-modify-write, pairs in ascending (i, j) order, then
  * the oscillator term), all in f32.  c12 = -12 p0 / rm2 (KIND 0).  At d_ij = 0 the double-well pair gradient is 0. */
 template <int D, int KIND>
-__device__ __forceinline__ void bgk_pair_row_gradient(const float* xr, float* gw, int n, float p0, float p1, float p3, float rm2, float c12,
-                                                      float osc) {
+__device__ __forceinline__ void bgk_pair_row_gradient(const float* xr, float* gw, const BgkPairTarget& tg) {
+    const int n = tg.n;
+    const float p0 = tg.p0, p1 = tg.p1, p3 = tg.p3, osc = tg.osc, rm2 = p1 * p1, c12 = -12.0f * p0 / rm2;
     for (int c = 0; c < n * D; ++c) gw[c] = 0.0f;
     if (KIND != 2) {
         for (int i = 0; i + 1 < n; ++i) {
@@ -125,8 +133,9 @@ __device__ __forceinline__ void bgk_pair_row_gradient(const float* xr, float* gw
  *           at r = 0 both are 0, the gradient's convention
  *   oscillator  (Hu)_i += osc (u_i - ubar) */
 template <int D, int KIND, bool WITH_G = true>
-__device__ __forceinline__ void bgk_pair_row_hvp(const float* xr, const float* ur, float* gw, float* hw, int n, float p0, float p1, float p3,
-                                                 float rm2, float c12, float osc) {
+__device__ __forceinline__ void bgk_pair_row_hvp(const float* xr, const float* ur, float* gw, float* hw, const BgkPairTarget& tg) {
+    const int n = tg.n;
+    const float p0 = tg.p0, p1 = tg.p1, p3 = tg.p3, osc = tg.osc, rm2 = p1 * p1, c12 = -12.0f * p0 / rm2;
     for (int c = 0; c < n * D; ++c) { if (WITH_G) gw[c] = 0.0f; hw[c] = 0.0f; }
     if (KIND != 2) {
         for (int i = 0; i + 1 < n; ++i) {
@@ -179,22 +188,6 @@ __device__ __forceinline__ void bgk_pair_row_hvp(const float* xr, const float* u
                 hw[i * D + k] += osc * (ur[i * D + k] - umean[k]);
             }
     }
-}
-
-/* the parameters of KIND 3 / 4, by value inside the kernels' argument records (wave-uniform) */
-struct BgkBoxParams {
-    float eps, rm2, spring, rc, rc2;
-    float dimer_k, dimer_slope, dimer_a, dimer_b, dimer_dmid;
-    float box_half, box_k;
-};
-
-/* the host array of the bgk_box_* entries (include/bgflow_amd.h): [eps, rm^2, rc, rc^2, spring_constant, dimer_slope, dimer_a, dimer_b,
- * dimer_dmid, dimer_k, box_halfsize, box_k]; the caller forms the squares in double, so that they are rounded once */
-constexpr int BGK_BOX_N_PARAMS = 12;
-inline void bgk_box_params_from_host(const float* h, BgkBoxParams* p) {
-    p->eps = h[0]; p->rm2 = h[1]; p->rc = h[2]; p->rc2 = h[3]; p->spring = h[4];
-    p->dimer_slope = h[5]; p->dimer_a = h[6]; p->dimer_b = h[7]; p->dimer_dmid = h[8]; p->dimer_k = h[9];
-    p->box_half = h[10]; p->box_k = h[11];
 }
 
 /* e(x) of the row [2 n] at temperature 1, before the rounding to f32: the pair terms of one i in f32, the row sums, the dimer's terms and
@@ -286,6 +279,19 @@ __device__ __forceinline__ void bgk_box_row_gradient(const float* xr, float* gw,
         const float v = xr[c], lo = -(v + p.box_half), hi = v - p.box_half;
         gw[c] += (hi > 0.0f ? k4 * hi : 0.0f) - (lo > 0.0f ? k4 * lo : 0.0f);
     }
+}
+
+/* the row's energy / gradient for any KIND: the one place that chooses between the pair and the box forms */
+template <int D, int KIND>
+__device__ __forceinline__ double bgk_row_energy(const float* xr, const BgkPairTarget& tg) {
+    if constexpr (KIND >= 3) return bgk_box_row_energy<KIND>(xr, tg.n, tg.box);
+    else return bgk_pair_row_energy<D, KIND>(xr, tg);
+}
+
+template <int D, int KIND>
+__device__ __forceinline__ void bgk_row_gradient(const float* xr, float* gw, const BgkPairTarget& tg) {
+    if constexpr (KIND >= 3) bgk_box_row_gradient<KIND>(xr, gw, tg.n, tg.box);
+    else bgk_pair_row_gradient<D, KIND>(xr, gw, tg);
 }
 
 #endif

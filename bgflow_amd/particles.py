@@ -23,8 +23,18 @@ __all__ = ["LennardJonesPotential", "MultiDoubleWellPotential", "MeanFreeNormalD
 PAIR_MAX_PARTICLES, PAIR_MAX_DIMS = 64, 3         # the kernel's envelope (csrc/bgk_pair.hip)
 
 
-def _number(*values):
-    return all(isinstance(v, (int, float)) for v in values)
+def _is_number(*values):
+    return all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in values)
+
+
+def _check_tensors(name, like, tensors, dtype=torch.float32):
+    """the argument check of the launch wrappers: every (tensor or None, shape) pair is a contiguous ``dtype`` tensor of that shape on
+    the device of ``like``"""
+    for t, shape in tensors:
+        if t is None:
+            continue
+        if not (t.is_cuda and t.device == like.device and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"{name}: expected a contiguous {dtype} HIP tensor of shape {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
 
 
 def _pair_rows(plan, xs):
@@ -51,12 +61,16 @@ def _entry(plan, name):
     return getattr(_lib.lib(), full), full
 
 
+def _target_args(plan):
+    """the target in a C entry's argument list, after B: of the bgk_box_* entries for a BoxPlan, else of the bgk_pair_* entries"""
+    if isinstance(plan, BoxPlan):
+        return (plan.n_particles, plan.kind, _box_params(plan), len(plan.params))
+    return (plan.n_particles, plan.n_dims, plan.kind, plan.p0, plan.p1, plan.p2, plan.p3, plan.osc_scale)
+
+
 def _launch_args(plan, x2):
     from . import _lib
-    if isinstance(plan, BoxPlan):
-        return (_lib.ptr(x2), x2.shape[1], x2.shape[0], plan.n_particles, plan.kind, _box_params(plan), len(plan.params), plan.temperature)
-    return (_lib.ptr(x2), x2.shape[1], x2.shape[0], plan.n_particles, plan.n_dims, plan.kind, plan.p0, plan.p1, plan.p2, plan.p3,
-            plan.osc_scale, plan.temperature)
+    return (_lib.ptr(x2), x2.shape[1], x2.shape[0], *_target_args(plan), plan.temperature)
 
 
 def _energy_backward(plan, x2, g):
@@ -182,7 +196,7 @@ class _ParticleEnergy(Energy):
         super().__init__([n_particles, dim // n_particles] if two_event_dims else dim)
 
     def _plan(self, temperature, kind, n, d, p, osc_scale):
-        if not (_number(temperature, osc_scale, *p) and temperature > 0 and 2 <= n <= PAIR_MAX_PARTICLES and 1 <= d <= PAIR_MAX_DIMS):
+        if not (_is_number(temperature, osc_scale, *p) and temperature > 0 and 2 <= n <= PAIR_MAX_PARTICLES and 1 <= d <= PAIR_MAX_DIMS):
             return None
         return PairPlan(kind, n, d, *(float(v) for v in p), float(osc_scale), float(temperature))
 
@@ -356,7 +370,7 @@ class RepulsiveParticles(Energy):
         p = self.params
         names = ("eps", "rm", "rc", "dimer_slope", "dimer_a", "dimer_b", "dimer_dmid", "dimer_k", "box_halfsize", "box_k")
         spring = self._spring()
-        if not (_number(temperature, spring, *(p[k] for k in names)) and temperature > 0 and isinstance(self.nparticles, int)
+        if not (_is_number(temperature, spring, *(p[k] for k in names)) and temperature > 0 and isinstance(self.nparticles, int)
                 and 2 <= self.nparticles <= PAIR_MAX_PARTICLES):
             return None
         values = (p["eps"], p["rm"] ** 2, p["rc"], p["rc"] ** 2, spring, p["dimer_slope"], p["dimer_a"], p["dimer_b"], p["dimer_dmid"],

@@ -20,6 +20,7 @@ from typing import Sequence
 import torch
 
 from .distributions import BoxPlan, PairPlan, Sampler, _FusedSampling, _kernel_plan
+from .particles import _check_tensors, _target_args
 from .utils import pack_tensor_in_list, pack_tensor_in_tuple, unpack_tensor_tuple
 
 __all__ = ["AbstractSamplerState", "SamplerState", "SamplerStep", "IterativeSampler", "GaussianProposal", "LatentProposal", "MCMCStep",
@@ -156,23 +157,14 @@ def pair_mcmc(plan, x, e, e_valid, temperature, noise_std, n_steps, noise=None, 
         raise ValueError("pair_mcmc: noise and uniforms go together")
     temps = temperature if torch.is_tensor(temperature) else None
     n_frames = n_steps // traj_every if traj is not None else 0
-    floats = [(x, (B, nd)), (e, (B,)), (temps, (B,)), (noise, (n_steps, B, nd)), (uniforms, (n_steps, B)), (traj, (n_frames, B, nd)),
-              (traj_e, (n_frames, B))]
-    for t, shape in floats + [(n_accepted, (B,))]:
-        if t is None:
-            continue
-        want = torch.int32 if t is n_accepted else torch.float32
-        if not (t.is_cuda and t.device == x.device and t.dtype == want and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError(f"pair_mcmc: expected a contiguous {want} HIP tensor of shape {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    _check_tensors("pair_mcmc", x, [(x, (B, nd)), (e, (B,)), (temps, (B,)), (noise, (n_steps, B, nd)), (uniforms, (n_steps, B)),
+                                    (traj, (n_frames, B, nd)), (traj_e, (n_frames, B))])
+    _check_tensors("pair_mcmc", x, [(n_accepted, (B,))], dtype=torch.int32)
     if traj is not None and traj_every < 1:
         raise ValueError("pair_mcmc: traj_every must be at least 1")
-    if isinstance(plan, BoxPlan):
-        from .particles import _box_params
-        name, target = "bgk_box_mcmc", (plan.n_particles, plan.kind, _box_params(plan), len(plan.params))
-    else:
-        name, target = "bgk_pair_mcmc", (plan.n_particles, plan.n_dims, plan.kind, plan.p0, plan.p1, plan.p2, plan.p3, plan.osc_scale)
+    name = "bgk_box_mcmc" if isinstance(plan, BoxPlan) else "bgk_pair_mcmc"
     with torch.cuda.device(x.device):
-        st = getattr(_lib.lib(), name)(_lib.ptr(x), B, *target, _lib.ptr(e), int(bool(e_valid)),
+        st = getattr(_lib.lib(), name)(_lib.ptr(x), B, *_target_args(plan), _lib.ptr(e), int(bool(e_valid)),
                                        1.0 if temps is not None else float(temperature),
                                        _lib.ptr(temps), float(noise_std), int(n_steps), _lib.ptr(noise), _lib.ptr(uniforms),
                                        int(seed) & (2 ** 64 - 1), int(offset) & 0xffffffff, int(row0), _lib.ptr(traj), _lib.ptr(traj_e),

@@ -39,6 +39,7 @@ import torch
 
 from .distributions import BoxPlan, Energy, PairPlan, _FusedSampling, _kernel_plan
 from .flow import Flow
+from .particles import _check_tensors, _energy_backward, _is_number, _target_args
 
 __all__ = ["BrownianFlow", "OverdampedLangevinFlow", "LangevinFlow", "MetropolisMCFlow"]
 
@@ -59,10 +60,6 @@ LANGEVIN_BACKWARD_MAX_STEPS_PER_LAUNCH = 24
 # The most bytes of recorded states (nsteps B n d 4, twice that for Langevin) the fused backward keeps; beyond, the general path.  A
 # policy constant, not a measurement: 1 GiB beside the model's activations.
 LANGEVIN_BACKWARD_MAX_BYTES = 2 ** 30
-
-
-def _is_number(*values):
-    return all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in values)
 
 
 def _split(total, cap):
@@ -95,11 +92,7 @@ def _check_launch(name, plan, q, v, w1, w2, tensors):
         raise ValueError(f"{name}: q has {nd} columns, the target {plan.n_particles} x {plan.n_dims}")
     if (w2 is not None) != (w1 is not None and v is not None):
         raise ValueError(f"{name}: w1 alone without velocities, w1 and w2 with them")
-    for t, shape in tensors:
-        if t is None:
-            continue
-        if not (t.is_cuda and t.device == q.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError(f"{name}: expected a contiguous float32 HIP tensor of shape {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    _check_tensors(name, q, tensors)
 
 
 def pair_langevin(plan, q, v, stepsize, mass, gamma, kT, n_steps, dW, w1=None, w2=None, seed=0, offset=0, row0=0, accumulate=False):
@@ -111,10 +104,10 @@ def pair_langevin(plan, q, v, stepsize, mass, gamma, kT, n_steps, dW, w1=None, w
     _check_launch("pair_langevin", plan, q, v, w1, w2,
                   ((q, (B, nd)), (v, (B, nd)), (dW, (B,)), (w1, (n_steps, B, nd)), (w2, (n_steps, B, nd))))
     with torch.cuda.device(q.device):
-        st = _lib.lib().bgk_pair_langevin(_lib.ptr(q), _lib.ptr(v), B, plan.n_particles, plan.n_dims, plan.kind, plan.p0, plan.p1, plan.p2,
-                                          plan.p3, plan.osc_scale, float(stepsize), float(mass), float(gamma), float(kT), int(n_steps),
-                                          _lib.ptr(w1), _lib.ptr(w2), int(seed) & (2 ** 64 - 1), int(offset) & 0xffffffff, int(row0),
-                                          _lib.ptr(dW), int(bool(accumulate)), _lib.stream_ptr(q.device))
+        st = _lib.lib().bgk_pair_langevin(_lib.ptr(q), _lib.ptr(v), B, *_target_args(plan), float(stepsize), float(mass), float(gamma),
+                                          float(kT), int(n_steps), _lib.ptr(w1), _lib.ptr(w2), int(seed) & (2 ** 64 - 1),
+                                          int(offset) & 0xffffffff, int(row0), _lib.ptr(dW), int(bool(accumulate)),
+                                          _lib.stream_ptr(q.device))
     _lib.check(st, "bgk_pair_langevin")
 
 
@@ -130,9 +123,8 @@ def pair_langevin_record(plan, q, v, stepsize, mass, gamma, kT, n_steps, dW, tra
                   ((q, (B, nd)), (v, (B, nd)), (dW, (B,)), (w1, (n_steps, B, nd)), (w2, (n_steps, B, nd)), (traj_q, (n_steps, B, nd)),
                    (traj_v, (n_steps, B, nd))))
     with torch.cuda.device(q.device):
-        st = _lib.lib().bgk_pair_langevin_record(_lib.ptr(q), _lib.ptr(v), B, plan.n_particles, plan.n_dims, plan.kind, plan.p0, plan.p1,
-                                                 plan.p2, plan.p3, plan.osc_scale, float(stepsize), float(mass), float(gamma), float(kT),
-                                                 int(n_steps), _lib.ptr(w1), _lib.ptr(w2), int(seed) & (2 ** 64 - 1),
+        st = _lib.lib().bgk_pair_langevin_record(_lib.ptr(q), _lib.ptr(v), B, *_target_args(plan), float(stepsize), float(mass),
+                                                 float(gamma), float(kT), int(n_steps), _lib.ptr(w1), _lib.ptr(w2), int(seed) & (2 ** 64 - 1),
                                                  int(offset) & 0xffffffff, int(row0), _lib.ptr(dW), int(bool(accumulate)), _lib.ptr(traj_q),
                                                  _lib.ptr(traj_v), _lib.stream_ptr(q.device))
     _lib.check(st, "bgk_pair_langevin_record")
@@ -153,8 +145,7 @@ def pair_langevin_backward(plan, q0, v0, traj_q, traj_v, stepsize, mass, gamma, 
                   ((q0, (B, nd)), (v0, (B, nd)), (traj_q, (n_steps, B, nd)), (traj_v, (n_steps, B, nd)), (g_dW, (B,)), (gq, (B, nd)),
                    (gv, (B, nd)), (carry, (B, nd)), (w1, (n_steps, B, nd)), (w2, (n_steps, B, nd))))
     with torch.cuda.device(q0.device):
-        st = _lib.lib().bgk_pair_langevin_backward(_lib.ptr(q0), _lib.ptr(v0), _lib.ptr(traj_q), _lib.ptr(traj_v), B, plan.n_particles,
-                                                   plan.n_dims, plan.kind, plan.p0, plan.p1, plan.p2, plan.p3, plan.osc_scale,
+        st = _lib.lib().bgk_pair_langevin_backward(_lib.ptr(q0), _lib.ptr(v0), _lib.ptr(traj_q), _lib.ptr(traj_v), B, *_target_args(plan),
                                                    float(stepsize), float(mass), float(gamma), float(kT), int(n_steps), _lib.ptr(w1),
                                                    _lib.ptr(w2), int(seed) & (2 ** 64 - 1), int(offset) & 0xffffffff, int(row0),
                                                    _lib.ptr(g_dW), _lib.ptr(gq), _lib.ptr(gv), _lib.ptr(carry), int(bool(first)),
@@ -232,17 +223,11 @@ class _MetropolisFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_y, g_dW):
-        from . import _lib, particles
         x, y = ctx.saved_tensors
         g = g_dW.reshape(-1).to(torch.float32).contiguous()
         out = g_y.to(torch.float32).clone()
         for state, g_u in ((y, g), (x, -g)):
-            gx = torch.empty_like(state)
-            with torch.cuda.device(state.device):
-                st = _lib.lib().bgk_pair_energy_backward(*particles._launch_args(ctx.plan, state), _lib.ptr(g_u), None, None, None, 0, None,
-                                                         _lib.ptr(gx), gx.shape[1], _lib.stream_ptr(state.device))
-            _lib.check(st, "bgk_pair_energy_backward")
-            out += gx
+            out += _energy_backward(ctx.plan, state, g_u)
         return None, None, out
 
 
