@@ -33,7 +33,8 @@ import warnings
 import numpy as np
 import torch
 
-from . import _lib
+from . import _driver, _lib
+from ._driver import DTYPE_CODES as _DTYPE_CODES
 
 __all__ = ["mean_finite_", "std_finite_", "mean_finite", "std_finite", "metropolis_function", "bar", "free_energy_bootstrap",
            "bootstrap_histogram"]
@@ -45,7 +46,6 @@ MAX_CHUNKS = 512
 MIN_DRAWS_PER_CHUNK = 4096     # 16 draws per thread
 TARGET_BLOCKS = 2048           # 8 blocks per CU
 TORCH_BATCH_ELEMENTS = 1 << 24  # gathered elements per batch of the torch path
-_DTYPE_CODES = {torch.float32: 0, torch.float64: 1}      # BGK_HIST_F32 / BGK_HIST_F64
 
 
 # ---- statistics over finite values ---------------------------------------------------------------------------------------------------
@@ -111,15 +111,10 @@ def _host_generator(seed):
 
 def _kernel_eligible(D, W):
     def one(t):
-        return (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.dtype in _DTYPE_CODES
-                and not t.requires_grad and t.numel() >= 1)
-    if not all(one(d) for d in D):
+        return _driver.kernel_takes(t) and t.numel() >= 1
+    if not (all(one(d) for d in D) and _driver.same_kind(D)):
         return False
-    if any(d.dtype != D[0].dtype or d.device != D[0].device for d in D):
-        return False
-    if W is None:
-        return True
-    return all(one(w) and w.dtype == d.dtype and w.device == d.device and w.shape == d.shape for d, w in zip(D, W))
+    return W is None or all(one(w) and _driver.same_kind((d, w)) and w.shape == d.shape for d, w in zip(D, W))
 
 
 def _n_chunks(n, sample):

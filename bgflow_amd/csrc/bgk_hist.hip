@@ -31,7 +31,7 @@
  * Reproducibility: unweighted sums are sums of 1.0 in f64, exact and bitwise reproducible in any order.  Weighted sums depend on the
  * arrival order of the LDS adds in their last bits: |sum - exact| <= m 2^-52 exact for a bin that received m draws (any order of m
  * positive f64 terms is within (m - 1) 2^-53; the factor 2 covers the wave and chunk merges and the second-order term). */
-#include "bgk_common.h"
+#include "bgk_reduce.h"
 #include "bgk_philox.h"
 
 namespace {
@@ -214,7 +214,7 @@ extern "C" int bgk_bootstrap_histogram(const void* d, const void* w, int64_t n, 
                                        int64_t* n_ignored, void* stream) {
     BGK_CHECK_ARG(d && edges && records && partial && out, "bgk_bootstrap_histogram: null pointer (d, edges, records, partial, out)");
     BGK_CHECK_ARG(n >= 1, "bgk_bootstrap_histogram: bad size (n = %lld, at least one sample)", (long long)n);
-    BGK_CHECK_ARG(dtype == BGK_HIST_F32 || dtype == BGK_HIST_F64, "bgk_bootstrap_histogram: dtype code %d (0 = f32, 1 = f64)", (int)dtype);
+    BGK_CHECK_DTYPE("bgk_bootstrap_histogram", dtype);
     BGK_CHECK_ARG(nb >= 1, "bgk_bootstrap_histogram: nb = %d bins (at least 1)", (int)nb);
     if (nb > HIST_MAX_BINS) {
         bgk_set_error("bgk_bootstrap_histogram: nb = %d bins is outside the envelope (1 .. %d)", (int)nb, HIST_MAX_BINS);
@@ -226,10 +226,9 @@ extern "C" int bgk_bootstrap_histogram(const void* d, const void* w, int64_t n, 
                   (long long)replicate0, (long long)n_replicates);
     BGK_CHECK_ARG(n_replicates * (int64_t)n_chunks <= 0x7fffffffLL, "bgk_bootstrap_histogram: n_replicates * n_chunks exceeds the grid (2^31 - 1 blocks)");
     BGK_CHECK_ARG(!(indices && segments), "bgk_bootstrap_histogram: both indices and segments given");
-    const uintptr_t elem = dtype == BGK_HIST_F32 ? 4 : 8;
-    BGK_CHECK_ARG((uintptr_t)d % elem == 0 && (uintptr_t)w % elem == 0 && (uintptr_t)edges % 8 == 0 && (uintptr_t)records % (2 * elem) == 0 &&
-                  (uintptr_t)partial % 8 == 0 && (uintptr_t)out % 8 == 0 && (uintptr_t)indices % 8 == 0 && (uintptr_t)segments % 8 == 0 &&
-                  (uintptr_t)n_ignored % 8 == 0, "bgk_bootstrap_histogram: a pointer is not aligned to its element size");
+    const uintptr_t elem = bgk_dtype_size(dtype);
+    BGK_CHECK_ALIGNED("bgk_bootstrap_histogram", bgk_aligned(elem, d, w) && bgk_aligned(2 * elem, records) &&
+                      bgk_aligned(8, edges, partial, out, indices, segments, n_ignored));
     if (n_replicates == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     if (n_ignored) {
@@ -244,7 +243,6 @@ extern "C" int bgk_bootstrap_histogram(const void* d, const void* w, int64_t n, 
     a.n = n; a.n_replicates = n_replicates; a.replicate0 = replicate0;
     a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.offset = offset;
     a.nb = nb; a.n_chunks = n_chunks; a.copies = nb <= HIST_COPY_BINS ? HIST_WAVES : 1;
-    if (dtype == BGK_HIST_F32) hist_enqueue<float>(d, w, edges, records, n_ignored, a, st);
-    else hist_enqueue<double>(d, w, edges, records, n_ignored, a, st);
+    bgk_dtype_dispatch(dtype, [&](auto e) { hist_enqueue<decltype(e)>(d, w, edges, records, n_ignored, a, st); });
     return bgk_launch_status("bgk_bootstrap_histogram");
 }

@@ -18,19 +18,13 @@
  * Finalize (moments_finalize_kernel): mean = K + S1 / n, var = (S2 - S1^2 / n) / (n - 1) clamped at 0 (n = 1: 0 / 0 = NaN as
  * torch.std; a constant column has S1 = S2 = 0 exactly).  A NaN in the data reaches S1, S2, min and max of its column only.
  */
-#include "bgk_common.h"
+#include "bgk_reduce.h"
 
 namespace {
 
 struct Mom {
     double n, K, S1, S2, mn, mx;
 };
-
-/* min / max that keep a NaN once seen (torch.min / torch.max semantics) */
-__device__ __forceinline__ float nan_minf(float m, float v) { return (v < m || v != v) ? v : m; }
-__device__ __forceinline__ float nan_maxf(float m, float v) { return (v > m || v != v) ? v : m; }
-__device__ __forceinline__ double nan_min(double m, double v) { return (v < m || v != v) ? v : m; }
-__device__ __forceinline__ double nan_max(double m, double v) { return (v > m || v != v) ? v : m; }
 
 /* a <- a merged with b, under a's K (b's when a is empty) */
 __device__ __forceinline__ void mom_merge(Mom& a, const Mom& b) {
@@ -40,8 +34,8 @@ __device__ __forceinline__ void mom_merge(Mom& a, const Mom& b) {
     a.S2 = a.S2 + (b.S2 + (2.0 * d * b.S1 + b.n * d * d));
     a.S1 = a.S1 + (b.S1 + b.n * d);
     a.n += b.n;
-    a.mn = nan_min(a.mn, b.mn);
-    a.mx = nan_max(a.mx, b.mx);
+    a.mn = bgk_nan_min(a.mn, b.mn);         /* min / max keep a NaN once seen */
+    a.mx = bgk_nan_max(a.mx, b.mx);
 }
 
 __device__ __forceinline__ Mom mom_load(const double* p) { return Mom{p[0], p[1], p[2], p[3], p[4], p[5]}; }
@@ -56,8 +50,8 @@ struct Acc {
         const double d = (double)v - K;
         S1 += d;
         S2 = __builtin_fma(d, d, S2);
-        mn = nan_minf(mn, v);
-        mx = nan_maxf(mx, v);
+        mn = bgk_nan_min(mn, v);
+        mx = bgk_nan_max(mx, v);
     }
 };
 

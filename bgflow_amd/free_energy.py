@@ -24,15 +24,14 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _driver, _lib
+from ._driver import BUDGET, CONVERGED, NO_ROOT, NOT_A_NUMBER, R_STATUS, STATUS_NAMES      # NOT_A_NUMBER: neither sign test fired (f is NaN)
+from ._driver import DTYPE_CODES as _DTYPE_CODES
 
 __all__ = ["bennett_acceptance_ratio", "bar_solve", "BARResult"]
 
 BARResult = namedtuple("BARResult", ["delta_f", "uncertainty", "residual", "status", "n_evaluations", "n_expansions", "n_iterations",
                                      "n_readbacks"])
-
-CONVERGED, BUDGET, NO_ROOT, NOT_A_NUMBER = 0, 1, 2, 3      # status: BUDGET = iterations exhausted, NO_ROOT = expansions exhausted,
-STATUS_NAMES = ("converged", "budget exhausted", "no root", "nan")     # NOT_A_NUMBER = neither sign test fired (f is NaN)
 
 BAR_CHUNK = 16                 # evaluations enqueued per host read-back of the record (kernel path)
 MAX_BLOCKS = 512               # stage-1 blocks per work array (2 per CU)
@@ -40,10 +39,9 @@ MIN_ELEMENTS_PER_BLOCK = 4096  # 16 elements per thread
 
 # the device record (f64), csrc/bgk_bar.hip / include/bgflow_amd.h
 RECORD_DOUBLES = 18
-(R_PHASE, R_STATUS, R_UPPER, R_LOWER, R_F_UPPER, R_F_LOWER, R_DELTA, R_DELTA_OLD, R_N_EVAL, R_N_EXPAND, R_N_ITER,
- R_L1F, R_L2F, R_L1R, R_L2R, R_RESIDUAL, R_RESULT, R_UNCERTAINTY) = range(RECORD_DOUBLES)
+(R_UPPER, R_LOWER, R_F_UPPER, R_F_LOWER, R_DELTA, R_DELTA_OLD, R_N_EVAL, R_N_EXPAND, R_N_ITER,
+ R_L1F, R_L2F, R_L1R, R_L2R, R_RESIDUAL, R_RESULT, R_UNCERTAINTY) = range(2, RECORD_DOUBLES)      # after R_PHASE, R_STATUS
 PHASE_DONE = 4
-_DTYPE_CODES = {torch.float32: 0, torch.float64: 1}
 
 
 def _clamp(x, lo=0.1, hi=1e10):
@@ -147,31 +145,23 @@ def _bar_kernel(wf, wr, maximum_iterations, relative_tolerance, chunk=None):
     dev = wf.device
     wf, wr = wf.detach().contiguous(), wr.detach().contiguous()
     nbf, nbr = _blocks(wf.numel()), _blocks(wr.numel())
-    record = torch.zeros(RECORD_DOUBLES, dtype=torch.float64, device=dev)      # all zeros: the solver's start state
     partial = torch.empty(3 * (nbf + nbr), dtype=torch.float64, device=dev)
+
+    def enqueue(record, n_steps):
+        return _lib.lib().bgk_bar_solve_steps(_lib.ptr(wf), wf.numel(), _lib.ptr(wr), wr.numel(), _DTYPE_CODES[wf.dtype], nbf, nbr,
+                                              _lib.ptr(partial), _lib.ptr(record), maximum_iterations, relative_tolerance, n_steps,
+                                              _lib.stream_ptr(dev))
+
     # one pass for the bounds, two evaluations per expansion (and the first two), one per iteration
     budget = 3 + 2 * maximum_iterations + maximum_iterations
-    reads, enqueued = 0, 0
-    while True:
-        with torch.cuda.device(dev):
-            st = _lib.lib().bgk_bar_solve_steps(_lib.ptr(wf), wf.numel(), _lib.ptr(wr), wr.numel(), _DTYPE_CODES[wf.dtype], nbf, nbr,
-                                                _lib.ptr(partial), _lib.ptr(record), maximum_iterations, relative_tolerance, chunk,
-                                                _lib.stream_ptr(dev))
-        _lib.check(st, "bgk_bar_solve_steps")
-        enqueued += chunk
-        host = record.cpu()
-        reads += 1
-        if int(host[R_PHASE]) == PHASE_DONE:
-            break
-        if enqueued > budget + chunk:
-            raise RuntimeError(f"bgk_bar_solve_steps: the record is not done after {enqueued} steps (budget {budget})")
+    record, host, reads = _driver.solve_record(enqueue, RECORD_DOUBLES, PHASE_DONE, budget, chunk, dev, "bgk_bar_solve_steps")
     return BARResult(record[R_RESULT].clone(), record[R_UNCERTAINTY].clone(), record[R_RESIDUAL].clone(), int(host[R_STATUS]),
                      int(host[R_N_EVAL]), int(host[R_N_EXPAND]), int(host[R_N_ITER]), reads)
 
 
 def _kernel_eligible(wf, wr):
-    return (wf.is_cuda and wf.device == wr.device and wf.dtype == wr.dtype and wf.dtype in _DTYPE_CODES
-            and not (torch.is_grad_enabled() and (wf.requires_grad or wr.requires_grad)))
+    grad = torch.is_grad_enabled()              # without it nothing is recorded, so inputs that require grad are taken too
+    return all(_driver.kernel_takes(w, any_layout=True, requires_grad_ok=not grad) for w in (wf, wr)) and _driver.same_kind((wf, wr))
 
 
 def bar_solve(forward_work, reverse_work, maximum_iterations=500, relative_tolerance=1e-12, path=None):
@@ -189,11 +179,8 @@ def bar_solve(forward_work, reverse_work, maximum_iterations=500, relative_toler
     maximum_iterations = int(maximum_iterations)
     if maximum_iterations <= 0:
         raise ValueError("bar_solve: maximum_iterations must be positive")
-    if path not in (None, "kernel", "torch"):
-        raise ValueError(f"bar_solve: unknown path {path!r}")
-    if path == "kernel" and not _kernel_eligible(wf, wr):
-        raise ValueError("bar_solve: the kernel path takes f32 or f64 work values of one dtype on one HIP device that do not require grad")
-    if path == "kernel" or (path is None and _kernel_eligible(wf, wr)):
+    if _driver.use_kernel(path, _kernel_eligible(wf, wr), "bar_solve",
+                          "f32 or f64 work values of one dtype on one HIP device that do not require grad"):
         return _bar_kernel(wf, wr, maximum_iterations, float(relative_tolerance))
     return _bar_torch(wf, wr, maximum_iterations, float(relative_tolerance))
 

@@ -36,7 +36,9 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _driver, _lib
+from ._driver import BUDGET, CONVERGED, NOT_A_NUMBER, R_STATUS      # NO_ROOT cannot happen here
+from ._driver import DTYPE_CODES as _DTYPE_CODES
 from .analysis import bar
 from .particles import HarmonicParticles, RepulsiveParticles
 from .sampling import GaussianMCMCSampler
@@ -44,8 +46,6 @@ from .sampling import GaussianMCMCSampler
 __all__ = ["UmbrellaModel", "UmbrellaSampling", "MetropolisGauss", "mbar_solve", "MBARResult", "biased_system"]
 
 MBARResult = namedtuple("MBARResult", ["f", "log_weights", "status", "iterations", "err"])
-
-CONVERGED, BUDGET, NOT_A_NUMBER = 0, 1, 3      # the status codes of free_energy.py; 2 (no root) cannot happen here
 
 MBAR_CHUNK = 32                # iterations enqueued per host read-back of the record (kernel path)
 MAX_WINDOWS = 256              # the kernel's envelope (one stage-2 thread per window); more windows take the torch path
@@ -55,9 +55,8 @@ TORCH_CHUNK_ELEMENTS = 1 << 22  # elements of the [samples, K] slices of the tor
 
 # the device record (f64), csrc/bgk_mbar.hip / include/bgflow_amd.h
 RECORD_DOUBLES = 8
-R_PHASE, R_STATUS, R_N_ITER, R_ERR, R_K, R_N = range(6)
+R_N_ITER, R_ERR, R_K, R_N = range(2, 6)      # after R_PHASE, R_STATUS
 PHASE_DONE = 1
-_DTYPE_CODES = {torch.float32: 0, torch.float64: 1}      # BGK_MBAR_F32 / BGK_MBAR_F64
 
 
 # ---- the estimator ---------------------------------------------------------------------------------------------------------------------
@@ -112,20 +111,15 @@ def _mbar_kernel(rc, table, maximum_iterations, tolerance, f0=None, n_blocks=Non
     nb = _blocks(n) if n_blocks is None else int(n_blocks)
     table = table.contiguous()
     f = torch.zeros(K, dtype=torch.float64, device=dev) if f0 is None else f0.to(device=dev, dtype=torch.float64).clone()
-    record = torch.zeros(RECORD_DOUBLES, dtype=torch.float64, device=dev)      # all zeros: the solver's start state
     partial = torch.empty(nb * K, dtype=torch.float64, device=dev)
-    code, enqueued = _DTYPE_CODES[rc.dtype], 0
-    while True:
-        with torch.cuda.device(dev):
-            st = _lib.lib().bgk_mbar_solve_steps(_lib.ptr(rc), n, code, _lib.ptr(table), K, nb, _lib.ptr(partial), _lib.ptr(f),
-                                                 _lib.ptr(record), maximum_iterations, tolerance, chunk, _lib.stream_ptr(dev))
-        _lib.check(st, "bgk_mbar_solve_steps")
-        enqueued += chunk
-        host = record.cpu()
-        if int(host[R_PHASE]) == PHASE_DONE:
-            break
-        if enqueued > maximum_iterations + chunk:
-            raise RuntimeError(f"bgk_mbar_solve_steps: the record is not done after {enqueued} iterations (budget {maximum_iterations})")
+    code = _DTYPE_CODES[rc.dtype]
+
+    def enqueue(record, n_steps):
+        return _lib.lib().bgk_mbar_solve_steps(_lib.ptr(rc), n, code, _lib.ptr(table), K, nb, _lib.ptr(partial), _lib.ptr(f),
+                                               _lib.ptr(record), maximum_iterations, tolerance, n_steps, _lib.stream_ptr(dev))
+
+    _, host, _ = _driver.solve_record(enqueue, RECORD_DOUBLES, PHASE_DONE, maximum_iterations, chunk, dev, "bgk_mbar_solve_steps",
+                                      unit="iterations")
     log_weights = torch.empty(n, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         st = _lib.lib().bgk_mbar_log_weights(_lib.ptr(rc), n, code, _lib.ptr(table), K, _lib.ptr(f), _lib.ptr(log_weights), _lib.stream_ptr(dev))
@@ -134,10 +128,7 @@ def _mbar_kernel(rc, table, maximum_iterations, tolerance, f0=None, n_blocks=Non
 
 
 def _kernel_eligible(trajs):
-    first = trajs[0]
-    return (len(trajs) <= MAX_WINDOWS and all(isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 1 and t.is_contiguous()
-                                              and t.dtype == first.dtype and t.device == first.device and not t.requires_grad for t in trajs)
-            and first.dtype in _DTYPE_CODES)
+    return len(trajs) <= MAX_WINDOWS and all(_driver.kernel_takes(t) for t in trajs) and _driver.same_kind(trajs)
 
 
 def _window_table(counts, centers, force_constants, temperature, device):
@@ -175,12 +166,8 @@ def mbar_solve(rc_trajs, centers, force_constants, temperature=1.0, maximum_iter
         raise ValueError("mbar_solve: maximum_iterations must be positive")
     if not float(tolerance) >= 0:
         raise ValueError("mbar_solve: the tolerance must be a number >= 0")
-    if path not in (None, "kernel", "torch"):
-        raise ValueError(f"mbar_solve: unknown path {path!r}")
-    eligible = _kernel_eligible(trajs)
-    if path == "kernel" and not eligible:
-        raise ValueError("mbar_solve: the kernel path takes contiguous 1-d f32 or f64 tensors of one dtype on one HIP device, at most "
-                         f"{MAX_WINDOWS} windows")
+    kernel = _driver.use_kernel(path, _kernel_eligible(trajs), "mbar_solve",
+                                f"contiguous 1-d f32 or f64 tensors of one dtype on one HIP device, at most {MAX_WINDOWS} windows")
     tensors = isinstance(trajs[0], torch.Tensor)
     if tensors:
         if any(not isinstance(t, torch.Tensor) or t.device != trajs[0].device for t in trajs):
@@ -189,7 +176,7 @@ def mbar_solve(rc_trajs, centers, force_constants, temperature=1.0, maximum_iter
     else:
         rc = torch.from_numpy(np.concatenate([np.asarray(t, np.float64).reshape(-1) for t in trajs]))
     table = _window_table(counts, centers, force_constants, temperature, rc.device)
-    if path == "kernel" or (path is None and eligible):
+    if kernel:
         return _mbar_kernel(rc.detach(), table, maximum_iterations, float(tolerance))
     r = _mbar_torch(rc.detach(), table, maximum_iterations, float(tolerance))
     return r if tensors else r._replace(f=r.f.numpy(), log_weights=r.log_weights.numpy())
