@@ -25,7 +25,19 @@
  * Envelope: bgk_pair_tile.h.  Dynamic LDS <= 63,488 B: rows per tile = the most (<= 64) with (round32(rows S) + rows S) 4 B within
  * it; lanes beyond the rows only stage and store:
  *   n d = 192 (S = 193): 41 rows, 63,396 B       LJ13 (S = 39): 64 rows, 19,968 B       DW4 (S = 9): 64 rows, 4,608 B
- *   the particle box of 38 particles (S = 77): 64 rows, 39,424 B       of 64 particles (S = 129): 61 rows, 62,964 B */
+ *   the particle box of 38 particles (S = 77): 64 rows, 39,424 B       of 64 particles (S = 129): 61 rows, 62,964 B
+ *
+ * Replica exchange (EXCHANGE = true; entries bgk_pair_remc / bgk_box_remc; ReplicaExchangeMetropolisGauss.run,
+ * distribution/sampling/_mcmc/metropolis.py:172-188): the B chains are L ladders of K temperatures, ladder-major -- chain b is slot
+ * b % K of ladder b / K -- and a tile holds whole ladders (rows = the plain kernel's rounded down to a multiple of K), so a ladder is K
+ * neighbouring lanes.  After the Metropolis part of every exchange_every-th step the pairs of slots (k, k + 1), k = parity (mod 2), try
+ *   c = -(e[k+1] - e[k]) (1 / T[k+1] - 1 / T[k]),  exchange iff -log r > c   (f32; false for a NaN on either side),
+ * r the number of the pair's LOWER slot: row j of exchange_uniforms for the j-th exchange of the launch, or Philox field 2 -- counter
+ * (global chain, 2 << 20, offset + step), word 0 -- next to fields 0 and 1 above.  The parity flips after every attempt.  An exchange moves
+ * no data: the lane keeps `row`, the LDS row that holds its state (both tiles), next to `cur`, and two lanes swap (row, cur, e, walker) by
+ * wave shuffles; the rows of a tile stay a permutation of its rows, so the banks stay distinct.  Temperatures, n_accepted and n_exchanged
+ * (counted at the lower slot) belong to the slot.  The exchange condition is uniform over the wave and every lane executes the shuffles.
+ * A frame due at the same step is recorded BEFORE the exchange.  Tile heights: floor(rows / K) K, e.g. K = 5: 40 rows at n d = 192. */
 #include "bgk_common.h"
 #include "bgk_pair_terms.h"
 #include "bgk_philox.h"
@@ -44,18 +56,35 @@ struct McArgs {
     uint32_t seed_lo, seed_hi, offset;
     float* traj; float* traj_e; int traj_every;
     int* n_accepted; int accumulate;
+    /* replica exchange (EXCHANGE kernels only) */
+    int n_replicas, ex_every, ex_phase, ex_parity;
+    const float* ex_uniforms; int* n_exchanged; int* walkers;
 };
 
-/* tile_store of every row's CURRENT state: s_sel[r] says which of the two tiles holds it; dst: the tile's first row in contiguous rows */
+/* tile_store of every row's CURRENT state: s_sel[r] says which of the two tiles holds it (EXCHANGE: bit 0, and the bits above which
+ * LDS row holds slot r's state); dst: the tile's first row in contiguous rows */
+template <bool EXCHANGE>
 __device__ __forceinline__ void mc_store_current(const McArgs& a, float* dst, int rows, const int* s_sel, const float* s_mem) {
     const int nd = a.t.nd, S = nd | 1;
     for (int i = threadIdx.x; i < rows * nd; i += BGK_TILE_THREADS) {
         const int r = (int)__umulhi((unsigned)i, a.t.magic), c = i - r * nd;
-        dst[i] = s_mem[(s_sel[r] ? a.tile_b : 0) + r * S + c];
+        if constexpr (EXCHANGE) {
+            const int sel = s_sel[r];
+            dst[i] = s_mem[((sel & 1) ? a.tile_b : 0) + (sel >> 1) * S + c];
+        } else {
+            dst[i] = s_mem[(s_sel[r] ? a.tile_b : 0) + r * S + c];
+        }
     }
 }
 
-template <int D, int KIND>
+/* v of this lane after the exchanges of a step: the upper neighbour's if this lane exchanges upwards, the lower one's if downwards */
+template <class T>
+__device__ __forceinline__ T mc_exchanged(T v, bool up, bool down) {
+    const T above = __shfl_down(v, 1), below = __shfl_up(v, 1);
+    return up ? above : (down ? below : v);
+}
+
+template <int D, int KIND, bool EXCHANGE>
 __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_mcmc_kernel(McArgs a) {
     extern __shared__ float s_mem[];
     __shared__ int s_sel[BGK_TILE_THREADS];             /* which tile holds row r's current state */
@@ -76,11 +105,23 @@ __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_mcmc_kernel(McArgs a) {
             temp = a.temperatures ? a.temperatures[b] : a.temperature;
             e = a.e_valid ? a.e[b] : (float)bgk_row_energy<D, KIND>(s_mem + tid * S, a.t);
         }
+        /* EXCHANGE: row = the LDS row of this slot's state; slot = tid % K (tiles start at multiples of K); d_beta = 1 / T of the slot
+         * above minus this slot's; ex_since / parity / n_ex: the schedule, the same for every tile */
+        int row = tid, slot = 0, walker = 0, exch = 0, ex_since = 0, parity = 0, n_ex = 0;
+        float d_beta = 0.0f;
+        if constexpr (EXCHANGE) {
+            slot = tid % a.n_replicas;
+            walker = (active && a.walkers) ? a.walkers[b] : slot;
+            const float beta = 1.0f / temp;
+            d_beta = __shfl_down(beta, 1) - beta;
+            ex_since = a.ex_phase; parity = a.ex_parity;
+        }
         int frame = 0, since = 0;
         for (int step = 0; step < a.n_steps; ++step) {
             if (active) {
-                const float* xc = s_mem + (cur ? a.tile_b : 0) + tid * S;
-                float* xp = s_mem + (cur ? 0 : a.tile_b) + tid * S;
+                const int lrow = EXCHANGE ? row : tid;
+                const float* xc = s_mem + (cur ? a.tile_b : 0) + lrow * S;
+                float* xp = s_mem + (cur ? 0 : a.tile_b) + lrow * S;
                 float r;
                 if (a.noise) {
                     const float* ns = a.noise + ((int64_t)step * a.B + b) * nd;
@@ -110,20 +151,57 @@ __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_mcmc_kernel(McArgs a) {
             }
             if (a.traj && ++since == a.traj_every) {    /* uniform over the wave */
                 since = 0;
-                s_sel[tid] = cur;
+                s_sel[tid] = EXCHANGE ? (cur | (row << 1)) : cur;
                 __syncthreads();
-                mc_store_current(a, a.traj + ((int64_t)frame * a.B + b0) * nd, rows, s_sel, s_mem);
+                mc_store_current<EXCHANGE>(a, a.traj + ((int64_t)frame * a.B + b0) * nd, rows, s_sel, s_mem);
                 if (active && a.traj_e) a.traj_e[(int64_t)frame * a.B + b] = e;
                 ++frame;
                 __syncthreads();                        /* the next proposals overwrite rows this store reads */
             }
+            if constexpr (EXCHANGE) {
+                if (++ex_since == a.ex_every) {         /* uniform over the wave; every lane runs the shuffles */
+                    ex_since = 0;
+                    const bool lower = active && (slot & 1) == parity && slot + 1 < a.n_replicas;      /* its upper slot is active too */
+                    const float e_up = __shfl_down(e, 1);
+                    bool up = false;
+                    if (lower) {
+                        float r;
+                        if (a.noise) {
+                            r = a.ex_uniforms[(int64_t)n_ex * a.B + b];
+                        } else {
+                            uint32_t o[4];
+                            philox4x32_10(r_lo, r_hi, 2u << 20, a.offset + (uint32_t)step, a.seed_lo, a.seed_hi, o);
+                            r = u01(o[0]);
+                        }
+                        const float c = -(e_up - e) * d_beta;
+                        up = -bgk_logf(r) > c;          /* false for a NaN on either side */
+                    }
+                    const bool down = __shfl_up((int)up, 1) != 0 && slot >= 1 && ((slot - 1) & 1) == parity;
+                    e = mc_exchanged(e, up, down);
+                    cur = mc_exchanged(cur, up, down);
+                    row = mc_exchanged(row, up, down);
+                    walker = mc_exchanged(walker, up, down);
+                    /* from here a lane reads and writes the LDS rows its partner wrote: ordered because the workgroup is ONE wave,
+                     * whose LDS accesses execute in issue order; the fence keeps the compiler from moving accesses across the exchange */
+                    static_assert(BGK_TILE_THREADS == 64, "the exchange relies on one wave per workgroup: more waves need a barrier here");
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    exch += up ? 1 : 0;
+                    parity ^= 1;
+                    ++n_ex;
+                }
+            }
         }
-        s_sel[tid] = cur;
+        s_sel[tid] = EXCHANGE ? (cur | (row << 1)) : cur;
         __syncthreads();
-        mc_store_current(a, a.x + b0 * nd, rows, s_sel, s_mem);
+        mc_store_current<EXCHANGE>(a, a.x + b0 * nd, rows, s_sel, s_mem);
         if (active) {
             a.e[b] = e;
             if (a.n_accepted) a.n_accepted[b] = a.accumulate ? a.n_accepted[b] + acc : acc;
+            if constexpr (EXCHANGE) {
+                if (a.n_exchanged) a.n_exchanged[b] = a.accumulate ? a.n_exchanged[b] + exch : exch;
+                if (a.walkers) a.walkers[b] = walker;
+            }
         }
         __syncthreads();
     }
@@ -138,6 +216,9 @@ struct BgkMcmcCall {
     uint64_t seed; uint32_t offset; int64_t row0;
     float* traj; float* traj_e; int32_t traj_every; int32_t* n_accepted; int32_t accumulate;
     void* stream;
+    /* replica exchange (the *_remc entries; n_replicas = 0: the plain kernel) */
+    int32_t n_replicas, exchange_every, exchange_phase, exchange_parity;
+    const float* exchange_uniforms; int32_t* n_exchanged; int32_t* walkers;
 };
 
 int mcmc_run(const BgkMcmcCall& c) {
@@ -151,12 +232,31 @@ int mcmc_run(const BgkMcmcCall& c) {
     BGK_CHECK_ARG((c.noise != nullptr) == (c.uniforms != nullptr), "%s: noise and uniforms go together", what);
     BGK_CHECK_ARG(!c.traj_e || c.traj, "%s: traj_e without traj", what);
     BGK_CHECK_ARG(!c.traj || c.traj_every >= 1, "%s: traj_every %d", what, c.traj_every);
-    if (c.B == 0) return 0;
-    BGK_CHECK_ARG(c.x && c.e, "%s: null tensor", what);
-    a.x = c.x; a.B = c.B; a.row0 = c.row0;
+    const bool exchange = c.n_replicas != 0;
+    if (exchange) {
+        BGK_CHECK_ARG(c.n_replicas >= 2, "%s: n_replicas %d (at least 2)", what, c.n_replicas);
+        BGK_CHECK_ARG(c.exchange_every >= 1 && c.exchange_phase >= 0 && c.exchange_phase < c.exchange_every,
+                      "%s: exchange_every %d / exchange_phase %d (0 <= phase < every)", what, c.exchange_every, c.exchange_phase);
+        BGK_CHECK_ARG(c.exchange_parity == 0 || c.exchange_parity == 1, "%s: exchange_parity %d", what, c.exchange_parity);
+        BGK_CHECK_ARG(c.B % c.n_replicas == 0 && c.row0 % c.n_replicas == 0, "%s: the batch size and row0 must be multiples of n_replicas", what);
+        const int64_t n_exchanges = ((int64_t)c.exchange_phase + c.n_steps) / c.exchange_every;
+        BGK_CHECK_ARG(n_exchanges == 0 || (c.noise != nullptr) == (c.exchange_uniforms != nullptr),
+                      "%s: noise, uniforms and exchange_uniforms go together", what);
+    }
     const int S = a.t.nd | 1;
     int rows = rows_within(MC_LDS_DYNAMIC, 2 * S * (int)sizeof(float));
     while ((((rows * S + 31) & ~31) + rows * S) * (int)sizeof(float) > MC_LDS_DYNAMIC) --rows;     /* the second tile starts at round32 */
+    if (exchange) {                                         /* the envelope of K, whatever the batch (an empty one included) */
+        if (c.n_replicas > rows) {
+            bgk_set_error("%s: %d replicas are more than the %d rows of a tile of this target", what, c.n_replicas, rows);
+            return BGK_EUNSUPPORTED;
+        }
+        rows = rows / c.n_replicas * c.n_replicas;          /* a tile holds whole ladders */
+    }
+    if (c.B == 0) return 0;
+    BGK_CHECK_ARG(c.x && c.e, "%s: null tensor", what);
+    BGK_CHECK_ARG(!exchange || c.temperatures, "%s: replica exchange needs temperatures [B]", what);
+    a.x = c.x; a.B = c.B; a.row0 = c.row0;
     a.rows = rows; a.tile_b = (rows * S + 31) & ~31;
     a.e = c.e; a.e_valid = c.e_valid != 0; a.temperature = (float)c.temperature; a.temperatures = c.temperatures;
     a.noise_std = (float)c.noise_std; a.n_steps = c.n_steps; a.noise = c.noise; a.uniforms = c.uniforms;
@@ -165,7 +265,13 @@ int mcmc_run(const BgkMcmcCall& c) {
     const size_t lds = (size_t)(a.tile_b + rows * S) * sizeof(float);
     const int grid = tile_grid(c.B, rows);
     hipStream_t s = (hipStream_t)c.stream;
-    tile_dispatch<true>(c.spec.kind, c.spec.n_dims, [&](auto D, auto K) { tile_launch(pair_mcmc_kernel<D(), K()>, grid, lds, s, a); });
+    if (exchange) {
+        a.n_replicas = c.n_replicas; a.ex_every = c.exchange_every; a.ex_phase = c.exchange_phase; a.ex_parity = c.exchange_parity;
+        a.ex_uniforms = c.exchange_uniforms; a.n_exchanged = c.n_exchanged; a.walkers = c.walkers;
+        tile_dispatch<true>(c.spec.kind, c.spec.n_dims, [&](auto D, auto K) { tile_launch(pair_mcmc_kernel<D(), K(), true>, grid, lds, s, a); });
+    } else {
+        tile_dispatch<true>(c.spec.kind, c.spec.n_dims, [&](auto D, auto K) { tile_launch(pair_mcmc_kernel<D(), K(), false>, grid, lds, s, a); });
+    }
     return bgk_launch_status(what);
 }
 
@@ -192,4 +298,34 @@ extern "C" int bgk_box_mcmc(float* x, int64_t B, int32_t n_particles, int32_t ki
     return mcmc_run({bgk_box_spec("bgk_box_mcmc", n_particles, kind, params, n_params), x, B,
                      e, e_valid, temperature, temperatures, noise_std, n_steps, noise, uniforms, seed, offset, row0,
                      traj, traj_e, traj_every, n_accepted, accumulate, stream});
+}
+
+/* replica exchange inside the chain kernel (the head comment's last part): the arguments of the *_mcmc entry, then the exchange's */
+extern "C" int bgk_pair_remc(float* x, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
+                             double p0, double p1, double p2, double p3, double osc_scale,
+                             float* e, int32_t e_valid, double temperature, const float* temperatures,
+                             double noise_std, int32_t n_steps, const float* noise, const float* uniforms,
+                             uint64_t seed, uint32_t offset, int64_t row0,
+                             float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream,
+                             int32_t n_replicas, int32_t exchange_every, int32_t exchange_phase, int32_t exchange_parity,
+                             const float* exchange_uniforms, int32_t* n_exchanged, int32_t* walkers) {
+    if (n_replicas == 0) n_replicas = -1;               /* 0 means "the plain kernel" inside mcmc_run: refused here like any K < 2 */
+    return mcmc_run({bgk_pair_spec("bgk_pair_remc", n_particles, n_dims, kind, p0, p1, p2, p3, osc_scale), x, B,
+                     e, e_valid, temperature, temperatures, noise_std, n_steps, noise, uniforms, seed, offset, row0,
+                     traj, traj_e, traj_every, n_accepted, accumulate, stream,
+                     n_replicas, exchange_every, exchange_phase, exchange_parity, exchange_uniforms, n_exchanged, walkers});
+}
+
+extern "C" int bgk_box_remc(float* x, int64_t B, int32_t n_particles, int32_t kind, const float* params, int32_t n_params,
+                            float* e, int32_t e_valid, double temperature, const float* temperatures,
+                            double noise_std, int32_t n_steps, const float* noise, const float* uniforms,
+                            uint64_t seed, uint32_t offset, int64_t row0,
+                            float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream,
+                            int32_t n_replicas, int32_t exchange_every, int32_t exchange_phase, int32_t exchange_parity,
+                            const float* exchange_uniforms, int32_t* n_exchanged, int32_t* walkers) {
+    if (n_replicas == 0) n_replicas = -1;
+    return mcmc_run({bgk_box_spec("bgk_box_remc", n_particles, kind, params, n_params), x, B,
+                     e, e_valid, temperature, temperatures, noise_std, n_steps, noise, uniforms, seed, offset, row0,
+                     traj, traj_e, traj_every, n_accepted, accumulate, stream,
+                     n_replicas, exchange_every, exchange_phase, exchange_parity, exchange_uniforms, n_exchanged, walkers});
 }

@@ -11,7 +11,10 @@ The fused path (csrc/bgk_mcmc.hip, entries bgk_pair_mcmc / bgk_box_mcmc) runs wh
 step (and whose ``extract_sample_hook`` is the default) runs ``stride * n_steps`` steps per iteration inside the launch and has the kernel
 write every recorded state straight into the ``[n, B, ...]`` result.  ``MCMCStep.fused = False`` forces the general path.
 
-Not in the reference: ``MCMCStep.n_accepted`` (per-chain accepted steps) / ``n_proposed``, ``MCMCStep.feed_noise`` and ``chain_offset``.
+Not in the reference: ``MCMCStep.n_accepted`` (per-chain accepted steps) / ``n_proposed``, ``MCMCStep.feed_noise`` and ``chain_offset``;
+``ReplicaExchangeMCMCStep`` / ``ReplicaExchangeSampler`` -- parallel tempering over ladders of temperatures with the exchange rule of the
+reference's numpy ``ReplicaExchangeMetropolisGauss`` (_mcmc/metropolis.py:138-188; its numpy port is in umbrella.py), fused as entries
+bgk_pair_remc / bgk_box_remc of the same kernel: the exchange is a swap of row index, tile flag and energy between two lanes.
 """
 import dataclasses
 import warnings
@@ -24,12 +27,14 @@ from .particles import _check_tensors, _target_args
 from .utils import pack_tensor_in_list, pack_tensor_in_tuple, unpack_tensor_tuple
 
 __all__ = ["AbstractSamplerState", "SamplerState", "SamplerStep", "IterativeSampler", "GaussianProposal", "LatentProposal", "MCMCStep",
-           "GaussianMCMCSampler", "metropolis_accept", "default_set_samples_hook", "default_extract_sample_hook"]
+           "GaussianMCMCSampler", "metropolis_accept", "default_set_samples_hook", "default_extract_sample_hook",
+           "ReplicaExchangeMCMCStep", "ReplicaExchangeSampler", "exchange_permutation", "mcmc_tile_rows"]
 
 # The most Metropolis steps one launch of bgk_pair_mcmc runs; longer runs are split (bitwise the same chain: the random stream and the
 # carried f32 energies do not depend on the split), so that no single launch holds a shared GPU for long.  Measured on an MI355X
 # (tools/mcmc_time.py, its last line): the widest shape of the envelope -- Lennard-Jones, n = 64, d = 3, 2^16 chains -- takes 70.46 ms
-# for one launch of 64 steps (70.29 .. 70.74 over three rounds), 1.10 ms per step, so 224 steps are 0.247 s.
+# for one launch of 64 steps (70.29 .. 70.74 over three rounds), 1.10 ms per step, so 224 steps are 0.247 s.  The replica-exchange
+# launches (bgk_pair_remc) reuse it: tools/remc_time.py measured 1.07 ms per step at that shape with an exchange after every step.
 MCMC_MAX_STEPS_PER_LAUNCH = 224
 
 
@@ -143,12 +148,19 @@ class SamplerState(AbstractSamplerState):
 
 # ---- the kernel launch ------------------------------------------------------------------------------------------------------------
 def pair_mcmc(plan, x, e, e_valid, temperature, noise_std, n_steps, noise=None, uniforms=None, seed=0, offset=0, row0=0,
-              traj=None, traj_e=None, traj_every=0, n_accepted=None, accumulate=False):
+              traj=None, traj_e=None, traj_every=0, n_accepted=None, accumulate=False, n_replicas=0, exchange_every=1,
+              exchange_phase=0, exchange_parity=0, exchange_uniforms=None, n_exchanged=None, walkers=None):
     """One launch of bgk_pair_mcmc (bgk_box_mcmc for a ``BoxPlan``): ``n_steps`` Metropolis steps of the chains x [B, n d] (f32,
     contiguous, HIP; updated IN PLACE) on the target of the plan.  e [B]: raw energies (temperature 1), read if ``e_valid``, written for the final state.
     ``temperature``: a positive number or an f32 tensor [B].  noise [n_steps, B, n d] and uniforms [n_steps, B], or neither (Philox
     numbers of (seed, offset + step, chain row0 + b)).  traj [n_steps // traj_every, B, n d] / traj_e [n_steps // traj_every, B]: the
-    state / energy after every ``traj_every``-th step.  n_accepted [B] (int32): written, or added to with ``accumulate``."""
+    state / energy after every ``traj_every``-th step.  n_accepted [B] (int32): written, or added to with ``accumulate``.
+
+    With ``n_replicas`` K >= 2 the launch is bgk_pair_remc / bgk_box_remc: the chains are B / K ladders of K temperatures, ladder-major,
+    ``temperature`` is the tensor [B], and after every step that completes an epoch of ``exchange_every`` steps (``exchange_phase`` of
+    which were taken before the launch) the pairs of slots (k, k + 1), k = parity (mod 2), try an exchange; ``exchange_parity`` is the
+    first attempt's.  exchange_uniforms [(exchange_phase + n_steps) // exchange_every, B]: with noise / uniforms, all or none.
+    n_exchanged [B] (int32): accepted exchanges at the pair's lower slot, like n_accepted; walkers [B] (int32, in / out)."""
     from . import _lib
     B, nd = x.shape
     if nd != plan.n_particles * plan.n_dims:
@@ -162,13 +174,31 @@ def pair_mcmc(plan, x, e, e_valid, temperature, noise_std, n_steps, noise=None, 
     _check_tensors("pair_mcmc", x, [(n_accepted, (B,))], dtype=torch.int32)
     if traj is not None and traj_every < 1:
         raise ValueError("pair_mcmc: traj_every must be at least 1")
-    name = "bgk_box_mcmc" if isinstance(plan, BoxPlan) else "bgk_pair_mcmc"
+    name = "bgk_box_" if isinstance(plan, BoxPlan) else "bgk_pair_"
+    more = ()
+    if n_replicas:
+        if temps is None:
+            raise ValueError("pair_mcmc: replica exchange needs a tensor of B temperatures")
+        if exchange_every < 1 or not 0 <= exchange_phase < exchange_every:
+            raise ValueError("pair_mcmc: exchange_every must be at least 1 and 0 <= exchange_phase < exchange_every")
+        n_exchanges = (exchange_phase + n_steps) // exchange_every
+        if n_exchanges == 0:
+            exchange_uniforms = None
+        elif (noise is None) != (exchange_uniforms is None):
+            raise ValueError("pair_mcmc: noise, uniforms and exchange_uniforms go together")
+        _check_tensors("pair_mcmc", x, [(exchange_uniforms, (n_exchanges, B))])
+        _check_tensors("pair_mcmc", x, [(n_exchanged, (B,)), (walkers, (B,))], dtype=torch.int32)
+        more = (int(n_replicas), int(exchange_every), int(exchange_phase), int(exchange_parity), _lib.ptr(exchange_uniforms),
+                _lib.ptr(n_exchanged), _lib.ptr(walkers))
+    elif exchange_uniforms is not None or n_exchanged is not None or walkers is not None:
+        raise ValueError("pair_mcmc: exchange arguments without n_replicas")
+    name += "remc" if n_replicas else "mcmc"
     with torch.cuda.device(x.device):
         st = getattr(_lib.lib(), name)(_lib.ptr(x), B, *_target_args(plan), _lib.ptr(e), int(bool(e_valid)),
                                        1.0 if temps is not None else float(temperature),
                                        _lib.ptr(temps), float(noise_std), int(n_steps), _lib.ptr(noise), _lib.ptr(uniforms),
                                        int(seed) & (2 ** 64 - 1), int(offset) & 0xffffffff, int(row0), _lib.ptr(traj), _lib.ptr(traj_e),
-                                       int(traj_every), _lib.ptr(n_accepted), int(bool(accumulate)), _lib.stream_ptr(x.device))
+                                       int(traj_every), _lib.ptr(n_accepted), int(bool(accumulate)), _lib.stream_ptr(x.device), *more)
     _lib.check(st, name)
 
 
@@ -388,7 +418,8 @@ class MCMCStep(SamplerStep, _FusedSampling):
                 fed[2] += steps
             pair_mcmc(plan, x2, e, e_valid, temps, self.proposal._noise_std, steps, noise, uniforms, seed, offset, self.chain_offset,
                       None if not frames else traj[frame:frame + frames].view(frames, B, -1),
-                      None if not frames or traj_e is None else traj_e[frame:frame + frames], every, self.n_accepted, not fresh)
+                      None if not frames or traj_e is None else traj_e[frame:frame + frames], every, self.n_accepted, not fresh,
+                      **self._begin_launch(steps, x2, fresh))
             e_valid, fresh = True, False
             offset += steps
             frame += frames
@@ -397,16 +428,31 @@ class MCMCStep(SamplerStep, _FusedSampling):
                 tick(done)
         self.n_proposed += total
 
-    def _fused_forward(self, state, setup, n_steps):
-        plan, B, _ = setup
+    def _begin_launch(self, steps, x2, fresh):
+        """called before every launch of ``steps`` steps; returns further keywords of ``pair_mcmc`` (a subclass advances its own
+        schedule here: the replica exchange)"""
+        return {}
+
+    def _hand_out(self, state, x2, e):
+        """called with the state a fused run hands out and the working chains it came from (a subclass may keep them)"""
+
+    def _working_copy(self, state, B):
+        """(x [B, n d], e [B], e_valid): the chains of a state as the launches advance them in place -- a copy of the samples and, if
+        they are up to date, of the energies"""
         x = state.__dict__["_data"].samples[0]
-        y = x.detach().clone()
         e = self._carried_energies(state, B)
         e_valid = e is not None
         if e is None:
             e = torch.empty(B, dtype=torch.float32, device=x.device)
-        self._run_chains(setup, y.view(B, -1), e, e_valid, [(k, 0, 0) for k in _split(n_steps, MCMC_MAX_STEPS_PER_LAUNCH)])
-        return _advanced_state(state, y, e)
+        return x.detach().clone().view(B, -1), e, e_valid
+
+    def _fused_forward(self, state, setup, n_steps):
+        plan, B, _ = setup
+        y, e, e_valid = self._working_copy(state, B)
+        self._run_chains(setup, y, e, e_valid, [(k, 0, 0) for k in _split(n_steps, MCMC_MAX_STEPS_PER_LAUNCH)])
+        out = _advanced_state(state, y.view(state.__dict__["_data"].samples[0].shape), e)
+        self._hand_out(out, y, e)
+        return out
 
     def forward(self, state):
         setup = self._fused_setup(state)
@@ -418,6 +464,277 @@ class MCMCStep(SamplerStep, _FusedSampling):
 def _split(total, cap):
     cap = max(1, int(cap))
     return [min(cap, total - s) for s in range(0, total, cap)]
+
+
+# ---- replica exchange --------------------------------------------------------------------------------------------------------------
+def mcmc_tile_rows(nd):
+    """rows of a tile of the chain kernel for rows of ``nd`` floats (csrc/bgk_mcmc.hip, ``mcmc_run``): the most, at most 64, whose two
+    LDS tiles (odd row stride, the second one starting at a multiple of 32 words) fit 63,488 bytes"""
+    S = nd | 1
+    rows = min(64, 63488 // (8 * S))
+    while (((rows * S + 31) & ~31) + rows * S) * 4 > 63488:
+        rows -= 1
+    return rows
+
+
+def exchange_permutation(energies, temperatures, r, n_replicas, parity):
+    """The exchange rule of ``ReplicaExchangeMetropolisGauss.run`` (_mcmc/metropolis.py:172-188) for L ladders at once: energies,
+    temperatures, r [B = L K], ladder-major.  For every pair of slots (k, k + 1) with k = parity (mod 2) and k + 1 < K
+    c = -(e[k+1] - e[k]) (1 / T[k+1] - 1 / T[k]), and the pair exchanges iff -log r > c, r the entry of its lower slot (a NaN never
+    exchanges).  Returns (perm [B]: the chain that sits in each slot afterwards, lower [P]: the pairs' lower slots, swap [P])."""
+    B, K = energies.shape[0], int(n_replicas)
+    dev = energies.device
+    lower = (torch.arange(0, B, K, device=dev)[:, None] + torch.arange(parity, K - 1, 2, device=dev)[None, :]).reshape(-1)
+    upper = lower + 1
+    beta = 1.0 / temperatures
+    c = -(energies[upper] - energies[lower]) * (beta[upper] - beta[lower])
+    swap = -torch.log(r[lower]) > c
+    perm = torch.arange(B, device=dev)
+    perm[lower] = torch.where(swap, upper, lower)
+    perm[upper] = torch.where(swap, lower, upper)
+    return perm, lower, swap
+
+
+class ReplicaExchangeMCMCStep(MCMCStep):
+    """Parallel tempering: Metropolis Monte Carlo of L ladders of K = len(temperatures) replicas -- the state's B = L K chains,
+    ladder-major: chain b is slot b % K of ladder b / K and runs at ``temperatures[b % K]`` -- with an exchange attempt between
+    neighbouring slots after every ``exchange_every``-th step (``exchange_permutation``: the rule of the reference's numpy
+    ``ReplicaExchangeMetropolisGauss``, pairs (0, 1), (2, 3), ... and (1, 2), (3, 4), ... in turn).  An exchange swaps configuration and
+    energy of two slots; temperatures and counters belong to the slot.
+
+    The schedule follows ``steps_done`` (an int, assignable; not the Philox counter): an exchange follows every step that makes it a
+    multiple of ``exchange_every``, with parity ``(steps_done // exchange_every - 1) & 1``.  The exchange FOLLOWS the frame of its step:
+    the state ``forward`` returns (and an ``IterativeSampler`` records) after such a step is the one before the exchange, which is
+    applied when the chains continue -- ``apply_pending_exchange(state)`` applies it at the end of a run.
+
+    ``n_exchanged`` (int32 [B]) counts the accepted exchanges of pair (k, k + 1) at its lower slot, ``n_exchange_attempts`` the exchange
+    steps, ``walkers`` (int32 [B]) says which walker (0..K-1 of its ladder, by its start slot) sits in each slot.
+
+    General path (any energy with energies [B], proposal, device, dtype): ``MCMCStep._step`` and the exchange in torch ops; every
+    exchange makes exactly one ``torch.rand_like(energies)`` call and uses the entry at each pair's lower slot.  Fused path
+    (bgk_pair_remc / bgk_box_remc, the exchange by wave shuffles inside the chain kernel): under the conditions of ``MCMCStep``'s, K within
+    the kernel's tile height (``mcmc_tile_rows``) and ``chain_offset`` a multiple of K.  There the due exchange of a run's last step has
+    already happened in the working chains the step keeps for the state it handed out (``_HandedOut``; ``forward`` and
+    ``IterativeSampler`` both register their runs), and in ``walkers`` / ``n_exchanged`` / ``n_exchange_attempts``.  Continuing from that
+    state, or ``apply_pending_exchange`` of it, uses those chains.  A state from elsewhere gets the exchange in torch ops instead, and the
+    kernel's exchange is taken out of ``walkers`` and the counters again, so that they describe the chains that go on."""
+
+    def __init__(self, target_energy, temperatures, proposal=GaussianProposal(), n_steps=1, exchange_every=1):
+        ladder = temperatures.detach().reshape(-1) if torch.is_tensor(temperatures) else torch.as_tensor(temperatures, dtype=torch.float64).reshape(-1)
+        if ladder.numel() < 2 or not ladder.dtype.is_floating_point or not bool((ladder > 0).all()) or not bool(torch.isfinite(ladder).all()):
+            raise ValueError("ReplicaExchangeMCMCStep: temperatures must be at least two positive numbers")
+        if not isinstance(exchange_every, int) or exchange_every < 1:
+            raise ValueError("ReplicaExchangeMCMCStep: exchange_every must be a positive integer")
+        super().__init__(target_energy, proposal=proposal, target_temperatures=ladder, n_steps=n_steps)
+        self.temperatures = ladder
+        self.n_replicas = ladder.numel()
+        self.exchange_every = exchange_every
+        self.steps_done = 0
+        self.n_exchanged = None
+        self.n_exchange_attempts = 0
+        self.walkers = None
+        self._applied_at = 0           # the value of ``steps_done`` whose exchange the states handed out have (``_exchange_due``)
+        self._handed = None            # _HandedOut: the fused path's working chains of the state handed out last
+        self._run = None               # inside ``_run_chains``: [steps left, counters before the run's last launch]
+        self._before_last = None       # those counters, from the end of a run that ended with an exchange until ``_hand_out``
+        self._tiled = None
+
+    def _exchange_due(self):
+        """the exchange after step ``steps_done`` is due and the state handed out does not have it -- also true for an object that was
+        assigned a ``steps_done`` at the end of an epoch: it continues a run whose last state is the one before that exchange"""
+        return self.steps_done > 0 and self.steps_done % self.exchange_every == 0 and self._applied_at != self.steps_done
+
+    # -- bookkeeping
+    def _tile(self, x):
+        """the ladder tiled over the batch of x, in x's dtype on x's device (kept while these do not change)"""
+        B, K = x.shape[0], self.n_replicas
+        if B % K != 0:
+            raise ValueError(f"ReplicaExchangeMCMCStep: {B} chains are not a whole number of ladders of {K} temperatures")
+        dtype = x.dtype if x.dtype.is_floating_point else torch.get_default_dtype()
+        key = (B, x.device, dtype)
+        if self._tiled is None or self._tiled[0] != key:
+            self._tiled = (key, self.temperatures.to(device=x.device, dtype=dtype).repeat(B // K))
+        return self._tiled[1]
+
+    def _book(self, B, device, reset=False):
+        if reset or self.n_exchanged is None or self.n_exchanged.shape != (B,) or self.n_exchanged.device != device:
+            self.n_exchanged = torch.zeros(B, dtype=torch.int32, device=device)
+        if self.walkers is None or self.walkers.shape != (B,) or self.walkers.device != device:
+            self.walkers = torch.arange(self.n_replicas, dtype=torch.int32, device=device).repeat(B // self.n_replicas)
+
+    @staticmethod
+    def _first_samples(state):
+        return state.__dict__["_data"].samples[0] if isinstance(state, SamplerState) else state.as_dict()["samples"][0]
+
+    # -- the general path
+    def _exchange(self, state):
+        """the exchange that is due, in torch ops"""
+        self._applied_at = self.steps_done
+        state = state.evaluate_energy_force(self.target_energy, evaluate_forces=False)
+        data = state.as_dict()
+        e = data["energies"]
+        if e.dim() != 1:
+            raise ValueError("ReplicaExchangeMCMCStep: the energies of the state must be one per chain, [B]")
+        temps = self._tile(e)
+        parity = (self.steps_done // self.exchange_every - 1) & 1
+        r = torch.rand_like(e)
+        perm, lower, swap = exchange_permutation(e, temps, r, self.n_replicas, parity)
+        self._book(e.shape[0], e.device)
+        self.n_exchanged[lower] += swap.to(torch.int32)
+        self.walkers = self.walkers[perm]
+        self.n_exchange_attempts += 1
+        moved = {"samples": tuple(x[perm] for x in data["samples"]), "energies": e[perm]}
+        if data.get("velocities") is not None:
+            moved["velocities"] = tuple(v[perm] for v in data["velocities"])
+        return state.replace(**moved)
+
+    def _step(self, state):
+        self.target_temperatures = self._tile(self._first_samples(state))
+        state = self.apply_pending_exchange(state)
+        self._handed = None
+        state = super()._step(state)
+        self.steps_done += 1
+        return state
+
+    def apply_pending_exchange(self, state):
+        """the state with the exchange that is due after the last step, if there is one (``forward`` returns the state before it).  For
+        the state the fused path handed out last that is a copy of its working chains, where the kernel has made the exchange; any other
+        state is exchanged in torch ops, after the kernel's exchange has been taken out of ``walkers`` and the counters again."""
+        if not self._exchange_due():
+            return state
+        handed = self._handed
+        if handed is not None and handed.state is state:
+            self._applied_at = self.steps_done
+            handed.state = _advanced_state(state, handed.x.clone().view(self._first_samples(state).shape), handed.e.clone())
+            return handed.state                        # the working chains now belong to this state: it has the exchange
+        self._take_back()
+        return self._exchange(state)
+
+    # -- the fused path
+    def feed_noise(self, noise, uniforms, exchange_uniforms=None):
+        """as ``MCMCStep.feed_noise``, with exchange_uniforms [X, B]: every exchange consumes one row (its entries at the pairs' lower
+        slots); all three or none"""
+        if noise is None and uniforms is None and exchange_uniforms is None:
+            self._fed = None
+            return self
+        if noise is None or uniforms is None or exchange_uniforms is None:
+            raise ValueError("feed_noise: noise, uniforms and exchange_uniforms go together")
+        super().feed_noise(noise, uniforms)
+        if exchange_uniforms.dim() != 2 or exchange_uniforms.shape[1] != uniforms.shape[1]:
+            raise ValueError("feed_noise: exchange_uniforms [X, B]")
+        self._fed += [exchange_uniforms.contiguous(), 0]
+        return self
+
+    def _fused_setup(self, state):
+        if not isinstance(state, SamplerState):
+            return None
+        samples = state.__dict__["_data"].samples
+        if len(samples) != 1 or not torch.is_tensor(samples[0]) or samples[0].dim() < 1:
+            return None
+        x = samples[0]
+        self.target_temperatures = self._tile(x)
+        setup = super()._fused_setup(state)
+        if setup is None or self.n_replicas > mcmc_tile_rows(setup[0].n_particles * setup[0].n_dims):
+            return None
+        if self.chain_offset % self.n_replicas != 0:
+            raise ValueError("ReplicaExchangeMCMCStep: chain_offset must be a multiple of the number of temperatures")
+        return setup
+
+    def _begin_launch(self, steps, x2, fresh):
+        K, E = self.n_replicas, self.exchange_every
+        self._book(x2.shape[0], x2.device, reset=fresh)
+        run = self._run
+        if run is not None:
+            run[0] -= steps
+            if run[0] == 0:                            # the run's last launch: what it may exchange is what ``_take_back`` undoes
+                run[1] = (self.walkers.clone(), self.n_exchanged.clone())
+        phase = self.steps_done % E
+        n_exchanges = (phase + steps) // E
+        parity = (self.steps_done // E) & 1            # of the next exchange: (its steps_done // E - 1) & 1
+        rows = None
+        fed = self._fed
+        if fed is not None and n_exchanges:
+            if fed[3].shape[0] - fed[4] < n_exchanges or fed[3].device != x2.device:
+                raise ValueError(f"ReplicaExchangeMCMCStep: {n_exchanges} exchanges need as many rows of fed exchange_uniforms; "
+                                 f"{fed[3].shape[0] - fed[4]} are left")
+            rows = fed[3][fed[4]:fed[4] + n_exchanges]
+            fed[4] += n_exchanges
+        self.steps_done += steps
+        self.n_exchange_attempts += n_exchanges
+        return dict(n_replicas=K, exchange_every=E, exchange_phase=phase, exchange_parity=parity, exchange_uniforms=rows,
+                    n_exchanged=self.n_exchanged, walkers=self.walkers)
+
+    def _run_chains(self, setup, x2, e, e_valid, launches, traj=None, traj_e=None, tick=None):
+        """x2 / e are working chains: every exchange so far is in them.  A run that ends with an exchange makes its last step a launch
+        of its own, so that the counters before that exchange can be kept (``_take_back``)"""
+        self._handed, self._before_last, self._applied_at = None, None, self.steps_done
+        total = sum(steps for steps, _, _ in launches)
+        ends = total > 0 and (self.steps_done + total) % self.exchange_every == 0
+        if ends:
+            launches = list(launches[:-1]) + _last_step_apart(launches[-1])
+        self._run = [total, None]
+        try:
+            super()._run_chains(setup, x2, e, e_valid, launches, traj, traj_e, tick)
+            self._before_last = self._run[1] if ends else None
+        finally:
+            self._run = None
+
+    def _hand_out(self, state, x2, e):
+        before, self._before_last = self._before_last, None
+        self._handed = _HandedOut(state, x2, e, *before) if before is not None and self._exchange_due() else None
+
+    def _take_back(self):
+        """forget the working chains of the state handed out last; the exchange the kernel made in them after the run's last step, if
+        it is still due for that state, leaves ``walkers``, ``n_exchanged`` and ``n_exchange_attempts`` with them"""
+        handed, self._handed = self._handed, None
+        if handed is not None and self._exchange_due():
+            self.walkers, self.n_exchanged = handed.walkers, handed.n_exchanged
+            self.n_exchange_attempts -= 1
+
+    def _working_copy(self, state, B):
+        handed = self._handed
+        if handed is not None and handed.state is state:       # the state handed out last: its working chains have the due exchange
+            self._handed, self._applied_at = None, self.steps_done
+            return handed.x, handed.e, True
+        state = self.apply_pending_exchange(state)
+        self._handed = None
+        return super()._working_copy(state, B)
+
+    def _fused_forward(self, state, setup, n_steps):
+        if n_steps <= 0 or (self.steps_done + n_steps) % self.exchange_every != 0:
+            return super()._fused_forward(state, setup, n_steps)
+        # the run ends with an exchange: the kernel records the last step's frame before it, and that frame is the state handed out
+        plan, B, _ = setup
+        x = state.__dict__["_data"].samples[0]
+        y, e, e_valid = self._working_copy(state, B)
+        pieces = _split(n_steps, MCMC_MAX_STEPS_PER_LAUNCH)
+        frame = torch.empty((1,) + tuple(x.shape), dtype=torch.float32, device=x.device)
+        frame_e = torch.empty((1, B), dtype=torch.float32, device=x.device)
+        self._run_chains(setup, y, e, e_valid, [(k, 0, 0) for k in pieces[:-1]] + [(pieces[-1], pieces[-1], 1)], frame, frame_e)
+        out = _advanced_state(state, frame[0], frame_e[0])
+        self._hand_out(out, y, e)
+        return out
+
+
+@dataclasses.dataclass
+class _HandedOut:
+    """What ``ReplicaExchangeMCMCStep`` keeps after a fused run that ended with an exchange: the state it handed out (the frame before
+    that exchange), the working chains x [B, n d] / e [B] in which the kernel has made it, and ``walkers`` / ``n_exchanged`` as they were
+    before it.  ``IterativeSampler`` and ``forward`` both register their runs here (``_hand_out``)."""
+    state: object
+    x: torch.Tensor
+    e: torch.Tensor
+    walkers: torch.Tensor
+    n_exchanged: torch.Tensor
+
+
+def _last_step_apart(launch):
+    """the launch (steps, traj_every, frames) of ``_launch_plan`` as launches that record the same frames, the last of one step"""
+    steps, every, frames = launch
+    if not frames:
+        return ([(steps - 1, 0, 0)] if steps > 1 else []) + [(1, 0, 0)]
+    return (([((frames - 1) * every, every, frames - 1)] if frames > 1 else []) + ([(every - 1, 0, 0)] if every > 1 else [])
+            + [(1, 1, 1)])
 
 
 def _advanced_state(state, samples, energies):
@@ -438,7 +755,8 @@ class IterativeSampler(Sampler, torch.utils.data.Dataset):
 
     With one fusable ``MCMCStep`` and the default ``extract_sample_hook`` an iteration is one launch of ``stride * n_steps`` steps and
     ``sample(n)`` has the kernel write the n states into the result (launches of at most ``MCMC_MAX_STEPS_PER_LAUNCH`` steps); the
-    state's samples are then the last recorded frame."""
+    state's samples are then the last recorded frame.  The same holds for one fusable ``ReplicaExchangeMCMCStep``: the exchanges happen
+    inside the launches, each after the frame of its step."""
 
     def __init__(
             self,
@@ -477,7 +795,8 @@ class IterativeSampler(Sampler, torch.utils.data.Dataset):
         if self.extract_sample_hook is not default_extract_sample_hook or not isinstance(steps, (list, tuple)) or len(steps) != 1:
             return None
         step = steps[0]
-        if not isinstance(step, MCMCStep) or type(step).forward is not MCMCStep.forward or type(step)._step is not MCMCStep._step:
+        base = ReplicaExchangeMCMCStep if isinstance(step, ReplicaExchangeMCMCStep) else MCMCStep
+        if not isinstance(step, MCMCStep) or type(step).forward is not base.forward or type(step)._step is not base._step:
             return None
         if not (isinstance(self.stride, int) and self.stride >= 1 and isinstance(step._n_steps, int) and step._n_steps >= 1):
             return None
@@ -496,10 +815,7 @@ class IterativeSampler(Sampler, torch.utils.data.Dataset):
         if n_ok > 0:
             chains = self._chains
             if chains is None or chains[0] is not self.state:          # a state from outside: take a working copy of it
-                e = step._carried_energies(self.state, B)
-                chains = [None, x.detach().clone().view(B, -1), e, e is not None]
-                if e is None:
-                    chains[2] = torch.empty(B, dtype=torch.float32, device=dev)
+                chains = [None, *step._working_copy(self.state, B)]
             else:
                 chains = [None, chains[1], chains[2], True]
             unit = self.stride * step._n_steps
@@ -519,6 +835,7 @@ class IterativeSampler(Sampler, torch.utils.data.Dataset):
                 pass
             self.state = _advanced_state(self.state, frames[-1], frames_e[-1])
             self._chains = (self.state, chains[1], chains[2])
+            step._hand_out(self.state, chains[1], chains[2])
             self.i += n_ok
         if n_ok < n:
             raise StopIteration
@@ -593,3 +910,15 @@ class GaussianMCMCSampler(IterativeSampler):
             n_burnin=n_burnin,
             return_hook=return_hook
         )
+
+
+class ReplicaExchangeSampler(IterativeSampler):
+    """Shortcut for a parallel-tempering sampler in the manner of ``GaussianMCMCSampler``: ``init_state`` holds B = L K chains,
+    ladder-major, K = len(temperatures); one ``ReplicaExchangeMCMCStep`` with a ``GaussianProposal(noise_std)`` and an exchange attempt
+    after every ``exchange_every``-th step.  Further keywords are ``IterativeSampler``'s."""
+
+    def __init__(self, energy, init_state, temperatures, noise_std=.1, stride=1, n_burnin=0, exchange_every=1, **kwargs):
+        if not isinstance(init_state, SamplerState):
+            init_state = SamplerState(samples=init_state)
+        step = ReplicaExchangeMCMCStep(energy, temperatures, proposal=GaussianProposal(noise_std=noise_std), exchange_every=exchange_every)
+        super().__init__(init_state, sampler_steps=[step], stride=stride, n_burnin=n_burnin, **kwargs)

@@ -30,7 +30,9 @@ Deviations from the reference:
 * ``mbar`` needs no pyemma; its ``F`` is -log of the normalised unbiased weight of every ``np.digitize`` state, empty states +inf.
 * ``MetropolisGauss`` keeps the reference's single uniform number per step, shared by ALL walkers (metropolis.py:85): the walkers of one
   step accept or reject against the same threshold.  Kept, so that ``np.random.seed`` reproduces the reference's trajectories; the
-  fused chain kernel (sampling.py) draws one per walker.  ``ReplicaExchangeMetropolisGauss`` and ``SystemWrapper`` are not ported."""
+  fused chain kernel (sampling.py) draws one per walker.  ``ReplicaExchangeMetropolisGauss`` (metropolis.py:138-188) is the numpy class
+  with the reference's calls in the reference's order; the sampler for particle targets on the GPU is
+  ``sampling.ReplicaExchangeMCMCStep``.  ``SystemWrapper`` is not ported."""
 from collections import namedtuple
 
 import numpy as np
@@ -43,7 +45,8 @@ from .analysis import bar
 from .particles import HarmonicParticles, RepulsiveParticles
 from .sampling import GaussianMCMCSampler
 
-__all__ = ["UmbrellaModel", "UmbrellaSampling", "MetropolisGauss", "mbar_solve", "MBARResult", "biased_system"]
+__all__ = ["UmbrellaModel", "UmbrellaSampling", "MetropolisGauss", "ReplicaExchangeMetropolisGauss", "mbar_solve", "MBARResult",
+           "biased_system"]
 
 MBARResult = namedtuple("MBARResult", ["f", "log_weights", "status", "iterations", "err"])
 
@@ -490,3 +493,38 @@ class MetropolisGauss(object):
     @property
     def etraj(self):
         return self.etrajs[0]
+
+
+class ReplicaExchangeMetropolisGauss(object):
+    """Parallel tempering on numpy arrays (metropolis.py:138-188): one ``MetropolisGauss`` walker per temperature (an ODD number of
+    temperatures, as the reference demands; ``temperatures`` a numpy array), all started at ``x0``.  ``run`` makes ``nepochs`` epochs of
+    ``nsteps_per_epoch`` Metropolis steps, each followed by an exchange attempt between the neighbours (k, k + 1), k = toggle, toggle + 2,
+    ...: with c = -(E[k+1] - E[k]) (1 / T[k+1] - 1 / T[k]) the two swap configuration and energy iff -log(np.random.rand()) > c; then
+    ``toggle`` flips.  One ``np.random.rand()`` per pair, in ascending k, after the epoch's steps: the reference's calls in its order."""
+
+    def __init__(self, energy_function, x0, temperatures, noise=0.1, burnin=0, stride=1, mapper=None):
+        if temperatures.size % 2 == 0:
+            raise ValueError("Please use an odd number of temperatures.")
+        self.temperatures = temperatures
+        self.sampler = MetropolisGauss(energy_function, x0, temperature=temperatures, noise=noise, burnin=burnin, stride=stride,
+                                       nwalkers=temperatures.size, mapper=mapper)
+        self.toggle = 0
+
+    @property
+    def trajs(self):
+        return self.sampler.trajs
+
+    @property
+    def etrajs(self):
+        return self.sampler.etrajs
+
+    def run(self, nepochs=1, nsteps_per_epoch=1, verbose=0):
+        s, T = self.sampler, self.temperatures
+        for _ in range(nepochs):
+            s.run(nsteps=nsteps_per_epoch)
+            for k in range(self.toggle, T.size - 1, 2):
+                c = -(s.E[k + 1] - s.E[k]) * (1.0 / T[k + 1] - 1.0 / T[k])
+                if -np.log(np.random.rand()) > c:
+                    s.x[[k, k + 1]] = s.x[[k + 1, k]]
+                    s.E[[k, k + 1]] = s.E[[k + 1, k]]
+            self.toggle = 1 - self.toggle

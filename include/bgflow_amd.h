@@ -768,6 +768,38 @@ int bgk_pair_mcmc(float* x, int64_t B, int32_t n_particles, int32_t n_dims, int3
                   uint64_t seed, uint32_t offset, int64_t row0,
                   float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream);
 
+/* Replica exchange (parallel tempering) inside the chain kernel, replacing the host loop over pairs of ReplicaExchangeMetropolisGauss.run
+ * (distribution/sampling/_mcmc/metropolis.py:172-188).  The arguments of bgk_pair_mcmc / bgk_box_mcmc with the same meaning, then:
+ *   n_replicas K >= 2: x [B, n d] holds L = B / K ladders, ladder-major -- chain b is slot b % K of ladder b / K; temperatures [B] is
+ *     required (the ladder tiled L times; `temperature` is not read); B and row0 must be multiples of K (BGK_EINVAL).
+ *   exchange_every E >= 1, exchange_phase (the steps already taken in the current epoch, 0 <= phase < E), exchange_parity (0 / 1): after
+ *     the Metropolis part of every step that completes an epoch of E steps, each pair of slots (k, k + 1) with k = parity (mod 2),
+ *     k + 1 < K, computes in f32   c = -(e[k+1] - e[k]) (1 / T[k+1] - 1 / T[k])   and exchanges iff -log r > c (never for a NaN on
+ *     either side); then the parity flips.  An exchange swaps configuration, carried energy and walker id of the two slots; temperatures,
+ *     n_accepted and n_exchanged belong to the slot.  A frame of traj due at the same step is written BEFORE the exchange.
+ *   r: the number of the pair's lower slot -- row j of exchange_uniforms [exchanges of this launch, B] for the launch's j-th exchange
+ *     (given together with noise / uniforms: all or none), else Philox field 2: counter (global chain, 2 << 20, offset + step), word 0,
+ *     i.e. what bgk_philox_fields writes for fields [normal n d, uniform 1, uniform 1] -- whatever the grid, row0 or the split into launches.
+ *   n_exchanged [B] (int32, may be NULL): accepted exchanges of pair (k, k + 1) at its lower slot, written or added to like n_accepted.
+ *   walkers [B] (int32, in / out, may be NULL: slot k starts with walker k): which walker (0..K-1 of its ladder) sits in each slot.
+ * A tile holds whole ladders: its height is the plain kernel's (64; 41 at n d = 192; 61 for the box of 64) rounded down to a multiple of
+ * K; K beyond the plain height: BGK_EUNSUPPORTED. */
+int bgk_pair_remc(float* x, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
+                  double p0, double p1, double p2, double p3, double osc_scale,
+                  float* e, int32_t e_valid, double temperature, const float* temperatures,
+                  double noise_std, int32_t n_steps, const float* noise, const float* uniforms,
+                  uint64_t seed, uint32_t offset, int64_t row0,
+                  float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream,
+                  int32_t n_replicas, int32_t exchange_every, int32_t exchange_phase, int32_t exchange_parity,
+                  const float* exchange_uniforms, int32_t* n_exchanged, int32_t* walkers);
+int bgk_box_remc(float* x, int64_t B, int32_t n_particles, int32_t kind, const float* params, int32_t n_params,
+                 float* e, int32_t e_valid, double temperature, const float* temperatures,
+                 double noise_std, int32_t n_steps, const float* noise, const float* uniforms,
+                 uint64_t seed, uint32_t offset, int64_t row0,
+                 float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream,
+                 int32_t n_replicas, int32_t exchange_every, int32_t exchange_phase, int32_t exchange_parity,
+                 const float* exchange_uniforms, int32_t* n_exchanged, int32_t* walkers);
+
 /* The particle box -- a bistable dimer (particles 0 and 1) in a bath of solvent particles in a 2-d box -- over ONE tensor
  * x [B, 2 n_particles] (rows [x0, y0, x1, y1, ...]) on the kernels of bgk_pair_energy and bgk_pair_mcmc (csrc/bgk_pair.hip, bgk_mcmc.hip,
  * bgk_pair_terms.h), replacing the [B, n, n] op chains of bgflow/distribution/energy/particles.py:
