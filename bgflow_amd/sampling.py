@@ -11,12 +11,20 @@ The fused path (csrc/bgk_mcmc.hip, entries bgk_pair_mcmc / bgk_box_mcmc) runs wh
 step (and whose ``extract_sample_hook`` is the default) runs ``stride * n_steps`` steps per iteration inside the launch and has the kernel
 write every recorded state straight into the ``[n, B, ...]`` result.  ``MCMCStep.fused = False`` forces the general path.
 
+Hamiltonian Monte Carlo (not in the reference outside its OpenMM integrators): ``HamiltonianProposal`` / ``HMCStep`` /
+``HamiltonianMCSampler``.  A ``HamiltonianProposal`` on the step's own energy and temperature, with numeric ``step_size`` and ``mass``,
+takes the fused path under the same conditions through csrc/bgk_hmc.hip (entries bgk_pair_hmc / bgk_box_hmc): the leapfrog trajectory
+and the accept step of every step inside the launch, in launches of at most ``hmc_max_steps_per_launch(n_leapfrog)`` steps.  By
+default (``fused = True``) that holds where the kernel was measured faster than the general path -- pair targets of n d <= 79,
+``hmc_fused_by_default`` -- and ``fused = "always"`` takes the kernel wherever it accepts the state.
+
 Not in the reference: ``MCMCStep.n_accepted`` (per-chain accepted steps) / ``n_proposed``, ``MCMCStep.feed_noise`` and ``chain_offset``;
 ``ReplicaExchangeMCMCStep`` / ``ReplicaExchangeSampler`` -- parallel tempering over ladders of temperatures with the exchange rule of the
 reference's numpy ``ReplicaExchangeMetropolisGauss`` (_mcmc/metropolis.py:138-188; its numpy port is in umbrella.py), fused as entries
 bgk_pair_remc / bgk_box_remc of the same kernel: the exchange is a swap of row index, tile flag and energy between two lanes.
 """
 import dataclasses
+import math
 import warnings
 from typing import Sequence
 
@@ -28,14 +36,27 @@ from .utils import pack_tensor_in_list, pack_tensor_in_tuple, unpack_tensor_tupl
 
 __all__ = ["AbstractSamplerState", "SamplerState", "SamplerStep", "IterativeSampler", "GaussianProposal", "LatentProposal", "MCMCStep",
            "GaussianMCMCSampler", "metropolis_accept", "default_set_samples_hook", "default_extract_sample_hook",
-           "ReplicaExchangeMCMCStep", "ReplicaExchangeSampler", "exchange_permutation", "mcmc_tile_rows"]
+           "ReplicaExchangeMCMCStep", "ReplicaExchangeSampler", "exchange_permutation", "mcmc_tile_rows",
+           "HamiltonianProposal", "HMCStep", "HamiltonianMCSampler", "hmc_tile_rows"]
 
 # The most Metropolis steps one launch of bgk_pair_mcmc runs; longer runs are split (bitwise the same chain: the random stream and the
 # carried f32 energies do not depend on the split), so that no single launch holds a shared GPU for long.  Measured on an MI355X
 # (tools/mcmc_time.py, its last line): the widest shape of the envelope -- Lennard-Jones, n = 64, d = 3, 2^16 chains -- takes 70.46 ms
 # for one launch of 64 steps (70.29 .. 70.74 over three rounds), 1.10 ms per step, so 224 steps are 0.247 s.  The replica-exchange
 # launches (bgk_pair_remc) reuse it: tools/remc_time.py measured 1.07 ms per step at that shape with an exchange after every step.
+# The HMC launches (bgk_pair_hmc) scale it, ``hmc_max_steps_per_launch``: tools/hmc_time.py measured, at that shape, 6.50 ms per step of
+# 1 leapfrog step (52.03 ms for a launch of 8 steps, 51.87 .. 52.16) and 33.88 ms per step of 10 (271.03 ms, 269.95 .. 271.18) next to
+# 1.062 ms per Metropolis step (67.98 ms for 64 steps) -- 16 rows per tile instead of 41 -- so a step of L leapfrog steps counts as
+# 2.86 L + 3.26 Metropolis steps: 7 steps per launch at L = 10 are 0.237 s.
 MCMC_MAX_STEPS_PER_LAUNCH = 224
+
+# The tile height from which an ``MCMCStep`` takes the HMC kernel by default on a pair target (``hmc_fused_by_default``): the lowest
+# at which it was measured faster than the general path.  Five LDS tiles per chain bound the chains in flight per CU, so the kernel
+# loses ground as rows grow wider.  tools/hmc_time.py on an MI355X, Lennard-Jones, 2^16 chains, 10 leapfrog steps, ms per step fused
+# (kernel forced) / general: n = 16 (64 rows) 0.637 / 3.629; n = 20 (51 rows) 1.329 / 3.686; n = 26 (40 rows) 2.668 / 3.722; n = 40
+# (26 rows) 7.283 / 6.067; n = 64 (16 rows) 33.70 / 18.56.  The particle box of 38 (41 rows) took 3.502 / 2.03: its general path is
+# cheaper, and no box was measured faster, so box targets take the kernel only with ``fused = "always"``.
+HMC_FUSED_MIN_ROWS = 40
 
 
 # ---- state ---------------------------------------------------------------------------------------------------------------------
@@ -202,6 +223,62 @@ def pair_mcmc(plan, x, e, e_valid, temperature, noise_std, n_steps, noise=None, 
     _lib.check(st, name)
 
 
+def pair_hmc(plan, x, e, e_valid, temperature, step_size, n_leapfrog, mass, n_steps, noise=None, uniforms=None, seed=0, offset=0, row0=0,
+             traj=None, traj_e=None, traj_every=0, n_accepted=None, accumulate=False):
+    """One launch of bgk_pair_hmc (bgk_box_hmc for a ``BoxPlan``): ``n_steps`` Hamiltonian Monte Carlo steps of ``n_leapfrog`` leapfrog
+    steps of size ``step_size`` at ``mass`` on the chains x [B, n d] (f32, contiguous, HIP; updated IN PLACE).  Every other argument is
+    ``pair_mcmc``'s; noise [n_steps, B, n d] holds the standard normals of the momenta."""
+    from . import _lib
+    B, nd = x.shape
+    if nd != plan.n_particles * plan.n_dims:
+        raise ValueError(f"pair_hmc: x has {nd} columns, the target {plan.n_particles} x {plan.n_dims}")
+    if (noise is None) != (uniforms is None):
+        raise ValueError("pair_hmc: noise and uniforms go together")
+    temps = temperature if torch.is_tensor(temperature) else None
+    n_frames = n_steps // traj_every if traj is not None else 0
+    _check_tensors("pair_hmc", x, [(x, (B, nd)), (e, (B,)), (temps, (B,)), (noise, (n_steps, B, nd)), (uniforms, (n_steps, B)),
+                                   (traj, (n_frames, B, nd)), (traj_e, (n_frames, B))])
+    _check_tensors("pair_hmc", x, [(n_accepted, (B,))], dtype=torch.int32)
+    if traj is not None and traj_every < 1:
+        raise ValueError("pair_hmc: traj_every must be at least 1")
+    name = "bgk_box_hmc" if isinstance(plan, BoxPlan) else "bgk_pair_hmc"
+    with torch.cuda.device(x.device):
+        st = getattr(_lib.lib(), name)(_lib.ptr(x), B, *_target_args(plan), _lib.ptr(e), int(bool(e_valid)),
+                                       1.0 if temps is not None else float(temperature), _lib.ptr(temps),
+                                       float(step_size), int(n_leapfrog), float(mass), int(n_steps), _lib.ptr(noise), _lib.ptr(uniforms),
+                                       int(seed) & (2 ** 64 - 1), int(offset) & 0xffffffff, int(row0), _lib.ptr(traj), _lib.ptr(traj_e),
+                                       int(traj_every), _lib.ptr(n_accepted), int(bool(accumulate)), _lib.stream_ptr(x.device))
+    _lib.check(st, name)
+
+
+def hmc_max_steps_per_launch(n_leapfrog):
+    """The most HMC steps of ``n_leapfrog`` leapfrog steps one launch of bgk_pair_hmc runs, so that a launch holds the device no longer
+    than ``MCMC_MAX_STEPS_PER_LAUNCH`` Metropolis steps do: the measured cost of an HMC step in Metropolis steps (the comment of
+    ``MCMC_MAX_STEPS_PER_LAUNCH``), rounded up.  Results do not depend on the split."""
+    return max(1, MCMC_MAX_STEPS_PER_LAUNCH // math.ceil(2.86 * int(n_leapfrog) + 3.26))
+
+
+def hmc_fused_by_default(plan):
+    """whether an ``MCMCStep`` with ``fused = True`` runs a ``HamiltonianProposal`` on the target of ``plan`` inside the kernel: a pair
+    target (kinds 0 .. 2) whose tile has at least ``HMC_FUSED_MIN_ROWS`` rows, i.e. n d <= 79.  ``fused = "always"`` takes the kernel wherever it
+    accepts the state."""
+    return isinstance(plan, PairPlan) and hmc_tile_rows(plan.n_particles * plan.n_dims) >= HMC_FUSED_MIN_ROWS
+
+
+def hmc_tile_rows(nd):
+    """rows of a tile of the HMC kernel for rows of ``nd`` floats (csrc/bgk_hmc.hip, ``hmc_run``): the most, at most 64, whose five LDS
+    tiles (odd row stride, the second (position, gradient) pair starting at a multiple of 32 words) fit 63,488 bytes"""
+    S = nd | 1
+    rows = min(64, 63488 // (20 * S))
+    while (((3 * rows * S + 31) & ~31) + 2 * rows * S) * 4 > 63488:
+        rows -= 1
+    return rows
+
+
+def _is_number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+
 def _launch_plan(unit, count, cap):
     """[(steps, traj_every, frames)] of the launches that run ``count`` units of ``unit`` steps and record the state after every unit,
     no launch longer than ``cap`` steps (traj_every = 0: a piece of a unit longer than the cap, nothing recorded)"""
@@ -272,6 +349,63 @@ class LatentProposal(torch.nn.Module):
         return proposed_latent.replace(samples=proposed_samples), delta_log_prob[:, 0]
 
 
+class HamiltonianProposal(torch.nn.Module):
+    """Hamiltonian Monte Carlo proposal: fresh momenta, ``n_leapfrog`` leapfrog steps of size ``step_size`` in the potential
+    ``energy`` / ``temperature``, and the change of the kinetic energy as ``delta_log_prob`` -- the proposal protocol of ``MCMCStep``,
+    ``forward(state) -> (proposed_state, delta_log_prob)``.  With h = step_size, m = mass (a positive number), T = temperature (a positive
+    number or a tensor of one value per chain), f(x) = -grad E(x) / T (E at temperature 1) and xi standard normal, shaped like the samples:
+
+        p0 = sqrt(m) xi;  p = p0 + (h / 2) f(x);  n_leapfrog times:  x = x + (h / m) p,  p = p + c f(x)  (c = h; h / 2 after the last drift)
+        delta_log_prob = K(p) - K(p0), [B],  K(p) = |p|^2 / (2 m)
+
+    so that ``metropolis_accept`` decides on -(E' / T - E / T) - delta_log_prob = -(change of the Hamiltonian).  The momenta are
+    refreshed in full at every step; ``n_leapfrog = 1`` is the Metropolis-adjusted Langevin algorithm.  The forces come from
+    ``energy.force`` on a detached copy (no graph reaches the state); the state holds exactly one samples tensor; its ``velocities``
+    and ``forces`` are ignored.
+
+    The chain stays exact when ``temperature`` differs from the step's ``target_temperatures``: leapfrog is reversible and
+    volume-preserving whatever potential drives it, so the accept step corrects for it and only the acceptance rate suffers.
+
+    Inside a plain ``MCMCStep`` on the same energy and temperature, with numeric ``step_size`` and ``mass``, whole chains run in one
+    launch of csrc/bgk_hmc.hip (module docstring).  Inside a ``ReplicaExchangeMCMCStep`` the general path runs: exchanges between HMC
+    chains inside the kernel are not built."""
+
+    def __init__(self, energy, step_size, n_leapfrog=10, mass=1.0, temperature=1.0):
+        super().__init__()
+        if not (_is_number(mass) and mass > 0):
+            raise ValueError("HamiltonianProposal: mass must be a positive number")
+        if not (isinstance(n_leapfrog, int) and not isinstance(n_leapfrog, bool) and n_leapfrog >= 1):
+            raise ValueError("HamiltonianProposal: n_leapfrog must be an integer, at least 1")
+        self.energy = energy
+        self.step_size = step_size
+        self.n_leapfrog = n_leapfrog
+        self.mass = mass
+        self.temperature = temperature
+
+    def _force(self, x):
+        """f(x) = -grad E(x) / T, detached"""
+        f = self.energy.force(x.detach().clone()).detach()
+        t = self.temperature
+        if torch.is_tensor(t):
+            t = t.to(device=x.device, dtype=x.dtype).reshape((-1,) + (1,) * (x.dim() - 1))
+        return f / t
+
+    def forward(self, state):
+        samples = state.as_dict()["samples"]
+        if len(samples) != 1 or not torch.is_tensor(samples[0]):
+            raise ValueError("HamiltonianProposal takes a state with exactly one samples tensor")
+        x = samples[0].detach()
+        h, m = self.step_size, self.mass
+        p0 = math.sqrt(m) * torch.randn_like(x)
+        p = p0 + (h / 2) * self._force(x)
+        for k in range(self.n_leapfrog):
+            x = x + (h / m) * p
+            p = p + (h if k + 1 < self.n_leapfrog else h / 2) * self._force(x)
+        batch = x.shape[0]
+        kinetic = [(q * q).reshape(batch, -1).sum(dim=-1) / (2 * m) for q in (p, p0)]
+        return state.replace(samples=(x,)), kinetic[0] - kinetic[1]
+
+
 def metropolis_accept(current_energies, proposed_energies, proposal_delta_log_prob):
     """Metropolis criterion (mcmc.py:192-222): True where min(0, -(u' - u) - delta_log_prob) >= log r, r ~ U(0, 1); a NaN or +inf
     proposed energy is never accepted (the comparison is False)."""
@@ -289,7 +423,7 @@ class MCMCStep(SamplerStep, _FusedSampling):
     numbers come from the Philox stream of this object (``_FusedSampling``: key from ``torch.initial_seed()``, rank and stream id, the
     per-object counter is the index of the next step, both travel in ``state_dict``), unless ``feed_noise`` has handed it explicit ones.
     ``n_accepted`` (int32 [B]) counts the accepted steps per chain and ``n_proposed`` the steps taken, on either path."""
-    fused = True
+    fused = True                       # False: the general path; "always": the HMC kernel also where it is not the default
 
     def __init__(self, target_energy, proposal=GaussianProposal(), target_temperatures=1.0, n_steps=1):
         super().__init__(n_steps=n_steps)
@@ -353,12 +487,36 @@ class MCMCStep(SamplerStep, _FusedSampling):
             hit = self.__dict__["_temp_cache"] = (key, dev_t)
         return hit[1]
 
+    def _chain_launch(self):
+        """the launch of the proposal's chain kernel, ``pair_mcmc`` / ``pair_hmc`` without the proposal's own arguments --
+        f(plan, x, e, e_valid, temperature, n_steps, noise, uniforms, ...) -- or None if no kernel takes the proposal"""
+        proposal = self.proposal
+        if type(proposal) is GaussianProposal:
+            std = proposal._noise_std
+            if not (_is_number(std) and std >= 0):
+                return None
+            return lambda plan, x, e, e_valid, temps, steps, *args, **kwargs: pair_mcmc(plan, x, e, e_valid, temps, std, steps, *args, **kwargs)
+        if type(proposal) is HamiltonianProposal:
+            h, L, m, t = proposal.step_size, proposal.n_leapfrog, proposal.mass, proposal.temperature
+            if proposal.energy is not self.target_energy or not (_is_number(h) and h > 0 and _is_number(m) and m > 0):
+                return None
+            if not (isinstance(L, int) and not isinstance(L, bool) and L >= 1):
+                return None
+            mine = self.target_temperatures
+            if not (t is mine if torch.is_tensor(t) or torch.is_tensor(mine) else _is_number(t) and _is_number(mine) and t == mine):
+                return None
+            return lambda plan, x, e, e_valid, temps, steps, *args, **kwargs: pair_hmc(plan, x, e, e_valid, temps, h, L, m, steps, *args, **kwargs)
+        return None
+
+    def _launch_cap(self):
+        """the most steps of one launch of ``_chain_launch``"""
+        if type(self.proposal) is HamiltonianProposal:
+            return hmc_max_steps_per_launch(self.proposal.n_leapfrog)
+        return MCMC_MAX_STEPS_PER_LAUNCH
+
     def _fused_setup(self, state):
         """(plan, B, temperature argument) if the kernel takes this state, else None"""
-        if not self.fused or type(self.proposal) is not GaussianProposal:
-            return None
-        std = self.proposal._noise_std
-        if not (isinstance(std, (int, float)) and not isinstance(std, bool) and std >= 0):
+        if not self.fused or self._chain_launch() is None:
             return None
         if not isinstance(state, SamplerState) or state.set_samples_hook is not default_set_samples_hook:
             return None
@@ -369,6 +527,8 @@ class MCMCStep(SamplerStep, _FusedSampling):
         plan = _kernel_plan(self.target_energy, 1.0)
         if not isinstance(plan, (PairPlan, BoxPlan)):
             return None
+        if type(self.proposal) is HamiltonianProposal and self.fused != "always" and not hmc_fused_by_default(plan):
+            return None                # measured slower than the general path, or not measured (HMC_FUSED_MIN_ROWS)
         x, nd = samples[0], plan.n_particles * plan.n_dims
         if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() in (2, 3) and x.shape[0] > 0):
             return None
@@ -409,6 +569,7 @@ class MCMCStep(SamplerStep, _FusedSampling):
             st = self._philox_ids()
             seed = (dp.rank_seed(torch.initial_seed()) + 0x9E3779B97F4A7C15 * (st[0] + 1)) & (2 ** 64 - 1)
             offset, st[1] = st[1], st[1] + total
+        launch = self._chain_launch()
         frame = 0
         done = 0
         for steps, every, frames in launches:
@@ -416,10 +577,10 @@ class MCMCStep(SamplerStep, _FusedSampling):
             if fed is not None:
                 noise, uniforms = fed[0][fed[2]:fed[2] + steps], fed[1][fed[2]:fed[2] + steps]
                 fed[2] += steps
-            pair_mcmc(plan, x2, e, e_valid, temps, self.proposal._noise_std, steps, noise, uniforms, seed, offset, self.chain_offset,
-                      None if not frames else traj[frame:frame + frames].view(frames, B, -1),
-                      None if not frames or traj_e is None else traj_e[frame:frame + frames], every, self.n_accepted, not fresh,
-                      **self._begin_launch(steps, x2, fresh))
+            launch(plan, x2, e, e_valid, temps, steps, noise, uniforms, seed, offset, self.chain_offset,
+                   None if not frames else traj[frame:frame + frames].view(frames, B, -1),
+                   None if not frames or traj_e is None else traj_e[frame:frame + frames], every, self.n_accepted, not fresh,
+                   **self._begin_launch(steps, x2, fresh))
             e_valid, fresh = True, False
             offset += steps
             frame += frames
@@ -449,7 +610,7 @@ class MCMCStep(SamplerStep, _FusedSampling):
     def _fused_forward(self, state, setup, n_steps):
         plan, B, _ = setup
         y, e, e_valid = self._working_copy(state, B)
-        self._run_chains(setup, y, e, e_valid, [(k, 0, 0) for k in _split(n_steps, MCMC_MAX_STEPS_PER_LAUNCH)])
+        self._run_chains(setup, y, e, e_valid, [(k, 0, 0) for k in _split(n_steps, self._launch_cap())])
         out = _advanced_state(state, y.view(state.__dict__["_data"].samples[0].shape), e)
         self._hand_out(out, y, e)
         return out
@@ -464,6 +625,15 @@ class MCMCStep(SamplerStep, _FusedSampling):
 def _split(total, cap):
     cap = max(1, int(cap))
     return [min(cap, total - s) for s in range(0, total, cap)]
+
+
+class HMCStep(MCMCStep):
+    """Hamiltonian Monte Carlo on ``target_energy`` at ``target_temperatures``: an ``MCMCStep`` whose proposal is a
+    ``HamiltonianProposal`` on the same energy and the same temperatures"""
+
+    def __init__(self, target_energy, step_size, n_leapfrog=10, mass=1.0, target_temperatures=1.0, n_steps=1):
+        proposal = HamiltonianProposal(target_energy, step_size, n_leapfrog=n_leapfrog, mass=mass, temperature=target_temperatures)
+        super().__init__(target_energy, proposal=proposal, target_temperatures=target_temperatures, n_steps=n_steps)
 
 
 # ---- replica exchange --------------------------------------------------------------------------------------------------------------
@@ -511,7 +681,8 @@ class ReplicaExchangeMCMCStep(MCMCStep):
     steps, ``walkers`` (int32 [B]) says which walker (0..K-1 of its ladder, by its start slot) sits in each slot.
 
     General path (any energy with energies [B], proposal, device, dtype): ``MCMCStep._step`` and the exchange in torch ops; every
-    exchange makes exactly one ``torch.rand_like(energies)`` call and uses the entry at each pair's lower slot.  Fused path
+    exchange makes exactly one ``torch.rand_like(energies)`` call and uses the entry at each pair's lower slot.  A
+    ``HamiltonianProposal`` always runs this path: exchanges between HMC chains inside the kernel are not built.  Fused path
     (bgk_pair_remc / bgk_box_remc, the exchange by wave shuffles inside the chain kernel): under the conditions of ``MCMCStep``'s, K within
     the kernel's tile height (``mcmc_tile_rows``) and ``chain_offset`` a multiple of K.  There the due exchange of a run's last step has
     already happened in the working chains the step keeps for the state it handed out (``_HandedOut``; ``forward`` and
@@ -633,6 +804,8 @@ class ReplicaExchangeMCMCStep(MCMCStep):
             return None
         x = samples[0]
         self.target_temperatures = self._tile(x)
+        if type(self.proposal) is HamiltonianProposal:      # no exchanges inside the HMC kernel: the general path
+            return None
         setup = super()._fused_setup(state)
         if setup is None or self.n_replicas > mcmc_tile_rows(setup[0].n_particles * setup[0].n_dims):
             return None
@@ -819,7 +992,8 @@ class IterativeSampler(Sampler, torch.utils.data.Dataset):
             else:
                 chains = [None, chains[1], chains[2], True]
             unit = self.stride * step._n_steps
-            launches = _launch_plan(unit, n_ok, MCMC_MAX_STEPS_PER_LAUNCH) if record else _launch_plan(unit * n_ok, 1, MCMC_MAX_STEPS_PER_LAUNCH)
+            cap = step._launch_cap()
+            launches = _launch_plan(unit, n_ok, cap) if record else _launch_plan(unit * n_ok, 1, cap)
             n_frames = n_ok if record else 1
             frames = torch.empty((n_frames,) + tuple(x.shape), dtype=torch.float32, device=dev)
             frames_e = torch.empty((n_frames, B), dtype=torch.float32, device=dev)
@@ -909,6 +1083,42 @@ class GaussianMCMCSampler(IterativeSampler):
             stride=stride,
             n_burnin=n_burnin,
             return_hook=return_hook
+        )
+
+
+class HamiltonianMCSampler(IterativeSampler):
+    """Shortcut for a Hamiltonian Monte Carlo sampler in the manner of ``GaussianMCMCSampler``: one ``HMCStep``; ``box_constraint`` is
+    applied whenever samples are set, the default ``return_hook`` combines the sample and batch dimensions.  Further keywords are
+    ``IterativeSampler``'s."""
+
+    def __init__(
+            self,
+            energy,
+            init_state,
+            temperature=1.,
+            step_size=.01,
+            n_leapfrog=10,
+            mass=1.,
+            stride=1,
+            n_burnin=0,
+            box_constraint=None,
+            return_hook=None,
+            **kwargs
+    ):
+        set_samples_hook = default_set_samples_hook
+        if box_constraint is not None:
+            set_samples_hook = lambda samples: [box_constraint(x) for x in samples]     # noqa: E731
+        if not isinstance(init_state, SamplerState):
+            init_state = SamplerState(samples=init_state, set_samples_hook=set_samples_hook)
+        if return_hook is None:
+            return_hook = lambda samples: [x.reshape(-1, *shape) for x, shape in zip(samples, energy.event_shapes)]     # noqa: E731
+        super().__init__(
+            init_state,
+            sampler_steps=[HMCStep(energy, step_size, n_leapfrog=n_leapfrog, mass=mass, target_temperatures=temperature)],
+            stride=stride,
+            n_burnin=n_burnin,
+            return_hook=return_hook,
+            **kwargs
         )
 
 

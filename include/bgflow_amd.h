@@ -832,6 +832,32 @@ int bgk_box_mcmc(float* x, int64_t B, int32_t n_particles, int32_t kind, const f
                  uint64_t seed, uint32_t offset, int64_t row0,
                  float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream);
 
+/* Hamiltonian Monte Carlo chains on the targets of bgk_pair_mcmc / bgk_box_mcmc, a whole run of steps in one launch (csrc/bgk_hmc.hip),
+ * replacing the per-step op chain of MCMCStep._step and metropolis_accept (distribution/sampling/mcmc.py:86-122, 192-222) with a
+ * Hamiltonian proposal -- L autograd force calls, about 4 L elementwise ops, two energy calls and the accept chain -- and standing in for
+ * the reference's OpenMM-only HMC integrator (HamiltonianMCPathProbabilityIntegrator, nn/flow/stochastic/snf_openmm.py).  Per step, with
+ * h = step_size, m = mass, L = n_leapfrog, f(x) = -(d e / d x) / T, xi ~ N(0, 1)^{n d}:
+ *   p0 = sqrt(m) xi,  p = p0 + (h / 2) f(x),  L times:  x' += (h / m) p,  p += c f(x')  (c = h; h / 2 after the last drift),
+ *   accept iff -(e(x') - e(x)) / T - (|p|^2 - |p0|^2) / (2 m) >= log r   (never for a NaN or +-inf energy, kinetic energy or coordinate)
+ * one lane per chain; state, momentum and both gradients in LDS; L gradient evaluations and one energy evaluation per step.  For kinds 0..2
+ * with osc_scale != 0 (translation-invariant) the mean of the f32 gradient over the particles is taken out per dimension before a kick: it
+ * is rounding error.  L = 1 is the
+ * Metropolis-adjusted Langevin algorithm.  The arguments are those of bgk_pair_mcmc / bgk_box_mcmc with the same meaning (x, e, e_valid,
+ * the temperatures, traj, traj_e, n_accepted, row0, the Philox counter layout with field 0 = xi and field 1 = r), with noise_std replaced
+ * by step_size, n_leapfrog, mass; noise [n_steps, B, n d] is xi.  BGK_EINVAL for step_size <= 0, mass <= 0, n_leapfrog < 1 or noise and
+ * uniforms not both given; BGK_EUNSUPPORTED outside the envelope of bgk_pair_energy / bgk_box_energy; 0 for B == 0. */
+int bgk_pair_hmc(float* x, int64_t B, int32_t n_particles, int32_t n_dims, int32_t kind,
+                 double p0, double p1, double p2, double p3, double osc_scale,
+                 float* e, int32_t e_valid, double temperature, const float* temperatures,
+                 double step_size, int32_t n_leapfrog, double mass, int32_t n_steps, const float* noise, const float* uniforms,
+                 uint64_t seed, uint32_t offset, int64_t row0,
+                 float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream);
+int bgk_box_hmc(float* x, int64_t B, int32_t n_particles, int32_t kind, const float* params, int32_t n_params,
+                float* e, int32_t e_valid, double temperature, const float* temperatures,
+                double step_size, int32_t n_leapfrog, double mass, int32_t n_steps, const float* noise, const float* uniforms,
+                uint64_t seed, uint32_t offset, int64_t row0,
+                float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream);
+
 /* Brownian and Langevin dynamics with the path-probability ratio on the targets of bgk_pair_energy, a whole run of steps in one launch
  * (csrc/bgk_langevin.hip), replacing the per-step op chain of BrownianFlow._forward and LangevinFlow._forward (nn/flow/stochastic/
  * langevin.py:32-45, 86-118) with f = -d e / d x at temperature 1, h = stepsize.  v == NULL, Brownian:
