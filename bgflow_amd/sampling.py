@@ -22,6 +22,9 @@ Not in the reference: ``MCMCStep.n_accepted`` (per-chain accepted steps) / ``n_p
 ``ReplicaExchangeMCMCStep`` / ``ReplicaExchangeSampler`` -- parallel tempering over ladders of temperatures with the exchange rule of the
 reference's numpy ``ReplicaExchangeMetropolisGauss`` (_mcmc/metropolis.py:138-188; its numpy port is in umbrella.py), fused as entries
 bgk_pair_remc / bgk_box_remc of the same kernel: the exchange is a swap of row index, tile flag and energy between two lanes.
+
+Chains that switch from one target to another and record the nonequilibrium work -- ``AnnealedSwitching``, annealed importance
+sampling -- are in annealing.py (csrc/bgk_anneal.hip: the same tile walk and Philox layout with two targets per lane).
 """
 import dataclasses
 import math

@@ -31,6 +31,9 @@ Random numbers of the fused path come from the object's Philox stream (``_FusedS
 stream id, the per-object counter is the index of the next step, both travel in ``state_dict``), unless ``feed_noise`` has handed the
 object explicit ones; fed numbers are also what the general path then uses, one row per step.  ``chain_offset`` is the global index of
 the batch's first row: a batch sharded over processes draws the numbers of the whole.
+
+``AnnealedMCFlow`` (not in the reference) anneals between two energies along a schedule on the protocol of annealing.py (fused:
+csrc/bgk_anneal.hip); its dW carries the nonequilibrium work.
 """
 import math
 import warnings
@@ -41,7 +44,7 @@ from .distributions import BoxPlan, Energy, PairPlan, _FusedSampling, _kernel_pl
 from .flow import Flow
 from .particles import _check_tensors, _energy_backward, _is_number, _target_args
 
-__all__ = ["BrownianFlow", "OverdampedLangevinFlow", "LangevinFlow", "MetropolisMCFlow"]
+__all__ = ["BrownianFlow", "OverdampedLangevinFlow", "LangevinFlow", "MetropolisMCFlow", "AnnealedMCFlow"]
 
 # The most steps one launch of bgk_pair_langevin runs; longer runs are split (the same q and v bit for bit: the random stream does not
 # depend on the split; dW is then the f32 sum of the launches' dW), so that no single launch holds a shared GPU for long.  Measured on
@@ -534,3 +537,37 @@ class MetropolisMCFlow(_StochasticFlow):
             sampling.pair_mcmc(plan, y, e, True, 1.0, self.stepsize, k, noise, unif, seed, offset + done, self.chain_offset)
             done += k
         return y, (e - E0)[:, None]
+
+
+class AnnealedMCFlow(Flow):
+    """Annealed Metropolis Monte Carlo between ``energy_a`` (lambda = 0) and ``energy_b`` (lambda = 1): the protocol of
+    ``annealing.AnnealedSwitching`` (its module docstring has the definitions) as a stochastic flow layer, ``nsteps`` steps of width
+    ``stepsize`` at every stage of ``lambdas``.  Not in the reference, whose ``MetropolisMCFlow`` thermalises at one energy.
+
+    ``_forward(x)`` returns ``(y, dW)``, dW [B, 1] in x's dtype:  dW = e_B(y) / T_B - e_A(x) / T_A - work.  With this convention
+    ``log_weights_given_latent`` of a generator with prior A and target B gives ``-work``, the annealed-importance-sampling weight, and
+    for A identical to B (work = 0) the layer reduces to ``MetropolisMCFlow``'s E - E0.  ``_inverse`` runs ``reverse()``, the mirrored
+    protocol from B to A, with the mirrored dW = e_A(y) / T_A - e_B(x) / T_B - work'.  Keyword arguments are ignored, as in the other
+    stochastic layers.  The protocols are ``switching`` and ``switching_reverse`` (``feed_noise``, ``chain_offset``, ``set_philox_stream``,
+    ``fused``, ``n_accepted`` are theirs); the kernel runs only where the input needs no grad, otherwise the torch path."""
+
+    def __init__(self, energy_a, energy_b, lambdas, nsteps=1, stepsize=0.01, temperature_a=1.0, temperature_b=1.0):
+        super().__init__()
+        from .annealing import AnnealedSwitching
+        self.switching = AnnealedSwitching(energy_a, energy_b, lambdas, n_steps=nsteps, noise_std=stepsize, temperature_a=temperature_a,
+                                           temperature_b=temperature_b)
+        self.switching_reverse = self.switching.reverse()
+        self.nsteps = nsteps
+        self.stepsize = stepsize
+
+    @staticmethod
+    def _switch(protocol, x):
+        y, work = protocol._run(x, start=True)
+        dW = protocol.e_b.to(torch.float64) / protocol.temperature_b - protocol.e_a_start.to(torch.float64) / protocol.temperature_a - work
+        return y, dW.to(x.dtype)[:, None]
+
+    def _forward(self, x, **kwargs):
+        return self._switch(self.switching, x)
+
+    def _inverse(self, x, **kwargs):
+        return self._switch(self.switching_reverse, x)

@@ -858,6 +858,38 @@ int bgk_box_hmc(float* x, int64_t B, int32_t n_particles, int32_t kind, const fl
                 uint64_t seed, uint32_t offset, int64_t row0,
                 float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream);
 
+/* Annealed switching between two of the targets of bgk_pair_mcmc / bgk_box_mcmc with the nonequilibrium work of every chain, a whole
+ * protocol in one launch (csrc/bgk_anneal.hip; its head comment states the definitions): in stock ops one annealed Metropolis step is two
+ * energy launches and about a dozen elementwise ones.  Ends A and B over the same rows x [B, n_particles * n_dims] (updated in place):
+ * bgk_pair_anneal takes two pair kinds 0..2 of the same n_particles and n_dims, each with its own (p0..p3, osc_scale); bgk_box_anneal
+ * two box kinds 3 / 4 of the same n_particles, each with its own 12 host floats (bgk_box_energy).
+ *   schedule [n_stages + 1, 2] (DEVICE, f32): the pairs (cA_m, cB_m) = ((1 - lambda_m) / T_A, lambda_m / T_B), m = 0 .. n_stages, formed by
+ *     the caller in f64 and rounded once.  u_m = cA_m e_A + cB_m e_B in f32; a coefficient that is exactly 0 drops its term.
+ *   the protocol has n_stages * n_steps global steps, stage m = s / n_steps + 1; this call runs the steps [step_begin, step_end).  At the
+ *     first step of a stage   work += (cA_m - cA_{m-1}) e_A + (cB_m - cB_{m-1}) e_B   of the current state (f64 from the f32 operands; a
+ *     difference that is exactly 0 drops its term), then   x' = x + noise_std xi_s,  accept iff -(u_m(x') - u_m(x)) >= log r_s.
+ *   Random numbers: noise [n_stages * n_steps, B, n d] and uniforms [n_stages * n_steps, B], ROW s whatever the launch (both or neither),
+ *     or, when NULL, Philox in the counter layout of bgk_pair_mcmc: (global chain row0 + b, field 0 normals / field 1 uniform, offset + s).
+ *   e_a, e_b [B]: raw energies of either end at temperature 1, bit for bit bgk_pair_energy's / bgk_box_energy's -- read when e_valid != 0
+ *     (else computed from x), written for the final state.  work [B] (f64) and n_accepted [B] (int32, may be NULL): written
+ *     (accumulate = 0: work starts at 0) or continued (accumulate != 0).  A protocol gives the same bits however it is split into calls.
+ * BGK_EINVAL for n_stages < 1, n_steps < 1, a step range outside the protocol, noise_std < 0, noise and uniforms not both given;
+ * BGK_EUNSUPPORTED outside the envelope of bgk_pair_energy / bgk_box_energy; 0 for B == 0 or an empty step range. */
+int bgk_pair_anneal(float* x, int64_t B, int32_t n_particles, int32_t n_dims,
+                    int32_t kind_a, double a0, double a1, double a2, double a3, double osc_scale_a,
+                    int32_t kind_b, double b0, double b1, double b2, double b3, double osc_scale_b,
+                    const float* schedule, int32_t n_stages, int32_t n_steps, int32_t step_begin, int32_t step_end,
+                    double noise_std, const float* noise, const float* uniforms,
+                    uint64_t seed, uint32_t offset, int64_t row0,
+                    float* e_a, float* e_b, int32_t e_valid, double* work, int32_t* n_accepted, int32_t accumulate, void* stream);
+int bgk_box_anneal(float* x, int64_t B, int32_t n_particles,
+                   int32_t kind_a, const float* params_a, int32_t n_params_a,
+                   int32_t kind_b, const float* params_b, int32_t n_params_b,
+                   const float* schedule, int32_t n_stages, int32_t n_steps, int32_t step_begin, int32_t step_end,
+                   double noise_std, const float* noise, const float* uniforms,
+                   uint64_t seed, uint32_t offset, int64_t row0,
+                   float* e_a, float* e_b, int32_t e_valid, double* work, int32_t* n_accepted, int32_t accumulate, void* stream);
+
 /* Brownian and Langevin dynamics with the path-probability ratio on the targets of bgk_pair_energy, a whole run of steps in one launch
  * (csrc/bgk_langevin.hip), replacing the per-step op chain of BrownianFlow._forward and LangevinFlow._forward (nn/flow/stochastic/
  * langevin.py:32-45, 86-118) with f = -d e / d x at temperature 1, h = stepsize.  v == NULL, Brownian:
