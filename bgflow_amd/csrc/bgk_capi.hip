@@ -1,11 +1,14 @@
 /* bgk_capi.hip -- library-level entry points (version, error string, math probe).
  * bgk_detmath_probe(which): 0 exp, 1 log, 2 softplus, 3 silu, 4 tanh (the deterministic forms of bgk_detmath.h), 5 erf_fast,
- * 6 erfinv_fast (bgk_erf.h; on the hardware log2 / exp2, so not bit-equal to a host evaluation); any other code copies the input. */
+ * 6 erfinv_fast (bgk_erf.h; on the hardware log2 / exp2, so not bit-equal to a host evaluation); 7 u01 and 8 / 9 the cos / sin
+ * member of philox_normal4 (bgk_philox.h) with the input's bit pattern as the 32-bit Philox word -- element i pairs the words of
+ * elements (i, i + 1), the last element pairs with itself; any other code copies the input. */
 #include <stdarg.h>
 
 #include "bgk_common.h"
 #include "bgk_erf.h"
 #include "bgk_fused2.h"
+#include "bgk_philox.h"
 
 extern int bgk_affine_variant;      /* bgk_fused_affine.hip */
 
@@ -54,6 +57,15 @@ __global__ void detmath_probe_kernel(const float* x, int64_t n, int which, float
         case 4: r = bgk_tanhf(v); break;
         case 5: r = erf_fast(v); break;
         case 6: r = erfinv_fast(v); break;      /* elements 64 k .. 64 k + 63 share a wave (and its tail-branch ballot) */
+        case 7: r = u01(__float_as_uint(v)); break;
+        case 8: case 9: {
+            const uint32_t w0 = __float_as_uint(v), w1 = __float_as_uint(x[i + 1 < n ? i + 1 : i]);
+            const uint32_t o[4] = {w0, w1, w0, w1};
+            float nrm[4];
+            philox_normal4(o, nrm);
+            r = nrm[which - 8];
+            break;
+        }
         default: r = v;
     }
     out[i] = r;

@@ -10,8 +10,9 @@
  * tile through LDS (the tile is the memory image of contiguous rows: coalesced loads), lane = row works on LDS with a row stride
  * made odd (conflict-free banks), and the [64][n_out] tile leaves the same way.
  * Sheaf draw of MULT_FWD: Philox4x32-10 with the counter layout of bgk_philox.hip -- (row low, row high, field 0 << 20 | 4-column
- * block, call offset), key = seed -- a pure function of (seed, call, GLOBAL row, column); u = ((x >> 8) + 0.5) 2^-24. */
+ * block, call offset), key = seed -- a pure function of (seed, call, GLOBAL row, column); u = u01 of bgk_philox.h, below 1. */
 #include "bgk_common.h"
+#include "bgk_philox.h"
 
 namespace {
 
@@ -29,18 +30,6 @@ struct CArgs {
     float logdet;
     uint32_t seed_lo, seed_hi, offset;
 };
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&o)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-__device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * 5.9604644775390625e-08f; }   /* 2^-24 */
 
 /* torch's remainder for a positive divisor: fmod, then + b if the result is non-zero and negative */
 __device__ __forceinline__ float remainder_pos(float a, float b) {
@@ -122,7 +111,8 @@ __global__ __launch_bounds__(256) void colmap_kernel(CArgs a) {
                         const int w = src & 3;
                         uu = u01(w == 0 ? o[0] : w == 1 ? o[1] : w == 2 ? o[2] : o[3]);
                     }
-                    /* u01 rounds to 1.0 for the 128 largest words (probability 2^-25): keep the sheaf below m */
+                    /* u01 is at most 1 - 2^-24 (unclamped, the 256 largest words, probability 2^-24, would round to 1.0), but the
+                     * f32 product u * m can still round up to m, and handed-in uniforms are the caller's: keep the sheaf below m */
                     float sheaf = floorf(uu * p0);
                     sheaf = sheaf > p0 - 1.0f ? p0 - 1.0f : sheaf;
                     y = (x + sheaf) / p0;

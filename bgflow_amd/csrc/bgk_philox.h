@@ -1,5 +1,5 @@
 /* bgk_philox.h -- the counter-based generator of bgk_philox.hip, shared with the kernels that draw inside their own launch
- * (bgk_mcmc.hip): Philox4x32-10 (Salmon et al., SC'11), the word -> (0, 1) map and the Box-Muller pair on the deterministic
+ * (bgk_mcmc.hip): Philox4x32-10 (Salmon et al., SC'11), the word -> [2^-25, 1 - 2^-24] map and the Box-Muller pair on the deterministic
  * log / sincos of bgk_detmath.h.  Counter layout of every user: (global row low, high, field << 20 | 4-column block, call offset),
  * key = seed; one call gives the four columns 4 cb .. 4 cb + 3 of a row. */
 #ifndef BGK_PHILOX_H
@@ -17,7 +17,11 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     }
     o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
 }
-__device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * 5.9604644775390625e-08f; }   /* 2^-24 */
+/* u = ((x >> 8) + 0.5) 2^-24 in f32, in [2^-25, 1 - 2^-24].  The sum needs 25 significand bits: exact for x >> 8 < 2^23, rounded
+ * to even above (|error| <= 2^-25, mean 0).  Unclamped, the 256 largest words would round to 1.0; the minimum moves only those. */
+__device__ __forceinline__ float u01(uint32_t x) {
+    return __builtin_fminf(((float)(x >> 8) + 0.5f) * 5.9604644775390625e-08f /* 2^-24 */, 0x1.fffffep-1f);
+}
 
 /* four standard normals from the four words of one call: r = sqrt(-2 ln u1), (r cos 2 pi u2, r sin 2 pi u2) per word pair */
 __device__ __forceinline__ void philox_normal4(const uint32_t (&o)[4], float (&v)[4]) {

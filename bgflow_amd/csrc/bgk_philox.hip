@@ -8,7 +8,8 @@
  * are pinned in tests/test_oracle_golden.py through oracle/philox.py).  One 128-bit counter = (row low, row high, field << 20 |
  * 4-column block, call offset), key = seed: the stream is a pure function of (seed, offset, GLOBAL row, field, column) -- independent
  * of the launch geometry and of how a batch is sharded over ranks (`row0` = first global row of this launch).
- *   uniform: u = ((x >> 8) + 0.5) 2^-24 in (0, 1), then low + u (high - low)
+ *   uniform: u = min(((x >> 8) + 0.5) 2^-24, 1 - 2^-24) in f32 (u01 of bgk_philox.h: in [2^-25, 1 - 2^-24], rounded to even in
+ *            the upper half), then low + u (high - low)
  *   normal:  Box-Muller on two such uniforms: r = sqrt(-2 ln u1), (r cos 2 pi u2, r sin 2 pi u2); value = mean + scale * n
  *            (scale = sigma sqrt(T)); ln / sincos are the deterministic forms of bgk_detmath.h (same bits as the C oracle)
  * Layout: lane = row of a 64-row tile; a field's [64][d] tile is assembled in LDS (the tile's memory image when rows are contiguous)

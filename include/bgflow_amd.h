@@ -55,7 +55,9 @@ int bgk_set_option(int32_t option, int32_t value);
 
 /* Deterministic-math probe: out[i] = f(x[i]) on the device with the same primitives the spline
  * kernels use (which: 0 exp, 1 log, 2 softplus(beta=ln2/(1-1e-3)), 3 silu, 4 tanh), or with the erf / erfinv
- * of the domain maps (5 erf_fast, 6 erfinv_fast; 256-thread blocks: elements 64 k .. 64 k + 63 share a wave).
+ * of the domain maps (5 erf_fast, 6 erfinv_fast; 256-thread blocks: elements 64 k .. 64 k + 63 share a wave),
+ * or with the generator's word maps, the bit pattern of x[i] being a 32-bit Philox word (7 the uniform u01 in
+ * [2^-25, 1 - 2^-24]; 8 / 9 the cos / sin Box-Muller normal of the words (x[i], x[i + 1]), the last with itself).
  * Test hook. */
 int bgk_detmath_probe(const float* x, int64_t n, int32_t which, float* out, void* stream);
 

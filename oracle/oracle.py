@@ -374,7 +374,8 @@ def global_ic_inverse(bonds, angles, torsions, x0, R, z_matrix, normalize_angles
 
 
 def detmath_probe(x, which):
-    names = {"exp": 0, "log": 1, "softplus": 2, "silu": 3, "tanh": 4}
+    # u01 / normal_cos / normal_sin: x holds 32-bit Philox words as bit patterns (``words.view(np.float32)``)
+    names = {"exp": 0, "log": 1, "softplus": 2, "silu": 3, "tanh": 4, "u01": 7, "normal_cos": 8, "normal_sin": 9}
     x = _np(x, np.float32)
     out = np.empty_like(x)
     lib().bgo_detmath_probe(_ptr(x), _c_i64(x.size), _c_int(names[which]), _ptr(out))

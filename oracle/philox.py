@@ -25,12 +25,15 @@ def philox4x32_10(ctr, key):
 
 
 def u01(x):
-    """((x >> 8) + 0.5) 2^-24 in f32: exact (24-bit integer + 0.5, scaled by a power of two)"""
-    return ((x >> np.uint32(8)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -24)
+    """min(((x >> 8) + 0.5) 2^-24, 1 - 2^-24) in f32, the kernels' u01 (csrc/bgk_philox.h): in [2^-25, 1 - 2^-24].  The 24-bit
+    integer + 0.5 needs 25 significand bits: exact for x >> 8 < 2^23, rounded to even above (|error| <= 2^-25).  Without the clamp
+    the 256 largest words would round to 1.0; the clamp changes those and no other."""
+    u = ((x >> np.uint32(8)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -24)
+    return np.minimum(u, np.float32(1.0 - 2.0 ** -24))
 
 
 def sample_field(seed, offset, field, n_rows, d, kind, row0=0):
-    """raw variates of one field as the kernel draws them: kind 0 -> u in (0, 1) [n_rows, d] (bit-exact), kind 1 -> standard
+    """raw variates of one field as the kernel draws them: kind 0 -> u in [2^-25, 1 - 2^-24] [n_rows, d] (bit-exact), kind 1 -> standard
     normals by Box-Muller on consecutive word pairs (f64 arithmetic here: the kernel's f32 forms agree to ~1e-6)"""
     rows = np.arange(row0, row0 + n_rows, dtype=np.uint64)
     out = np.zeros((n_rows, 4 * ((d + 3) // 4)), np.float64 if kind == 1 else np.float32)
