@@ -34,10 +34,11 @@ _MAP = {
     "nn.flow.crd_transform": "ic",
     "nn.flow.crd_transform.ic": "ic",
     "nn.flow.crd_transform.pca": "ic",
-    "distribution": ("distributions", "particles", "sampling"),
+    "distribution": ("distributions", "particles", "sampling", "mixture"),
     "distribution.distributions": "distributions",
     "distribution.normal": ("distributions", "particles"),
     "distribution.product": "distributions",
+    "distribution.mixture": "mixture",
     "distribution.energy": ("distributions", "particles"),
     "distribution.energy.lennard_jones": "particles",
     "distribution.energy.multi_double_well_potential": "particles",

@@ -302,6 +302,13 @@ class BoxPlan(collections.namedtuple("BoxPlan", "kind n_particles params tempera
     n_dims = 2
 
 
+class MixturePlan(collections.namedtuple("MixturePlan", "dist n_components dim temperature")):
+    """the plan of a mixture of diagonal normals over ONE tensor (mixture.MixtureDistribution; the bgk_mixture_* entries of
+    csrc/bgk_mixture.hip): a log-sum-exp over components is no sum of fields, so it is a plan kind of its own.  ``dist`` holds the
+    parameter tables and the live log-weights.  Four entries: the callers that fold field plans pass it by."""
+    __slots__ = ()
+
+
 def _own_methods(obj, cls):
     """``obj`` evaluates its energy with the code of ``cls`` (no subclass override of ``energy`` / ``_energy``)"""
     return all(getattr(type(obj), name, None) is getattr(cls, name) for name in ("energy", "_energy"))
@@ -354,6 +361,12 @@ def _kernel_plan(dist, temperature):
             if any(getattr(type(dist), name, None) is not getattr(owner, name, None) for name in ("energy", "_energy")):
                 return None
             return pair(temperature)
+        mix = getattr(dist, "_mixture_kernel", None)
+        if mix is not None:              # a mixture of diagonal normals (mixture.py): a MixturePlan, under the same rule
+            owner = next(c for c in type(dist).__mro__ if "_mixture_kernel" in c.__dict__)
+            if any(getattr(type(dist), name, None) is not getattr(owner, name, None) for name in ("energy", "_energy")):
+                return None
+            return mix(temperature)
         if hasattr(dist, "delegate"):
             from . import clipped
             if isinstance(dist, (clipped.LinLogCutEnergy, clipped.GradientClippedEnergy)):
@@ -375,6 +388,9 @@ def kernel_energy(dist, xs, temperature=1.0):
     if isinstance(plan, (PairPlan, BoxPlan)):
         from . import particles
         return particles.pair_energy(plan, xs)
+    if isinstance(plan, MixturePlan):
+        from . import mixture
+        return mixture.mixture_energy(plan, xs)
     specs, dims, c_in, c_out, t_eff, *wrap = plan
     if not (_fields_ok(xs, dims) and isinstance(temperature, (int, float)) and temperature > 0):
         return None
@@ -393,6 +409,9 @@ def kl_loss_sums(target, xs, dlogp, temperature=1.0, drop_nonfinite=False):
     if isinstance(plan, (PairPlan, BoxPlan)):    # a particle system over one tensor: the same pair from bgk_pair_energy_kl_sums / bgk_box_energy_kl_sums
         from . import particles
         return particles.pair_kl_loss_sums(plan, xs, dlogp, drop_nonfinite)
+    if isinstance(plan, MixturePlan):            # a mixture of diagonal normals: the same pair from bgk_mixture_energy
+        from . import mixture
+        return mixture.mixture_kl_loss_sums(plan, xs, dlogp, drop_nonfinite)
     specs, dims, c_in, c_out, t_eff, *wrap = plan
     if not (_fields_ok(xs, dims) and isinstance(temperature, (int, float)) and temperature > 0 and torch.is_tensor(dlogp)
             and dlogp.is_cuda and dlogp.numel() == xs[0].shape[0]):
@@ -431,6 +450,8 @@ def philox_sample(fields, n_samples, device, seed, offset, row0=0, want_energy=F
 _PHILOX_STREAMS = [0]          # next automatically assigned stream id (construction-order fallback, see _FusedSampling)
 _PHILOX_LIVE = {}              # stream id -> weak reference of the live object that draws from it
 PHILOX_MAX_WIDTH = 160         # widest field bgk_philox_fields assembles in its LDS tile (4 waves x 64 rows x d floats)
+MIXTURE_MAX_COMPONENTS = 64    # most components bgk_mixture_* keep in their [K][64] LDS table (BGK_MIXTURE_MAX_COMPONENTS)
+MIXTURE_MAX_WIDTH = 128        # widest row bgk_mixture_* stage (a [64][d | 1] tile in LDS; BGK_MIXTURE_MAX_WIDTH)
 COLMAP_MAX_WIDTH = 256         # widest field bgk_colmap stages (a [64][n_in] and a [64][n_out] tile per wave in LDS; BGK_COLMAP_MAX_WIDTH)
 
 
@@ -491,16 +512,27 @@ class _FusedSampling(torch.nn.Module):
             _philox_claim(self, k)
         return st
 
-    def _fused_sample(self, fields, n_samples, device, temperature, c_out=0.0):
-        import weakref
+    def _philox_seed(self):
+        """the Philox key of this object's draws: torch's seed mixed with the data-parallel rank and the object's stream id"""
         from . import dp
-        st = self._philox_ids()
-        seed = (dp.rank_seed(torch.initial_seed()) + 0x9E3779B97F4A7C15 * (st[0] + 1)) & (2 ** 64 - 1)
+        return (dp.rank_seed(torch.initial_seed()) + 0x9E3779B97F4A7C15 * (self._philox_ids()[0] + 1)) & (2 ** 64 - 1)
+
+    def _philox_next(self):
+        """(seed, offset) of the next fused draw; advances the call counter"""
+        seed, st = self._philox_seed(), self._philox_ids()
         off, st[1] = st[1], st[1] + 1
-        outs, energy = philox_sample(fields, n_samples, device, seed, off, want_energy=True, c_out=c_out)
-        # the energy is valid for exactly these tensor objects in exactly this state: weak references (no sample batch is pinned)
-        # + their version counters (any in-place edit invalidates the cache)
+        return seed, off
+
+    def _philox_remember(self, outs, temperature, energy):
+        """keep the energy [B, 1] a fused draw reported for its tensors ``outs``: valid for exactly these tensor objects in exactly this
+        state -- weak references (no sample batch is pinned) + their version counters (any in-place edit invalidates the cache)"""
+        import weakref
         self.__dict__["_philox_last"] = ([weakref.ref(t) for t in outs], [t._version for t in outs], float(temperature), energy)
+
+    def _fused_sample(self, fields, n_samples, device, temperature, c_out=0.0):
+        seed, off = self._philox_next()
+        outs, energy = philox_sample(fields, n_samples, device, seed, off, want_energy=True, c_out=c_out)
+        self._philox_remember(outs, temperature, energy)
         return outs
 
     def _fused_energy(self, xs, temperature):

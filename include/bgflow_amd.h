@@ -944,6 +944,38 @@ int bgk_philox_fields(uint64_t seed, uint32_t offset, int64_t row0, int32_t n_fi
                       const int32_t* d, const int32_t* kind, const float* const* p0, const float* const* p1,
                       const float* scale, const float* e_const, double c_out, int64_t B, float* energy, void* stream);
 
+/* A mixture of K diagonal normals over one tensor x [B, d] (row stride ldx) in one launch forward and one backward (csrc/bgk_mixture.hip),
+ * replacing MixtureDistribution._energy / _log_assignments (distribution/mixture.py:41-47: K component energies, a [B, 1, K] stack and a
+ * logsumexp per call, the same again under autograd).  Device tables: mu [K, d], h [K, d] (inverse variances; 1 without a covariance),
+ * logz [K] (d / 2 log 2 pi + 1/2 sum log variances), logw [K] (normalised log-weights; -inf = a component of weight zero).  Per row, f32:
+ *   q_k = sum_j (x_j - mu_kj)^2 h_kj (ascending j),  a_k = (logw_k - logz_k) - q_k / 2,  m = max_k a_k,
+ *   s = sum_k exp(a_k - m) (ascending k),  u = -(m + log s) / temperature        (energy/base.py:124-146: NOT the tempered mixture)
+ * exp / log of csrc/bgk_detmath.h, an exp argument below -80 giving exactly 0.  A row's result depends on that row alone.
+ * bgk_mixture_energy: u [B]; neg_e [B, K] = -(q_k / 2 + logz_k) (may be NULL); loss_sums [2] (f64, may be NULL) = [sum_b (u[b] -
+ *   dlogp[b]), samples kept] with the workspace partial [nblk, 2], as bgk_energy_fields.
+ * bgk_mixture_energy_backward: with r_bk = exp(a_k - m) / s (m and s formed again from the row; u only masks the loss-sum form) and g_b = g_u[b] or, in the loss-sum form (g_u == NULL),
+ *   g_scalar[0] for the kept samples:  g_x[b, j] = (g_b / temperature) sum_k r_bk (x_j - mu_kj) h_kj (row stride ldg; may be NULL),
+ *   g_dlogp[b] = -g_b (may be NULL),  g_logw[k] = -(1 / temperature) sum_b g_b r_bk (may be NULL; else summed in f64 in a fixed order
+ *   through the workspace wpartial [nblk, K] of doubles).  A row with g_b == 0 contributes exactly 0 to g_x and g_logw.
+ * bgk_mixture_sample: row b draws the numbers bgk_philox_fields(seed, offset, row0, fields [uniform 1, normal d]) writes; the uniform
+ *   picks the first k whose running sum of exp(logw) (f32, ascending k) exceeds it (the last component of positive weight otherwise);
+ *   x[b, j] = mu_kj + n_j / sqrt(h_kj); assign [B] (int32, may be NULL) = k; energy [B] (may be NULL) = u of the sample at temperature 1.
+ * Envelope: 1 <= K <= BGK_MIXTURE_MAX_COMPONENTS, 1 <= d <= BGK_MIXTURE_MAX_WIDTH; BGK_EUNSUPPORTED beyond. */
+#define BGK_MIXTURE_MAX_COMPONENTS 64
+#define BGK_MIXTURE_MAX_WIDTH 128
+int bgk_mixture_energy(const float* x, int64_t ldx, int64_t B, int32_t n_components, int32_t d,
+                       const float* mu, const float* h, const float* logz, const float* logw, double temperature,
+                       float* u, float* neg_e, const float* dlogp, int32_t drop_nonfinite, float* partial, int32_t nblk,
+                       double* loss_sums, void* stream);
+int bgk_mixture_energy_backward(const float* x, int64_t ldx, int64_t B, int32_t n_components, int32_t d,
+                                const float* mu, const float* h, const float* logz, const float* logw, double temperature,
+                                const float* u, const float* g_u, const float* g_scalar, const float* dlogp,
+                                int32_t drop_nonfinite, float* g_dlogp, float* g_x, int64_t ldg,
+                                float* g_logw, double* wpartial, int32_t nblk, void* stream);
+int bgk_mixture_sample(uint64_t seed, uint32_t offset, int64_t row0, int64_t B, int32_t n_components, int32_t d,
+                       const float* mu, const float* h, const float* logz, const float* logw,
+                       float* x, int64_t ldx, int32_t* assign, float* energy, void* stream);
+
 /* Column map of one [B, n_in] f32 field with contiguous rows into a [B, n_out] one, in one launch: output column j is a function of
  * at most one input column, given by table[j] = (int32 kind, int32 src, float p0, float p1) (device memory, 16 bytes per entry):
  *   0 COPY        in[src]                           index SplitFlow / MergeFlow (nn/flow/coupling.py:13-110)
