@@ -14,6 +14,7 @@ from .ic import *            # noqa: F401,F403
 from .distributions import * # noqa: F401,F403
 from .particles import *     # noqa: F401,F403
 from .mixture import *       # noqa: F401,F403
+from .molecule import *      # noqa: F401,F403
 from .dynamics import *      # noqa: F401,F403
 from .sampling import *      # noqa: F401,F403
 from .annealing import *     # noqa: F401,F403
@@ -29,7 +30,7 @@ from .free_energy import *   # noqa: F401,F403
 from .permutation import *   # noqa: F401,F403
 from .analysis import free_energy_bootstrap, bootstrap_histogram   # noqa: F401
 from .umbrella import *      # noqa: F401,F403
-from . import analysis, annealing, clipped, configs, dp, dynamics, factory, free_energy, mixture, particles, permutation, sampling, stochastic, training, umbrella, utils      # noqa: F401
+from . import analysis, annealing, clipped, configs, dp, dynamics, factory, free_energy, mixture, molecule, particles, permutation, sampling, stochastic, training, umbrella, utils      # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -27,7 +27,7 @@ from .transformer import AffineTransformer, ConditionalSplineTransformer
 from .utils import hash_init_, synth
 
 __all__ = ["ala2_system", "make_readme_generator", "make_affine8_generator", "make_ala2_spline_generator",
-           "make_ala2_augmented_generator", "IC_FIELDS"]
+           "make_ala2_augmented_generator", "make_ala2_mm_generator", "synthetic_forcefield", "ala2_global_z_matrix", "IC_FIELDS"]
 
 IC_FIELDS = ("BONDS", "ANGLES", "TORSIONS", "FIXED")
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "ala2_system.npz")
@@ -132,8 +132,9 @@ class _NormalMarginal(torch.nn.Module):
 
 
 def make_ala2_spline_generator(device=None, dtype=torch.float32, hidden=(128, 128), num_bins=8,
-                               n_torsion_blocks=4, n_bond_blocks=4):
-    """cfg 3 / 4: 16 RQ-spline couplings + icdf domain maps + Mixed IC -> 66 Cartesian dof."""
+                               n_torsion_blocks=4, n_bond_blocks=4, target=None):
+    """cfg 3 / 4: 16 RQ-spline couplings + icdf domain maps + Mixed IC -> 66 Cartesian dof.  ``target``: the target energy over the 66
+    Cartesian coordinates (default: the Gaussian around the reference geometry)."""
     zmat, rigid, xyz = ala2_system()
     ic = MixedCoordinateTransformation(ala2_whitening_data(dtype), zmat, rigid, keepdims=9, raise_warnings=False)
     dims = {"BONDS": ic.dim_bonds, "ANGLES": ic.dim_angles, "TORSIONS": ic.dim_torsions, "FIXED": ic.dim_fixed}
@@ -152,9 +153,84 @@ def make_ala2_spline_generator(device=None, dtype=torch.float32, hidden=(128, 12
     flow = hash_init_(SequentialFlow(layers))
     prior = ProductDistribution([UniformDistribution(torch.zeros(dims[f], **ctx), torch.ones(dims[f], **ctx))
                                  for f in IC_FIELDS])
-    target = NormalDistribution(66, torch.tensor(xyz[0], dtype=dtype))
+    if target is None:
+        target = NormalDistribution(66, torch.tensor(xyz[0], dtype=dtype))
     gen = BoltzmannGenerator(prior, flow, target)
     return gen.to(device) if device is not None else gen
+
+
+def ala2_global_z_matrix():
+    """a global Z-matrix [22, 4] of capped alanine (-1: no reference atom) from ``ala2_system()``: the rigid block's atoms first, chained
+    on its second atom (r0; r1 r0; r2 r1 r0; r3 r1 r0 r2; r4 r1 r0 r3), then the relative rows"""
+    z, rigid, _ = ala2_system()
+    r = [int(v) for v in rigid]
+    rows = [[r[0], -1, -1, -1], [r[1], r[0], -1, -1], [r[2], r[1], r[0], -1]] + [[r[m], r[1], r[0], r[m - 1]] for m in range(3, len(r))]
+    return np.array(rows + [[int(v) for v in row] for row in z], np.int64)
+
+
+def _dihedral(p, i, j, k, l):
+    b1, b2, b3 = p[j] - p[i], p[k] - p[j], p[l] - p[k]
+    n1, n2 = np.cross(b1, b2), np.cross(b2, b3)
+    return float(np.arctan2(np.linalg.norm(b2) * (b1 @ n2), n1 @ n2))
+
+
+def synthetic_forcefield(z_matrix, xyz, seed=0, unit_energy=1.0):
+    """A ``MolecularMechanicsEnergy`` on the topology of a global Z-matrix [n, 4] (rows ``atom, bond, angle, torsion partner``; -1: none)
+    with the geometry ``xyz`` [n, 3] (nm) as its bonded minimum.  This is a molecule-SHAPED TEST TARGET, NOT AMBER or any other
+    published force field: its parameters are made up.
+
+      * a bond, an angle and a torsion per Z-matrix row that names the partners, with r0 / theta0 of ``xyz`` and the torsion's minimum at
+        the dihedral of ``xyz`` (periodicity 1, 2, 3, 1, ... by row); force constants 2.5e5 kJ/mol/nm^2, 400 kJ/mol/rad^2, 5 kJ/mol;
+      * per-atom charge (uniform in [-0.5, 0.5], shifted to a neutral molecule), sigma (uniform in [0.15, 0.35] nm) and epsilon (uniform
+        in [0.05, 0.5] kJ/mol) from ``numpy.random.RandomState(seed)``;
+      * 1-2 and 1-3 pairs of the bond graph excluded; 1-4 pairs as exceptions with the Coulomb product scaled by 1 / 1.2 and the
+        Lennard-Jones epsilon by 0.5."""
+    from .molecule import MolecularMechanicsEnergy
+    z = np.asarray(z_matrix, np.int64)
+    p = np.asarray(xyz, np.float64).reshape(-1, 3)
+    n = len(p)
+    bonds = np.array([row[:2] for row in z if row[1] >= 0], np.int64).reshape(-1, 2)
+    angles = np.array([row[:3] for row in z if row[2] >= 0], np.int64).reshape(-1, 3)
+    torsions = np.array([row[:4] for row in z if row[3] >= 0], np.int64).reshape(-1, 4)
+
+    def angle(i, j, k):
+        a, b = p[i] - p[j], p[k] - p[j]
+        return float(np.arctan2(np.linalg.norm(np.cross(a, b)), a @ b))
+
+    periodicity = 1 + np.arange(len(torsions), dtype=np.int64) % 3
+    phi0 = np.array([_dihedral(p, *t) for t in torsions]).reshape(-1)
+    rng = np.random.RandomState(seed)
+    charge = rng.uniform(-0.5, 0.5, n)
+    charge -= charge.mean()
+    sigma, epsilon = rng.uniform(0.15, 0.35, n), rng.uniform(0.05, 0.5, n)
+    near = np.eye(n, dtype=bool)                          # the bond graph's neighbours within 1, 2, 3 bonds
+    adj = np.zeros((n, n), bool)
+    adj[bonds[:, 0], bonds[:, 1]] = adj[bonds[:, 1], bonds[:, 0]] = True
+    within = [near]
+    for _ in range(3):
+        within.append(within[-1] | ((within[-1].astype(np.int64) @ adj.astype(np.int64)) > 0))
+    i, j = np.triu_indices(n, 1)
+    keep = within[3][i, j]
+    i, j = i[keep], j[keep]
+    one_four = ~within[2][i, j]
+    return MolecularMechanicsEnergy(
+        n,
+        bonds=(bonds, np.array([np.linalg.norm(p[a] - p[b]) for a, b in bonds]).reshape(-1), np.full(len(bonds), 2.5e5)),
+        angles=(angles, np.array([angle(*t) for t in angles]).reshape(-1), np.full(len(angles), 400.0)),
+        torsions=(torsions, periodicity, periodicity * phi0 - np.pi, np.full(len(torsions), 5.0)),
+        nonbonded=(charge, sigma, epsilon),
+        exceptions=(np.stack([i, j], axis=1), np.where(one_four, charge[i] * charge[j] / 1.2, 0.0), 0.5 * (sigma[i] + sigma[j]),
+                    np.where(one_four, 0.5 * np.sqrt(epsilon[i] * epsilon[j]), 0.0)),
+        unit_energy=unit_energy)
+
+
+def make_ala2_mm_generator(device=None, dtype=torch.float32, seed=0, unit_energy=2.494, **kwargs):
+    """the alanine-dipeptide spline generator (``make_ala2_spline_generator``, same flow and prior) with the synthetic force field of
+    ``synthetic_forcefield(ala2_global_z_matrix(), xyz, seed)`` as its target in place of the Gaussian; ``unit_energy``: kT in kJ/mol
+    (2.494 at 300 K)"""
+    _, _, xyz = ala2_system()
+    target = synthetic_forcefield(ala2_global_z_matrix(), xyz.reshape(-1, 3), seed=seed, unit_energy=unit_energy)
+    return make_ala2_spline_generator(device=device, dtype=dtype, target=target, **kwargs)
 
 
 def _affine_coupling(what, on, dims, circular, slot, hidden=(128, 128)):

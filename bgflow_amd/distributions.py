@@ -309,6 +309,13 @@ class MixturePlan(collections.namedtuple("MixturePlan", "dist n_components dim t
     __slots__ = ()
 
 
+class MoleculePlan(collections.namedtuple("MoleculePlan", "dist n_atoms unit_energy temperature")):
+    """the plan of a force-field energy over ONE tensor of Cartesian coordinates (molecule.MolecularMechanicsEnergy; the bgk_molecule_*
+    entries of csrc/bgk_molecule.hip): bonded terms read from tables are no sum of fields and no particle kind, so it is a plan kind of
+    its own.  ``dist`` holds the term tables.  Four entries: the callers that fold field plans pass it by."""
+    __slots__ = ()
+
+
 def _own_methods(obj, cls):
     """``obj`` evaluates its energy with the code of ``cls`` (no subclass override of ``energy`` / ``_energy``)"""
     return all(getattr(type(obj), name, None) is getattr(cls, name) for name in ("energy", "_energy"))
@@ -367,6 +374,12 @@ def _kernel_plan(dist, temperature):
             if any(getattr(type(dist), name, None) is not getattr(owner, name, None) for name in ("energy", "_energy")):
                 return None
             return mix(temperature)
+        mol = getattr(dist, "_molecule_kernel", None)
+        if mol is not None:              # a force-field energy (molecule.py): a MoleculePlan, under the same rule
+            owner = next(c for c in type(dist).__mro__ if "_molecule_kernel" in c.__dict__)
+            if any(getattr(type(dist), name, None) is not getattr(owner, name, None) for name in ("energy", "_energy")):
+                return None
+            return mol(temperature)
         if hasattr(dist, "delegate"):
             from . import clipped
             if isinstance(dist, (clipped.LinLogCutEnergy, clipped.GradientClippedEnergy)):
@@ -391,6 +404,9 @@ def kernel_energy(dist, xs, temperature=1.0):
     if isinstance(plan, MixturePlan):
         from . import mixture
         return mixture.mixture_energy(plan, xs)
+    if isinstance(plan, MoleculePlan):
+        from . import molecule
+        return molecule.molecule_energy(plan, xs)
     specs, dims, c_in, c_out, t_eff, *wrap = plan
     if not (_fields_ok(xs, dims) and isinstance(temperature, (int, float)) and temperature > 0):
         return None
@@ -412,6 +428,9 @@ def kl_loss_sums(target, xs, dlogp, temperature=1.0, drop_nonfinite=False):
     if isinstance(plan, MixturePlan):            # a mixture of diagonal normals: the same pair from bgk_mixture_energy
         from . import mixture
         return mixture.mixture_kl_loss_sums(plan, xs, dlogp, drop_nonfinite)
+    if isinstance(plan, MoleculePlan):           # a force-field energy: the same pair from bgk_molecule_energy_kl_sums
+        from . import molecule
+        return molecule.molecule_kl_loss_sums(plan, xs, dlogp, drop_nonfinite)
     specs, dims, c_in, c_out, t_eff, *wrap = plan
     if not (_fields_ok(xs, dims) and isinstance(temperature, (int, float)) and temperature > 0 and torch.is_tensor(dlogp)
             and dlogp.is_cuda and dlogp.numel() == xs[0].shape[0]):

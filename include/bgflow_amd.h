@@ -976,6 +976,41 @@ int bgk_mixture_sample(uint64_t seed, uint32_t offset, int64_t row0, int64_t B, 
                        const float* mu, const float* h, const float* logz, const float* logw,
                        float* x, int64_t ldx, int32_t* assign, float* energy, void* stream);
 
+/* A classical force-field energy over the Cartesian coordinates x [B, 3 n_atoms] (contiguous rows; nm) of one molecule, one launch forward and
+ * one backward (csrc/bgk_molecule.hip; the formulas: csrc/bgk_molecule_terms.h), in the forms and units (kJ/mol, rad) of OpenMM's forces:
+ *   bonds     HarmonicBondForce       k / 2 (r - r0)^2
+ *   angles    HarmonicAngleForce      k / 2 (theta - theta0)^2 at the middle atom
+ *   torsions  PeriodicTorsionForce    k (1 + cos(n phi - phase)), n = 1..6, phi the IUPAC dihedral (trans = pi); several terms may share atoms
+ *   pairs     NonbondedForce with NoCutoff: 4 eps ((sigma / r)^12 - (sigma / r)^6) + 138.935458 qq / r over the pairs i < j, with the
+ *             combination rules (Lorentz-Berthelot), exclusions and exceptions already applied by the caller
+ * u[b] = E(x[b]) / unit_energy / temperature (energy/base.py:124-146).  Terms are added in table order, pairs in ascending (i, j) order, in
+ * f32: deterministic, and a row's result depends on that row alone.  A pair that interacts at distance 0 gives u = +inf and no gradient.
+ * `tables`: ONE device buffer of int32 words, 16-byte aligned (f32 values as their bits; bgflow_amd/molecule.py packs it):
+ *   [n_bonds][4]     (i | j << 6,  r0,  k,  0)                                      atoms in 6-bit fields
+ *   [n_angles][4]    (i | j << 6 | k << 12,  theta0,  k,  0)
+ *   [n_torsions][4]  (i | j << 6 | k << 12 | l << 18 | n << 24,  k,  k cos(phase),  k sin(phase))
+ *   [n_pairs][3]     (138.935458 qq_ij,  sigma_ij,  4 eps_ij), n_pairs = n_atoms (n_atoms - 1) / 2 or 0; qq = 0 and eps = 0: excluded
+ * bgk_molecule_energy_kl_sums: the same launch + the KL integrand's sums: loss_sums [2] (f64) = [sum_b (u[b] - dlogp[b]), samples kept]
+ *   (non-finite ones dropped if drop_nonfinite), as bgk_pair_energy_kl_sums but summed in f64 throughout: workspace partial [nblk, 2] DOUBLES.
+ * bgk_molecule_energy_backward: g_x[b] = g_row (d E / d x)(x[b]) / unit_energy / temperature (contiguous rows); g_row = g_u[b], or, in the
+ *   loss-sum form (g_u == NULL), g_scalar[0] for the kept samples (u: the energies the forward wrote), with g_dlogp[b] = -g_row (g_dlogp
+ *   may be NULL).  A row with g_row == 0 is written as exact zeros.
+ * Envelope: 2 <= n_atoms <= 64, n_bonds <= 256, n_angles <= 512, n_torsions <= 1024; BGK_EUNSUPPORTED beyond (the caller's torch formulas). */
+#define BGK_MOLECULE_MAX_ATOMS 64
+#define BGK_MOLECULE_MAX_BONDS 256
+#define BGK_MOLECULE_MAX_ANGLES 512
+#define BGK_MOLECULE_MAX_TORSIONS 1024
+int bgk_molecule_energy(const float* x, int64_t B, int32_t n_atoms, int32_t n_bonds, int32_t n_angles, int32_t n_torsions,
+                        int32_t n_pairs, const int32_t* tables, double unit_energy, double temperature, float* u, void* stream);
+int bgk_molecule_energy_kl_sums(const float* x, int64_t B, int32_t n_atoms, int32_t n_bonds, int32_t n_angles, int32_t n_torsions,
+                                int32_t n_pairs, const int32_t* tables, double unit_energy, double temperature, float* u,
+                                const float* dlogp, int32_t drop_nonfinite, double* partial, int32_t nblk, double* loss_sums,
+                                void* stream);
+int bgk_molecule_energy_backward(const float* x, int64_t B, int32_t n_atoms, int32_t n_bonds, int32_t n_angles, int32_t n_torsions,
+                                 int32_t n_pairs, const int32_t* tables, double unit_energy, double temperature, const float* g_u,
+                                 const float* g_scalar, const float* u, const float* dlogp, int32_t drop_nonfinite,
+                                 float* g_dlogp, float* g_x, void* stream);
+
 /* Column map of one [B, n_in] f32 field with contiguous rows into a [B, n_out] one, in one launch: output column j is a function of
  * at most one input column, given by table[j] = (int32 kind, int32 src, float p0, float p1) (device memory, 16 bytes per entry):
  *   0 COPY        in[src]                           index SplitFlow / MergeFlow (nn/flow/coupling.py:13-110)
