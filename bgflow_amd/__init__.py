@@ -21,6 +21,7 @@ from .annealing import *     # noqa: F401,F403
 from .stochastic import *    # noqa: F401,F403
 from .cdf import *           # noqa: F401,F403
 from .modulo import *        # noqa: F401,F403
+from .circular import *      # noqa: F401,F403
 from .moments import *       # noqa: F401,F403
 from .bg import *            # noqa: F401,F403
 from .factory import *       # noqa: F401,F403
@@ -30,7 +31,7 @@ from .free_energy import *   # noqa: F401,F403
 from .permutation import *   # noqa: F401,F403
 from .analysis import free_energy_bootstrap, bootstrap_histogram   # noqa: F401
 from .umbrella import *      # noqa: F401,F403
-from . import analysis, annealing, clipped, configs, dp, dynamics, factory, free_energy, mixture, molecule, particles, permutation, sampling, stochastic, training, umbrella, utils      # noqa: F401
+from . import analysis, annealing, circular, clipped, configs, dp, dynamics, factory, free_energy, mixture, molecule, particles, permutation, sampling, stochastic, training, umbrella, utils      # noqa: F401
 
 __version__ = "0.1.0"
 

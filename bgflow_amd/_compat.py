@@ -21,6 +21,7 @@ _MAP = {
     "nn.flow.inverted": "flow",
     "nn.flow.cdf": "cdf",
     "nn.flow.modulo": "modulo",
+    "nn.flow.circular": "circular",
     "nn.flow.torchtransform": "modulo",
     "nn.flow.diffeq": "dynamics",
     "nn.flow.stochastic": ("flow", "stochastic"),

@@ -976,6 +976,30 @@ int bgk_mixture_sample(uint64_t seed, uint32_t offset, int64_t row0, int64_t B, 
                        const float* mu, const float* h, const float* logz, const float* logw,
                        float* x, int64_t ldx, int32_t* assign, float* energy, void* stream);
 
+/* The circular bump-mixture bijection of [0, 1] (nn/flow/circular.py: _cdf_transform and its bisection) on contiguous f32 rows
+ * y [B, d], one launch per direction and one for the backward of either (csrc/bgk_circular.hip; the arithmetic is defined in that file's
+ * header comment).  Raw conditioner outputs mu_raw, log_sigma, log_weight [B, K d] (k major) with the row pitch param_pitch, log_eps
+ * [B, d] with the row pitch eps_pitch; a pitch of 0 shares one row among the whole batch.
+ * bgk_circular_bump_transform: inverse == 0: out [B, d] = F (1 - eps) + y eps and dlogp [B] = sum_j log(f (1 - eps) + eps) (ascending
+ *   j).  inverse != 0: out = x with out(x) = y after exactly 25 halvings of [0, 1] (the midpoint of the last bracket), dlogp = -sum_j
+ *   log(..) at that x; targets outside [-1e-6, 1 + 1e-6] are counted into bad_count[0] (if not NULL) with an atomic add.
+ * bgk_circular_bump_backward: `point` is the forward's y (inverse == 0) or the inverse's x (inverse != 0), g_out [B, d] and g_dlogp [B]
+ *   the upstream gradients of that direction's two outputs; writes g_point [B, d] (the gradient of the direction's input), the
+ *   gradients of the RAW tensors g_mu_raw, g_log_sigma, g_log_weight [B, K d] (contiguous, per row also when the pitch is 0) and
+ *   g_log_eps [B, d].  The inverse's are those of the implicit-function theorem at x.  No second derivatives.
+ * Envelope: 1 <= K <= BGK_CIRCULAR_MAX_COMPONENTS, 1 <= d <= BGK_CIRCULAR_MAX_WIDTH; BGK_EUNSUPPORTED beyond. */
+#define BGK_CIRCULAR_MAX_COMPONENTS 32
+#define BGK_CIRCULAR_MAX_WIDTH 2048
+int bgk_circular_bump_transform(const float* y, const float* mu_raw, const float* log_sigma, const float* log_weight,
+                                int64_t param_pitch, const float* log_eps, int64_t eps_pitch, int64_t B,
+                                int32_t n_components, int32_t d, int32_t inverse, float* out, float* dlogp,
+                                int32_t* bad_count, void* stream);
+int bgk_circular_bump_backward(const float* point, const float* mu_raw, const float* log_sigma, const float* log_weight,
+                               int64_t param_pitch, const float* log_eps, int64_t eps_pitch, int64_t B,
+                               int32_t n_components, int32_t d, int32_t inverse, const float* g_out, const float* g_dlogp,
+                               float* g_point, float* g_mu_raw, float* g_log_sigma, float* g_log_weight, float* g_log_eps,
+                               void* stream);
+
 /* A classical force-field energy over the Cartesian coordinates x [B, 3 n_atoms] (contiguous rows; nm) of one molecule, one launch forward and
  * one backward (csrc/bgk_molecule.hip; the formulas: csrc/bgk_molecule_terms.h), in the forms and units (kJ/mol, rad) of OpenMM's forces:
  *   bonds     HarmonicBondForce       k / 2 (r - r0)^2
