@@ -32,6 +32,7 @@ import torch
 
 from .distributions import BoxPlan, Energy, PairPlan, _FusedSampling, _kernel_plan
 from .particles import _check_tensors, _target_args
+from .sampling import _chain_launch_checks, mcmc_tile_rows
 
 __all__ = ["InterpolatedEnergy", "AnnealedSwitching", "annealed_importance_sampling", "jarzynski_free_energy", "anneal_coefficients",
            "anneal_fused_by_default", "pair_anneal", "ANNEAL_MAX_STEPS_PER_LAUNCH", "ANNEAL_FUSED_MIN_ROWS"]
@@ -105,19 +106,14 @@ def pair_anneal(plan_a, plan_b, x, schedule, n_steps, step_begin, step_end, nois
     box = isinstance(plan_a, BoxPlan)
     if box != isinstance(plan_b, BoxPlan) or plan_a.n_particles != plan_b.n_particles or plan_a.n_dims != plan_b.n_dims:
         raise ValueError("pair_anneal: both ends must be pair targets of equal (n, d) or boxes of equal n")
-    if nd != plan_a.n_particles * plan_a.n_dims:
-        raise ValueError(f"pair_anneal: x has {nd} columns, the targets {plan_a.n_particles} x {plan_a.n_dims}")
-    if (noise is None) != (uniforms is None):
-        raise ValueError("pair_anneal: noise and uniforms go together")
     if schedule.dim() != 2 or schedule.shape[0] < 2 or schedule.shape[1] != 2:
         raise ValueError("pair_anneal: schedule [M + 1, 2], M >= 1")
     M, K = schedule.shape[0] - 1, int(n_steps)
     if K < 1 or not 0 <= step_begin <= step_end <= M * K:
         raise ValueError(f"pair_anneal: steps [{step_begin}, {step_end}) of {M} stages of {K} steps")
-    _check_tensors("pair_anneal", x, [(x, (B, nd)), (schedule, (M + 1, 2)), (e_a, (B,)), (e_b, (B,)), (noise, (M * K, B, nd)),
-                                      (uniforms, (M * K, B))])
+    _chain_launch_checks("pair_anneal", plan_a, x, None, noise, uniforms, M * K, n_accepted,
+                         [(schedule, (M + 1, 2)), (e_a, (B,)), (e_b, (B,))], noun="targets")
     _check_tensors("pair_anneal", x, [(work, (B,))], dtype=torch.float64)
-    _check_tensors("pair_anneal", x, [(n_accepted, (B,))], dtype=torch.int32)
     if box:
         name = "bgk_box_anneal"
         ends = (plan_a.n_particles, *_target_args(plan_a)[1:], *_target_args(plan_b)[1:])
@@ -136,7 +132,6 @@ def anneal_fused_by_default(plan_a, plan_b):
     """whether ``fused = True`` takes the kernel for these ends: where tools/anneal_time.py measured it faster than the general path,
     tiles of at least ``ANNEAL_FUSED_MIN_ROWS`` rows (its comment has the numbers).  ``fused = "always"`` takes the kernel wherever it
     accepts the state."""
-    from .sampling import mcmc_tile_rows
     return mcmc_tile_rows(plan_a.n_particles * plan_a.n_dims) >= ANNEAL_FUSED_MIN_ROWS
 
 

@@ -13,44 +13,33 @@
  *   protocol      global steps s = 0 .. M K - 1, K steps per stage, stage m = s / K + 1.  At the first step of a stage, first
  *                   W += (cA_m - cA_{m-1}) e_A + (cB_m - cB_{m-1}) e_B
  *                 of the CURRENT state, in f64 from the f32 operands (a difference that is exactly 0 drops its term, as above); then the
- *                 Metropolis step at u_m:  x' = x + noise_std xi_s,  accept iff -(u_m(x') - u_m(x)) >= log r_s  (false for a NaN on either
- *                 side, as in bgk_mcmc.hip).  Steps are taken at every stage, the last included
+ *                 Metropolis step at u_m:  x' = x + noise_std xi_s,  accept iff -(u_m(x') - u_m(x)) >= log r_s.  Steps are taken at
+ *                 every stage, the last included
  *   results       the final state, work [B] (f64), e_A and e_B of the final state, n_accepted per chain
  *
- * By the rules of bgk_pair_tile.h, and in the pattern of pair_mcmc_kernel (bgk_mcmc.hip, unchanged): one wave per workgroup, ONE LANE PER
- * CHAIN, two LDS tiles A and B at the odd row stride, the second one a multiple of 32 words behind the first; a lane's current row is in
- * one, its proposal goes into the other, accepting is a per-lane flip.  Rows move through tile_stage and a per-row tile flag.  The tile
- * height is bgk_mcmc.hip's: 64 rows up to the 63,488-byte budget, 41 rows at n d = 192.  The argument record holds two BgkPairTargets; a
- * lane keeps cur, e_a, e_b, the f64 W and acc; every proposal evaluates bgk_row_energy<D, KIND_A> and bgk_row_energy<D, KIND_B> on the
- * proposal row.
+ * A chain kernel by the rules of bgk_chain.h (sides, banks, budget, numbers, accept, carried), with 1 + 1 tiles and so bgk_mcmc.hip's
+ * tile heights; no frames.  The argument record holds two BgkPairTargets; a lane keeps cur, e_a, e_b, the f64 W and acc; every proposal
+ * evaluates bgk_row_energy<D, KIND_A> and bgk_row_energy<D, KIND_B> on the proposal row.  The numbers of global step s are row s of
+ * noise / uniforms, or Philox at offset + s.
  *
- * Random numbers: explicit -- noise [M K, B, n d] and uniforms [M K, B], row s -- or Philox4x32-10 in bgk_mcmc.hip's counter layout:
- * (global chain row0 + b, field 0 << 20 | 4-column block for the normals / 1 << 20 for the uniform, offset + s).  A pure function of
- * (seed, s, row0 + b, column).
- *
- * A launch runs the global steps [step_begin, step_end).  work, e_a, e_b and n_accepted are carried in memory between launches
- * (e_valid: read e_a / e_b instead of computing them; accumulate: continue work and n_accepted): the same bits however a protocol is
- * split, inside a stage included -- the increment belongs to the stage's first step, whichever launch runs it.
+ * A launch runs the global steps [step_begin, step_end).  With e_a, e_b and n_accepted, work is carried in memory between launches
+ * (accumulate: continue it): the same bits however a protocol is split, inside a stage included -- the increment belongs to the stage's
+ * first step, whichever launch runs it.
  *
  * Dispatch: ALL ordered pairs (KIND_A, KIND_B) are instantiated -- 3 x 3 pair kinds x 3 dimensions, 2 x 2 box kinds -- so the host
  * never swaps the ends or mirrors the table.  Plain C++ and vector stores only. */
-#include "bgk_common.h"
+#include "bgk_chain.h"
 #include "bgk_pair_terms.h"
-#include "bgk_philox.h"
 
 namespace {
 
-constexpr int AN_LDS_DYNAMIC = 63488;
-
 struct AnArgs {
-    float* x; int64_t B, row0;
-    BgkPairTarget ta, tb; int rows, tile_b;             /* tile_b: word offset of the second tile, a multiple of 32 */
+    ChainArgs c;
+    BgkPairTarget ta, tb;
     const float* schedule; int stage_steps, step_begin, step_end;
     float noise_std;
-    const float* noise; const float* uniforms;
-    uint32_t seed_lo, seed_hi, offset;
     float* e_a; float* e_b; int e_valid;
-    double* work; int* n_accepted; int accumulate;
+    double* work;
 };
 
 /* c_a e_a + c_b e_b; a coefficient that is exactly 0 drops its term */
@@ -63,24 +52,19 @@ template <int D, int KIND_A, int KIND_B>
 __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_anneal_kernel(AnArgs a) {
     extern __shared__ float s_mem[];
     __shared__ int s_sel[BGK_TILE_THREADS];             /* which tile holds row r's current state */
-    const int tid = threadIdx.x, nd = a.ta.nd, S = nd | 1;
-    const int64_t n_tiles = (a.B + a.rows - 1) / a.rows;
+    const int tid = threadIdx.x, S = a.c.nd | 1;
+    const int64_t n_tiles = chain_n_tiles(a.c);
     for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const int64_t b0 = t * a.rows;
-        const int rows = (int)((a.B - b0) < a.rows ? (a.B - b0) : a.rows);
-        tile_stage(a.x, b0, rows, nd, a.ta.magic, s_mem);
-        __syncthreads();
-        const bool active = tid < rows;
-        const int64_t b = b0 + (active ? tid : 0);
-        const uint64_t grow = (uint64_t)(a.row0 + b);
-        const uint32_t r_lo = (uint32_t)grow, r_hi = (uint32_t)(grow >> 32);
+        const ChainLane l = chain_tile_begin(a.c, t, s_mem);
+        const bool active = l.active;
+        const int64_t b = l.b;
         int cur = 0, acc = 0;
         float e_a = 0.0f, e_b = 0.0f;
         double W = 0.0;
         if (active) {
             e_a = a.e_valid ? a.e_a[b] : (float)bgk_row_energy<D, KIND_A>(s_mem + tid * S, a.ta);
             e_b = a.e_valid ? a.e_b[b] : (float)bgk_row_energy<D, KIND_B>(s_mem + tid * S, a.tb);
-            W = a.accumulate ? a.work[b] : 0.0;
+            W = a.c.accumulate ? a.work[b] : 0.0;
         }
         int m = a.step_begin / a.stage_steps + 1, in_stage = a.step_begin - (m - 1) * a.stage_steps;
         for (int s = a.step_begin; s < a.step_end; ++s) {
@@ -91,33 +75,13 @@ __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_anneal_kernel(AnArgs a)
                     const double w_a = d_a != 0.0 ? d_a * (double)e_a : 0.0, w_b = d_b != 0.0 ? d_b * (double)e_b : 0.0;
                     W += w_a + w_b;
                 }
-                const float* xc = s_mem + (cur ? a.tile_b : 0) + tid * S;
-                float* xp = s_mem + (cur ? 0 : a.tile_b) + tid * S;
-                float r;
-                if (a.noise) {
-                    const float* ns = a.noise + ((int64_t)s * a.B + b) * nd;
-                    for (int c = 0; c < nd; ++c) xp[c] = xc[c] + a.noise_std * ns[c];
-                    r = a.uniforms[(int64_t)s * a.B + b];
-                } else {
-                    const uint32_t off = a.offset + (uint32_t)s;
-                    uint32_t o[4];
-                    for (int cb = 0; 4 * cb < nd; ++cb) {
-                        philox4x32_10(r_lo, r_hi, (uint32_t)cb, off, a.seed_lo, a.seed_hi, o);
-                        float v[4];
-                        philox_normal4(o, v);
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const int c = 4 * cb + q;
-                            if (c < nd) xp[c] = xc[c] + a.noise_std * v[q];
-                        }
-                    }
-                    philox4x32_10(r_lo, r_hi, 1u << 20, off, a.seed_lo, a.seed_hi, o);
-                    r = u01(o[0]);
-                }
+                const float* xc = s_mem + (cur ? a.c.tile_b : 0) + tid * S;
+                float* xp = s_mem + (cur ? 0 : a.c.tile_b) + tid * S;
+                const float r = chain_draws(a.c, l, s, [&](int c, float v) { xp[c] = xc[c] + a.noise_std * v; });
                 const float p_a = (float)bgk_row_energy<D, KIND_A>(xp, a.ta);       /* at temperature 1: the calls of pair_energy_kernel */
                 const float p_b = (float)bgk_row_energy<D, KIND_B>(xp, a.tb);
                 const float u = an_reduced(c_a, c_b, e_a, e_b), up = an_reduced(c_a, c_b, p_a, p_b);
-                const bool accept = -(up - u) >= bgk_logf(r);                       /* false for a NaN on either side */
+                const bool accept = -(up - u) >= bgk_logf(r);
                 cur = accept ? cur ^ 1 : cur;
                 e_a = accept ? p_a : e_a;
                 e_b = accept ? p_b : e_b;
@@ -125,28 +89,18 @@ __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_anneal_kernel(AnArgs a)
             }
             if (++in_stage == a.stage_steps) { in_stage = 0; ++m; }
         }
-        s_sel[tid] = cur;
-        __syncthreads();
-        for (int i = tid; i < rows * nd; i += BGK_TILE_THREADS) {       /* tile_store of every row's CURRENT state */
-            const int r = (int)__umulhi((unsigned)i, a.ta.magic), c = i - r * nd;
-            a.x[b0 * nd + i] = s_mem[(s_sel[r] ? a.tile_b : 0) + r * S + c];
-        }
-        if (active) {
-            a.e_a[b] = e_a; a.e_b[b] = e_b; a.work[b] = W;
-            if (a.n_accepted) a.n_accepted[b] = a.accumulate ? a.n_accepted[b] + acc : acc;
-        }
-        __syncthreads();
+        chain_tile_end(a.c, l, cur, acc, s_sel, s_mem, [&] { a.e_a[b] = e_a; a.e_b[b] = e_b; a.work[b] = W; });
     }
 }
 
-/* one call of either entry: the two ends as the entry names them, then the entries' common arguments in order */
+/* one call of either entry: the two ends as the entry names them, then the entries' arguments: the chain kernels' common ones (no
+ * frames), the protocol's and the stream */
 struct BgkAnnealCall {
     BgkPairSpec a, b;
-    float* x; int64_t B;
+    ChainCall chain;
     const float* schedule; int32_t n_stages, stage_steps, step_begin, step_end;
-    double noise_std; const float* noise; const float* uniforms;
-    uint64_t seed; uint32_t offset; int64_t row0;
-    float* e_a; float* e_b; int32_t e_valid; double* work; int32_t* n_accepted; int32_t accumulate;
+    double noise_std;
+    float* e_a; float* e_b; int32_t e_valid; double* work;
     void* stream;
 };
 
@@ -165,7 +119,7 @@ void anneal_launch_b(int kind_b, int grid, size_t lds, hipStream_t s, const AnAr
 int anneal_run(const BgkAnnealCall& c) {
     const char* what = c.a.what;
     AnArgs a{};
-    BGK_CHECK_ARG(c.B >= 0 && c.row0 >= 0, "%s: bad batch size / row0", what);
+    BGK_CHECK_ARG(c.chain.B >= 0 && c.chain.row0 >= 0, "%s: bad batch size / row0", what);
     int st = bgk_pair_target(c.a, &a.ta);
     if (st) return st;
     st = bgk_pair_target(c.b, &a.tb);
@@ -176,24 +130,19 @@ int anneal_run(const BgkAnnealCall& c) {
     BGK_CHECK_ARG(c.step_begin >= 0 && c.step_begin <= c.step_end && c.step_end <= c.n_stages * c.stage_steps,
                   "%s: steps [%d, %d) of %d", what, c.step_begin, c.step_end, c.n_stages * c.stage_steps);
     BGK_CHECK_ARG(c.noise_std >= 0.0, "%s: noise_std must not be negative", what);
-    BGK_CHECK_ARG((c.noise != nullptr) == (c.uniforms != nullptr), "%s: noise and uniforms go together", what);
-    if (c.B == 0 || c.step_begin == c.step_end) return 0;
-    BGK_CHECK_ARG(c.x && c.e_a && c.e_b && c.work && c.schedule, "%s: null tensor", what);
-    const int S = a.ta.nd | 1;
-    int rows = rows_within(AN_LDS_DYNAMIC, 2 * S * (int)sizeof(float));
-    while ((((rows * S + 31) & ~31) + rows * S) * (int)sizeof(float) > AN_LDS_DYNAMIC) --rows;     /* the second tile starts at round32 */
-    a.x = c.x; a.B = c.B; a.row0 = c.row0;
-    a.rows = rows; a.tile_b = (rows * S + 31) & ~31;
+    st = chain_check(what, c.chain, true);              /* the temperatures are in the schedule */
+    if (st) return st;
+    if (c.chain.B == 0 || c.step_begin == c.step_end) return 0;
+    BGK_CHECK_ARG(c.chain.x && c.e_a && c.e_b && c.work && c.schedule, "%s: null tensor", what);
+    const ChainLayout lay = chain_layout(c.chain.B, a.ta.nd, 1, 1);
+    a.c = chain_args(c.chain, a.ta.nd, a.ta.magic, lay);
     a.schedule = c.schedule; a.stage_steps = c.stage_steps; a.step_begin = c.step_begin; a.step_end = c.step_end;
-    a.noise_std = (float)c.noise_std; a.noise = c.noise; a.uniforms = c.uniforms;
-    a.seed_lo = (uint32_t)c.seed; a.seed_hi = (uint32_t)(c.seed >> 32); a.offset = c.offset;
+    a.noise_std = (float)c.noise_std;
     a.e_a = c.e_a; a.e_b = c.e_b; a.e_valid = c.e_valid != 0;
-    a.work = c.work; a.n_accepted = c.n_accepted; a.accumulate = c.accumulate != 0;
-    const size_t lds = (size_t)(a.tile_b + rows * S) * sizeof(float);
-    const int grid = tile_grid(c.B, rows);
+    a.work = c.work;
     hipStream_t s = (hipStream_t)c.stream;
     const int kind_b = c.b.kind;
-    tile_dispatch<true>(c.a.kind, c.a.n_dims, [&](auto D, auto K) { anneal_launch_b<D(), K()>(kind_b, grid, lds, s, a); });
+    tile_dispatch<true>(c.a.kind, c.a.n_dims, [&](auto D, auto K) { anneal_launch_b<D(), K()>(kind_b, lay.grid, lay.lds, s, a); });
     return bgk_launch_status(what);
 }
 
@@ -207,9 +156,9 @@ extern "C" int bgk_pair_anneal(float* x, int64_t B, int32_t n_particles, int32_t
                                uint64_t seed, uint32_t offset, int64_t row0,
                                float* e_a, float* e_b, int32_t e_valid, double* work, int32_t* n_accepted, int32_t accumulate, void* stream) {
     return anneal_run({bgk_pair_spec("bgk_pair_anneal", n_particles, n_dims, kind_a, a0, a1, a2, a3, osc_scale_a),
-                       bgk_pair_spec("bgk_pair_anneal", n_particles, n_dims, kind_b, b0, b1, b2, b3, osc_scale_b), x, B,
-                       schedule, n_stages, n_steps, step_begin, step_end, noise_std, noise, uniforms, seed, offset, row0,
-                       e_a, e_b, e_valid, work, n_accepted, accumulate, stream});
+                       bgk_pair_spec("bgk_pair_anneal", n_particles, n_dims, kind_b, b0, b1, b2, b3, osc_scale_b),
+                       {x, B, noise, uniforms, seed, offset, row0, nullptr, nullptr, 0, n_accepted, accumulate},
+                       schedule, n_stages, n_steps, step_begin, step_end, noise_std, e_a, e_b, e_valid, work, stream});
 }
 
 /* the particle box (kinds 3 / 4 of bgk_pair_terms.h) at both ends, each with its own parameter array; two dimensions */
@@ -221,7 +170,7 @@ extern "C" int bgk_box_anneal(float* x, int64_t B, int32_t n_particles,
                               uint64_t seed, uint32_t offset, int64_t row0,
                               float* e_a, float* e_b, int32_t e_valid, double* work, int32_t* n_accepted, int32_t accumulate, void* stream) {
     return anneal_run({bgk_box_spec("bgk_box_anneal", n_particles, kind_a, params_a, n_params_a),
-                       bgk_box_spec("bgk_box_anneal", n_particles, kind_b, params_b, n_params_b), x, B,
-                       schedule, n_stages, n_steps, step_begin, step_end, noise_std, noise, uniforms, seed, offset, row0,
-                       e_a, e_b, e_valid, work, n_accepted, accumulate, stream});
+                       bgk_box_spec("bgk_box_anneal", n_particles, kind_b, params_b, n_params_b),
+                       {x, B, noise, uniforms, seed, offset, row0, nullptr, nullptr, 0, n_accepted, accumulate},
+                       schedule, n_stages, n_steps, step_begin, step_end, noise_std, e_a, e_b, e_valid, work, stream});
 }

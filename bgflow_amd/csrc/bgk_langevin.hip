@@ -78,19 +78,6 @@ struct LgArgs {
     float* traj_q; float* traj_v;                      /* RECORD: the state after every step [n_steps, B, n d] */
 };
 
-/* the four normals of columns 4 cb .. 4 cb + 3 of a field: the explicit row (columns beyond n d: 0) or the Philox block */
-__device__ __forceinline__ void lg_normal4(const float* row, int nd, int cb, uint32_t r_lo, uint32_t r_hi, uint32_t field, uint32_t off,
-                                           uint32_t k0, uint32_t k1, float (&w)[4]) {
-    if (row) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = 4 * cb + j < nd ? row[4 * cb + j] : 0.0f;
-    } else {
-        uint32_t o[4];
-        philox4x32_10(r_lo, r_hi, (field << 20) | (uint32_t)cb, off, k0, k1, o);
-        philox_normal4(o, w);
-    }
-}
-
 template <int D, int KIND, bool LANGEVIN, bool RECORD>
 __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_langevin_kernel(LgArgs a) {
     extern __shared__ float s_mem[];
@@ -127,7 +114,7 @@ __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_langevin_kernel(LgArgs 
                     float* xb = s_mem + oy + tid * S;
                     for (int cb = 0; 4 * cb < nd; ++cb) {
                         float w[4];
-                        lg_normal4(n1, nd, cb, r_lo, r_hi, 0u, off, a.seed_lo, a.seed_hi, w);
+                        philox_field_normal4(n1, nd, cb, r_lo, r_hi, 0u, off, a.seed_lo, a.seed_hi, w);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             const int c = 4 * cb + j;
@@ -149,7 +136,7 @@ __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_langevin_kernel(LgArgs 
                     float* tr = s_mem + 4 * T + tid * S;
                     for (int cb = 0; 4 * cb < nd; ++cb) {
                         float w[4];
-                        lg_normal4(n1, nd, cb, r_lo, r_hi, 0u, off, a.seed_lo, a.seed_hi, w);
+                        philox_field_normal4(n1, nd, cb, r_lo, r_hi, 0u, off, a.seed_lo, a.seed_hi, w);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             const int c = 4 * cb + j;
@@ -164,7 +151,7 @@ __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_langevin_kernel(LgArgs 
                     bgk_pair_row_gradient<D, KIND>(qr, gg, a.t);
                     for (int cb = 0; 4 * cb < nd; ++cb) {
                         float w[4];
-                        lg_normal4(n2, nd, cb, r_lo, r_hi, 1u, off, a.seed_lo, a.seed_hi, w);
+                        philox_field_normal4(n2, nd, cb, r_lo, r_hi, 1u, off, a.seed_lo, a.seed_hi, w);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             const int c = 4 * cb + j;
@@ -274,7 +261,7 @@ __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_langevin_bwd_kernel(LbA
                     if (j > 0) {
                         for (int cb = 0; 4 * cb < nd; ++cb) {
                             float w[4];
-                            lg_normal4(n2, nd, cb, r_lo, r_hi, 1u, off, a.seed_lo, a.seed_hi, w);
+                            philox_field_normal4(n2, nd, cb, r_lo, r_hi, 1u, off, a.seed_lo, a.seed_hi, w);
 #pragma unroll
                             for (int k = 0; k < 4; ++k) {
                                 const int c = 4 * cb + k;
@@ -298,7 +285,7 @@ __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_langevin_bwd_kernel(LbA
                 if (active) {
                     for (int cb = 0; 4 * cb < nd; ++cb) {
                         float w[4];
-                        lg_normal4(n1, nd, cb, r_lo, r_hi, 0u, off, a.seed_lo, a.seed_hi, w);
+                        philox_field_normal4(n1, nd, cb, r_lo, r_hi, 0u, off, a.seed_lo, a.seed_hi, w);
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
                             const int c = 4 * cb + k;

@@ -6,24 +6,13 @@
  *   launches (randn_like, add, the energy's op chain, rand_like, log, min, compare, two where) over a state of n d <= 192 floats per chain;
  *   here the state of a chain never leaves LDS between recorded frames.
  *
- * By the rules of bgk_pair_tile.h: one wave per workgroup, ONE LANE PER CHAIN, a tile of rows staged coalesced through LDS at the odd
- * row stride S.  Two LDS tiles, A and B: a lane's current row is in one, its proposal is written into the other, and accepting is a
- * per-lane flip of which is which -- no copy.  B starts a
- * multiple of 32 words behind A, so lanes whose current rows sit in different tiles still hit distinct banks.  The steps run in lockstep
- * across the wave (the accept flag only selects); a recorded frame leaves as one coalesced tile store through a per-row tile flag in LDS.
+ * A chain kernel by the rules of bgk_chain.h (sides, banks, budget, numbers, accept, carried, frames), with 1 + 1 tiles: a lane's current
+ * row is in one, its proposal is written into the other.
  *
  * Energy: bgk_row_energy of bgk_pair_terms.h -- the call of pair_energy_kernel, so e is, bit for bit, what bgk_pair_energy returns for
- * the row at temperature 1.  min(0, .) is dropped: log r < 0, so v >= log r and min(0, v) >= log r decide alike.  A proposal whose energy
- * is NaN or +inf is rejected by the comparison itself, as in the reference.
+ * the row at temperature 1.
  *
- * Random numbers: explicit (noise [n_steps, B, n d] and uniforms [n_steps, B], read by the chain's lane) or drawn in the kernel from
- * Philox4x32-10 in the counter layout of bgk_philox.hip (bgk_philox.h): counter = (global chain low, high, field << 20 | 4-column block,
- * offset + step), field 0 = the n d normals (Box-Muller), field 1 / block 0 / word 0 = the uniform.  The stream is a pure function of
- * (seed, step, global chain, column): the same bits whatever the tiling, the grid, row0 sharding or the split of a run into launches, and
- * the bits bgk_philox_fields writes for (seed, offset + step) with fields [normal n d, uniform 1].
- *
- * Envelope: bgk_pair_tile.h.  Dynamic LDS <= 63,488 B: rows per tile = the most (<= 64) with (round32(rows S) + rows S) 4 B within
- * it; lanes beyond the rows only stage and store:
+ * Tile heights (rows, dynamic LDS):
  *   n d = 192 (S = 193): 41 rows, 63,396 B       LJ13 (S = 39): 64 rows, 19,968 B       DW4 (S = 9): 64 rows, 4,608 B
  *   the particle box of 38 particles (S = 77): 64 rows, 39,424 B       of 64 particles (S = 129): 61 rows, 62,964 B
  *
@@ -32,50 +21,27 @@
  * b % K of ladder b / K -- and a tile holds whole ladders (rows = the plain kernel's rounded down to a multiple of K), so a ladder is K
  * neighbouring lanes.  After the Metropolis part of every exchange_every-th step the pairs of slots (k, k + 1), k = parity (mod 2), try
  *   c = -(e[k+1] - e[k]) (1 / T[k+1] - 1 / T[k]),  exchange iff -log r > c   (f32; false for a NaN on either side),
- * r the number of the pair's LOWER slot: row j of exchange_uniforms for the j-th exchange of the launch, or Philox field 2 -- counter
- * (global chain, 2 << 20, offset + step), word 0 -- next to fields 0 and 1 above.  The parity flips after every attempt.  An exchange moves
+ * r the number of the pair's LOWER slot: row j of exchange_uniforms for the j-th exchange of the launch, or Philox field 2 at the step's
+ * offset.  The parity flips after every attempt.  An exchange moves
  * no data: the lane keeps `row`, the LDS row that holds its state (both tiles), next to `cur`, and two lanes swap (row, cur, e, walker) by
  * wave shuffles; the rows of a tile stay a permutation of its rows, so the banks stay distinct.  Temperatures, n_accepted and n_exchanged
  * (counted at the lower slot) belong to the slot.  The exchange condition is uniform over the wave and every lane executes the shuffles.
  * A frame due at the same step is recorded BEFORE the exchange.  Tile heights: floor(rows / K) K, e.g. K = 5: 40 rows at n d = 192. */
-#include "bgk_common.h"
+#include "bgk_chain.h"
 #include "bgk_pair_terms.h"
-#include "bgk_philox.h"
 
 namespace {
 
-constexpr int MC_LDS_DYNAMIC = 63488;
-
 struct McArgs {
-    float* x; int64_t B, row0;
-    BgkPairTarget t; int rows, tile_b;                  /* tile_b: word offset of the second tile, a multiple of 32 */
+    ChainArgs c;
+    BgkPairTarget t;
     float* e; int e_valid;
     float temperature; const float* temperatures;
     float noise_std; int n_steps;
-    const float* noise; const float* uniforms;
-    uint32_t seed_lo, seed_hi, offset;
-    float* traj; float* traj_e; int traj_every;
-    int* n_accepted; int accumulate;
     /* replica exchange (EXCHANGE kernels only) */
     int n_replicas, ex_every, ex_phase, ex_parity;
     const float* ex_uniforms; int* n_exchanged; int* walkers;
 };
-
-/* tile_store of every row's CURRENT state: s_sel[r] says which of the two tiles holds it (EXCHANGE: bit 0, and the bits above which
- * LDS row holds slot r's state); dst: the tile's first row in contiguous rows */
-template <bool EXCHANGE>
-__device__ __forceinline__ void mc_store_current(const McArgs& a, float* dst, int rows, const int* s_sel, const float* s_mem) {
-    const int nd = a.t.nd, S = nd | 1;
-    for (int i = threadIdx.x; i < rows * nd; i += BGK_TILE_THREADS) {
-        const int r = (int)__umulhi((unsigned)i, a.t.magic), c = i - r * nd;
-        if constexpr (EXCHANGE) {
-            const int sel = s_sel[r];
-            dst[i] = s_mem[((sel & 1) ? a.tile_b : 0) + (sel >> 1) * S + c];
-        } else {
-            dst[i] = s_mem[(s_sel[r] ? a.tile_b : 0) + r * S + c];
-        }
-    }
-}
 
 /* v of this lane after the exchanges of a step: the upper neighbour's if this lane exchanges upwards, the lower one's if downwards */
 template <class T>
@@ -88,17 +54,12 @@ template <int D, int KIND, bool EXCHANGE>
 __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_mcmc_kernel(McArgs a) {
     extern __shared__ float s_mem[];
     __shared__ int s_sel[BGK_TILE_THREADS];             /* which tile holds row r's current state */
-    const int tid = threadIdx.x, nd = a.t.nd, S = nd | 1;
-    const int64_t n_tiles = (a.B + a.rows - 1) / a.rows;
+    const int tid = threadIdx.x, S = a.c.nd | 1;
+    const int64_t n_tiles = chain_n_tiles(a.c);
     for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const int64_t b0 = t * a.rows;
-        const int rows = (int)((a.B - b0) < a.rows ? (a.B - b0) : a.rows);
-        tile_stage(a.x, b0, rows, nd, a.t.magic, s_mem);
-        __syncthreads();
-        const bool active = tid < rows;
-        const int64_t b = b0 + (active ? tid : 0);
-        const uint64_t grow = (uint64_t)(a.row0 + b);
-        const uint32_t r_lo = (uint32_t)grow, r_hi = (uint32_t)(grow >> 32);
+        ChainLane l = chain_tile_begin(a.c, t, s_mem);
+        const bool active = l.active;
+        const int64_t b = l.b;
         int cur = 0, acc = 0;
         float e = 0.0f, temp = 1.0f;
         if (active) {
@@ -116,48 +77,19 @@ __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_mcmc_kernel(McArgs a) {
             d_beta = __shfl_down(beta, 1) - beta;
             ex_since = a.ex_phase; parity = a.ex_parity;
         }
-        int frame = 0, since = 0;
         for (int step = 0; step < a.n_steps; ++step) {
             if (active) {
                 const int lrow = EXCHANGE ? row : tid;
-                const float* xc = s_mem + (cur ? a.tile_b : 0) + lrow * S;
-                float* xp = s_mem + (cur ? 0 : a.tile_b) + lrow * S;
-                float r;
-                if (a.noise) {
-                    const float* ns = a.noise + ((int64_t)step * a.B + b) * nd;
-                    for (int c = 0; c < nd; ++c) xp[c] = xc[c] + a.noise_std * ns[c];
-                    r = a.uniforms[(int64_t)step * a.B + b];
-                } else {
-                    const uint32_t off = a.offset + (uint32_t)step;
-                    uint32_t o[4];
-                    for (int cb = 0; 4 * cb < nd; ++cb) {
-                        philox4x32_10(r_lo, r_hi, (uint32_t)cb, off, a.seed_lo, a.seed_hi, o);
-                        float v[4];
-                        philox_normal4(o, v);
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const int c = 4 * cb + q;
-                            if (c < nd) xp[c] = xc[c] + a.noise_std * v[q];
-                        }
-                    }
-                    philox4x32_10(r_lo, r_hi, 1u << 20, off, a.seed_lo, a.seed_hi, o);
-                    r = u01(o[0]);
-                }
+                const float* xc = s_mem + (cur ? a.c.tile_b : 0) + lrow * S;
+                float* xp = s_mem + (cur ? 0 : a.c.tile_b) + lrow * S;
+                const float r = chain_draws(a.c, l, step, [&](int c, float v) { xp[c] = xc[c] + a.noise_std * v; });
                 const float ep = (float)bgk_row_energy<D, KIND>(xp, a.t);      /* at temperature 1: the call of pair_energy_kernel */
-                const bool accept = -(ep - e) / temp >= bgk_logf(r);      /* false for a NaN on either side */
+                const bool accept = -(ep - e) / temp >= bgk_logf(r);
                 cur = accept ? cur ^ 1 : cur;
                 e = accept ? ep : e;
                 acc += accept ? 1 : 0;
             }
-            if (a.traj && ++since == a.traj_every) {    /* uniform over the wave */
-                since = 0;
-                s_sel[tid] = EXCHANGE ? (cur | (row << 1)) : cur;
-                __syncthreads();
-                mc_store_current<EXCHANGE>(a, a.traj + ((int64_t)frame * a.B + b0) * nd, rows, s_sel, s_mem);
-                if (active && a.traj_e) a.traj_e[(int64_t)frame * a.B + b] = e;
-                ++frame;
-                __syncthreads();                        /* the next proposals overwrite rows this store reads */
-            }
+            chain_record<EXCHANGE>(a.c, l, EXCHANGE ? (cur | (row << 1)) : cur, e, s_sel, s_mem);
             if constexpr (EXCHANGE) {
                 if (++ex_since == a.ex_every) {         /* uniform over the wave; every lane runs the shuffles */
                     ex_since = 0;
@@ -165,14 +97,8 @@ __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_mcmc_kernel(McArgs a) {
                     const float e_up = __shfl_down(e, 1);
                     bool up = false;
                     if (lower) {
-                        float r;
-                        if (a.noise) {
-                            r = a.ex_uniforms[(int64_t)n_ex * a.B + b];
-                        } else {
-                            uint32_t o[4];
-                            philox4x32_10(r_lo, r_hi, 2u << 20, a.offset + (uint32_t)step, a.seed_lo, a.seed_hi, o);
-                            r = u01(o[0]);
-                        }
+                        const float r = philox_field_uniform(a.c.noise ? a.ex_uniforms + ((int64_t)n_ex * a.c.B + b) : nullptr, l.r_lo, l.r_hi,
+                                                             2u, a.c.offset + (uint32_t)step, a.c.seed_lo, a.c.seed_hi);
                         const float c = -(e_up - e) * d_beta;
                         up = -bgk_logf(r) > c;          /* false for a NaN on either side */
                     }
@@ -192,29 +118,23 @@ __global__ __launch_bounds__(BGK_TILE_THREADS) void pair_mcmc_kernel(McArgs a) {
                 }
             }
         }
-        s_sel[tid] = EXCHANGE ? (cur | (row << 1)) : cur;
-        __syncthreads();
-        mc_store_current<EXCHANGE>(a, a.x + b0 * nd, rows, s_sel, s_mem);
-        if (active) {
+        chain_tile_end<EXCHANGE>(a.c, l, EXCHANGE ? (cur | (row << 1)) : cur, acc, s_sel, s_mem, [&] {
             a.e[b] = e;
-            if (a.n_accepted) a.n_accepted[b] = a.accumulate ? a.n_accepted[b] + acc : acc;
             if constexpr (EXCHANGE) {
-                if (a.n_exchanged) a.n_exchanged[b] = a.accumulate ? a.n_exchanged[b] + exch : exch;
+                if (a.n_exchanged) a.n_exchanged[b] = a.c.accumulate ? a.n_exchanged[b] + exch : exch;
                 if (a.walkers) a.walkers[b] = walker;
             }
-        }
-        __syncthreads();
+        });
     }
 }
 
-/* one call of either entry: the target as the entry names it (bgk_pair_spec / bgk_box_spec), then the entries' common arguments in order */
+/* one call of either entry: the target as the entry names it (bgk_pair_spec / bgk_box_spec), then the entries' arguments: the chain
+ * kernels' common ones, the Metropolis step's and the stream */
 struct BgkMcmcCall {
     BgkPairSpec spec;
-    float* x; int64_t B;
+    ChainCall chain;
     float* e; int32_t e_valid; double temperature; const float* temperatures;
-    double noise_std; int32_t n_steps; const float* noise; const float* uniforms;
-    uint64_t seed; uint32_t offset; int64_t row0;
-    float* traj; float* traj_e; int32_t traj_every; int32_t* n_accepted; int32_t accumulate;
+    double noise_std; int32_t n_steps;
     void* stream;
     /* replica exchange (the *_remc entries; n_replicas = 0: the plain kernel) */
     int32_t n_replicas, exchange_every, exchange_phase, exchange_parity;
@@ -224,53 +144,44 @@ struct BgkMcmcCall {
 int mcmc_run(const BgkMcmcCall& c) {
     const char* what = c.spec.what;
     McArgs a{};
-    BGK_CHECK_ARG(c.B >= 0 && c.row0 >= 0 && c.n_steps >= 0, "%s: bad batch size / row0 / n_steps", what);
-    const int st = bgk_pair_target(c.spec, &a.t);
+    int st = chain_check_batch(what, c.chain, c.n_steps);
+    if (!st) st = bgk_pair_target(c.spec, &a.t);
+    if (!st) st = chain_check(what, c.chain, c.temperatures || c.temperature > 0.0);
     if (st) return st;
-    BGK_CHECK_ARG(c.temperatures || c.temperature > 0.0, "%s: the temperature must be positive", what);
     BGK_CHECK_ARG(c.noise_std >= 0.0, "%s: noise_std must not be negative", what);
-    BGK_CHECK_ARG((c.noise != nullptr) == (c.uniforms != nullptr), "%s: noise and uniforms go together", what);
-    BGK_CHECK_ARG(!c.traj_e || c.traj, "%s: traj_e without traj", what);
-    BGK_CHECK_ARG(!c.traj || c.traj_every >= 1, "%s: traj_every %d", what, c.traj_every);
     const bool exchange = c.n_replicas != 0;
     if (exchange) {
         BGK_CHECK_ARG(c.n_replicas >= 2, "%s: n_replicas %d (at least 2)", what, c.n_replicas);
         BGK_CHECK_ARG(c.exchange_every >= 1 && c.exchange_phase >= 0 && c.exchange_phase < c.exchange_every,
                       "%s: exchange_every %d / exchange_phase %d (0 <= phase < every)", what, c.exchange_every, c.exchange_phase);
         BGK_CHECK_ARG(c.exchange_parity == 0 || c.exchange_parity == 1, "%s: exchange_parity %d", what, c.exchange_parity);
-        BGK_CHECK_ARG(c.B % c.n_replicas == 0 && c.row0 % c.n_replicas == 0, "%s: the batch size and row0 must be multiples of n_replicas", what);
+        BGK_CHECK_ARG(c.chain.B % c.n_replicas == 0 && c.chain.row0 % c.n_replicas == 0,
+                      "%s: the batch size and row0 must be multiples of n_replicas", what);
         const int64_t n_exchanges = ((int64_t)c.exchange_phase + c.n_steps) / c.exchange_every;
-        BGK_CHECK_ARG(n_exchanges == 0 || (c.noise != nullptr) == (c.exchange_uniforms != nullptr),
+        BGK_CHECK_ARG(n_exchanges == 0 || (c.chain.noise != nullptr) == (c.exchange_uniforms != nullptr),
                       "%s: noise, uniforms and exchange_uniforms go together", what);
     }
-    const int S = a.t.nd | 1;
-    int rows = rows_within(MC_LDS_DYNAMIC, 2 * S * (int)sizeof(float));
-    while ((((rows * S + 31) & ~31) + rows * S) * (int)sizeof(float) > MC_LDS_DYNAMIC) --rows;     /* the second tile starts at round32 */
+    ChainLayout lay = chain_layout(c.chain.B, a.t.nd, 1, 1);
     if (exchange) {                                         /* the envelope of K, whatever the batch (an empty one included) */
-        if (c.n_replicas > rows) {
-            bgk_set_error("%s: %d replicas are more than the %d rows of a tile of this target", what, c.n_replicas, rows);
+        if (c.n_replicas > lay.rows) {
+            bgk_set_error("%s: %d replicas are more than the %d rows of a tile of this target", what, c.n_replicas, lay.rows);
             return BGK_EUNSUPPORTED;
         }
-        rows = rows / c.n_replicas * c.n_replicas;          /* a tile holds whole ladders */
+        lay = chain_layout(c.chain.B, a.t.nd, 1, 1, lay.rows / c.n_replicas * c.n_replicas);      /* a tile holds whole ladders */
     }
-    if (c.B == 0) return 0;
-    BGK_CHECK_ARG(c.x && c.e, "%s: null tensor", what);
+    if (c.chain.B == 0) return 0;
+    BGK_CHECK_ARG(c.chain.x && c.e, "%s: null tensor", what);
     BGK_CHECK_ARG(!exchange || c.temperatures, "%s: replica exchange needs temperatures [B]", what);
-    a.x = c.x; a.B = c.B; a.row0 = c.row0;
-    a.rows = rows; a.tile_b = (rows * S + 31) & ~31;
+    a.c = chain_args(c.chain, a.t.nd, a.t.magic, lay);
     a.e = c.e; a.e_valid = c.e_valid != 0; a.temperature = (float)c.temperature; a.temperatures = c.temperatures;
-    a.noise_std = (float)c.noise_std; a.n_steps = c.n_steps; a.noise = c.noise; a.uniforms = c.uniforms;
-    a.seed_lo = (uint32_t)c.seed; a.seed_hi = (uint32_t)(c.seed >> 32); a.offset = c.offset;
-    a.traj = c.traj; a.traj_e = c.traj_e; a.traj_every = c.traj_every; a.n_accepted = c.n_accepted; a.accumulate = c.accumulate != 0;
-    const size_t lds = (size_t)(a.tile_b + rows * S) * sizeof(float);
-    const int grid = tile_grid(c.B, rows);
+    a.noise_std = (float)c.noise_std; a.n_steps = c.n_steps;
     hipStream_t s = (hipStream_t)c.stream;
     if (exchange) {
         a.n_replicas = c.n_replicas; a.ex_every = c.exchange_every; a.ex_phase = c.exchange_phase; a.ex_parity = c.exchange_parity;
         a.ex_uniforms = c.exchange_uniforms; a.n_exchanged = c.n_exchanged; a.walkers = c.walkers;
-        tile_dispatch<true>(c.spec.kind, c.spec.n_dims, [&](auto D, auto K) { tile_launch(pair_mcmc_kernel<D(), K(), true>, grid, lds, s, a); });
+        tile_dispatch<true>(c.spec.kind, c.spec.n_dims, [&](auto D, auto K) { tile_launch(pair_mcmc_kernel<D(), K(), true>, lay.grid, lay.lds, s, a); });
     } else {
-        tile_dispatch<true>(c.spec.kind, c.spec.n_dims, [&](auto D, auto K) { tile_launch(pair_mcmc_kernel<D(), K(), false>, grid, lds, s, a); });
+        tile_dispatch<true>(c.spec.kind, c.spec.n_dims, [&](auto D, auto K) { tile_launch(pair_mcmc_kernel<D(), K(), false>, lay.grid, lay.lds, s, a); });
     }
     return bgk_launch_status(what);
 }
@@ -283,9 +194,9 @@ extern "C" int bgk_pair_mcmc(float* x, int64_t B, int32_t n_particles, int32_t n
                              double noise_std, int32_t n_steps, const float* noise, const float* uniforms,
                              uint64_t seed, uint32_t offset, int64_t row0,
                              float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream) {
-    return mcmc_run({bgk_pair_spec("bgk_pair_mcmc", n_particles, n_dims, kind, p0, p1, p2, p3, osc_scale), x, B,
-                     e, e_valid, temperature, temperatures, noise_std, n_steps, noise, uniforms, seed, offset, row0,
-                     traj, traj_e, traj_every, n_accepted, accumulate, stream});
+    return mcmc_run({bgk_pair_spec("bgk_pair_mcmc", n_particles, n_dims, kind, p0, p1, p2, p3, osc_scale),
+                     {x, B, noise, uniforms, seed, offset, row0, traj, traj_e, traj_every, n_accepted, accumulate},
+                     e, e_valid, temperature, temperatures, noise_std, n_steps, stream});
 }
 
 /* the particle box (kinds 3 / 4 of bgk_pair_terms.h) in the same chain kernel: MCMCStep._step (mcmc.py:86-122) over
@@ -295,9 +206,9 @@ extern "C" int bgk_box_mcmc(float* x, int64_t B, int32_t n_particles, int32_t ki
                             double noise_std, int32_t n_steps, const float* noise, const float* uniforms,
                             uint64_t seed, uint32_t offset, int64_t row0,
                             float* traj, float* traj_e, int32_t traj_every, int32_t* n_accepted, int32_t accumulate, void* stream) {
-    return mcmc_run({bgk_box_spec("bgk_box_mcmc", n_particles, kind, params, n_params), x, B,
-                     e, e_valid, temperature, temperatures, noise_std, n_steps, noise, uniforms, seed, offset, row0,
-                     traj, traj_e, traj_every, n_accepted, accumulate, stream});
+    return mcmc_run({bgk_box_spec("bgk_box_mcmc", n_particles, kind, params, n_params),
+                     {x, B, noise, uniforms, seed, offset, row0, traj, traj_e, traj_every, n_accepted, accumulate},
+                     e, e_valid, temperature, temperatures, noise_std, n_steps, stream});
 }
 
 /* replica exchange inside the chain kernel (the head comment's last part): the arguments of the *_mcmc entry, then the exchange's */
@@ -310,9 +221,9 @@ extern "C" int bgk_pair_remc(float* x, int64_t B, int32_t n_particles, int32_t n
                              int32_t n_replicas, int32_t exchange_every, int32_t exchange_phase, int32_t exchange_parity,
                              const float* exchange_uniforms, int32_t* n_exchanged, int32_t* walkers) {
     if (n_replicas == 0) n_replicas = -1;               /* 0 means "the plain kernel" inside mcmc_run: refused here like any K < 2 */
-    return mcmc_run({bgk_pair_spec("bgk_pair_remc", n_particles, n_dims, kind, p0, p1, p2, p3, osc_scale), x, B,
-                     e, e_valid, temperature, temperatures, noise_std, n_steps, noise, uniforms, seed, offset, row0,
-                     traj, traj_e, traj_every, n_accepted, accumulate, stream,
+    return mcmc_run({bgk_pair_spec("bgk_pair_remc", n_particles, n_dims, kind, p0, p1, p2, p3, osc_scale),
+                     {x, B, noise, uniforms, seed, offset, row0, traj, traj_e, traj_every, n_accepted, accumulate},
+                     e, e_valid, temperature, temperatures, noise_std, n_steps, stream,
                      n_replicas, exchange_every, exchange_phase, exchange_parity, exchange_uniforms, n_exchanged, walkers});
 }
 
@@ -324,8 +235,8 @@ extern "C" int bgk_box_remc(float* x, int64_t B, int32_t n_particles, int32_t ki
                             int32_t n_replicas, int32_t exchange_every, int32_t exchange_phase, int32_t exchange_parity,
                             const float* exchange_uniforms, int32_t* n_exchanged, int32_t* walkers) {
     if (n_replicas == 0) n_replicas = -1;
-    return mcmc_run({bgk_box_spec("bgk_box_remc", n_particles, kind, params, n_params), x, B,
-                     e, e_valid, temperature, temperatures, noise_std, n_steps, noise, uniforms, seed, offset, row0,
-                     traj, traj_e, traj_every, n_accepted, accumulate, stream,
+    return mcmc_run({bgk_box_spec("bgk_box_remc", n_particles, kind, params, n_params),
+                     {x, B, noise, uniforms, seed, offset, row0, traj, traj_e, traj_every, n_accepted, accumulate},
+                     e, e_valid, temperature, temperatures, noise_std, n_steps, stream,
                      n_replicas, exchange_every, exchange_phase, exchange_parity, exchange_uniforms, n_exchanged, walkers});
 }

@@ -1,4 +1,4 @@
-/* bgk_pair_tile.h -- what the particle-system kernels share: bgk_pair.hip (energy / backward / hvp), bgk_mcmc.hip (Metropolis chains),
+/* bgk_pair_tile.h -- what the particle-system kernels share: bgk_pair.hip (energy / backward / hvp), the chain kernels of bgk_chain.h (bgk_mcmc.hip, bgk_hmc.hip, bgk_anneal.hip),
  * bgk_langevin.hip (Brownian / Langevin forward, record, adjoint) and bgk_kdyn.hip (kernel dynamics).  The formulas of the targets are in
  * bgk_pair_terms.h; here are the target's parameter record, the walk over tiles of rows and the choice of a kernel instantiation.
  *

@@ -34,4 +34,26 @@ __device__ __forceinline__ void philox_normal4(const uint32_t (&o)[4], float (&v
     }
 }
 
+/* the four normals of columns 4 cb .. 4 cb + 3 of a field: the explicit row (columns beyond n d: 0) or the Philox block */
+__device__ __forceinline__ void philox_field_normal4(const float* row, int nd, int cb, uint32_t r_lo, uint32_t r_hi, uint32_t field,
+                                                     uint32_t off, uint32_t k0, uint32_t k1, float (&w)[4]) {
+    if (row) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = 4 * cb + j < nd ? row[4 * cb + j] : 0.0f;
+    } else {
+        uint32_t o[4];
+        philox4x32_10(r_lo, r_hi, (field << 20) | (uint32_t)cb, off, k0, k1, o);
+        philox_normal4(o, w);
+    }
+}
+
+/* the one uniform of a field: the explicit number, or word 0 of the field's block 0 */
+__device__ __forceinline__ float philox_field_uniform(const float* given, uint32_t r_lo, uint32_t r_hi, uint32_t field, uint32_t off,
+                                                      uint32_t k0, uint32_t k1) {
+    if (given) return *given;
+    uint32_t o[4];
+    philox4x32_10(r_lo, r_hi, field << 20, off, k0, k1, o);
+    return u01(o[0]);
+}
+
 #endif

@@ -171,6 +171,21 @@ class SamplerState(AbstractSamplerState):
 
 
 # ---- the kernel launch ------------------------------------------------------------------------------------------------------------
+def _chain_launch_checks(fn, plan, x, temperature, noise, uniforms, n_rows, n_accepted, tensors=(), noun="target"):
+    """What ``pair_mcmc``, ``pair_hmc`` and ``annealing.pair_anneal`` check first: the columns of x [B, n d] against the plan, noise with
+    uniforms (``n_rows`` rows each), and the tensors every chain launch has next to the caller's f32 ``tensors``, (tensor or None, shape)
+    pairs.  Returns the tensor [B] of temperatures, or None for a number."""
+    B, nd = x.shape
+    if nd != plan.n_particles * plan.n_dims:
+        raise ValueError(f"{fn}: x has {nd} columns, the {noun} {plan.n_particles} x {plan.n_dims}")
+    if (noise is None) != (uniforms is None):
+        raise ValueError(f"{fn}: noise and uniforms go together")
+    temps = temperature if torch.is_tensor(temperature) else None
+    _check_tensors(fn, x, [(x, (B, nd)), (temps, (B,)), (noise, (n_rows, B, nd)), (uniforms, (n_rows, B)), *tensors])
+    _check_tensors(fn, x, [(n_accepted, (B,))], dtype=torch.int32)
+    return temps
+
+
 def pair_mcmc(plan, x, e, e_valid, temperature, noise_std, n_steps, noise=None, uniforms=None, seed=0, offset=0, row0=0,
               traj=None, traj_e=None, traj_every=0, n_accepted=None, accumulate=False, n_replicas=0, exchange_every=1,
               exchange_phase=0, exchange_parity=0, exchange_uniforms=None, n_exchanged=None, walkers=None):
@@ -187,15 +202,9 @@ def pair_mcmc(plan, x, e, e_valid, temperature, noise_std, n_steps, noise=None, 
     n_exchanged [B] (int32): accepted exchanges at the pair's lower slot, like n_accepted; walkers [B] (int32, in / out)."""
     from . import _lib
     B, nd = x.shape
-    if nd != plan.n_particles * plan.n_dims:
-        raise ValueError(f"pair_mcmc: x has {nd} columns, the target {plan.n_particles} x {plan.n_dims}")
-    if (noise is None) != (uniforms is None):
-        raise ValueError("pair_mcmc: noise and uniforms go together")
-    temps = temperature if torch.is_tensor(temperature) else None
     n_frames = n_steps // traj_every if traj is not None else 0
-    _check_tensors("pair_mcmc", x, [(x, (B, nd)), (e, (B,)), (temps, (B,)), (noise, (n_steps, B, nd)), (uniforms, (n_steps, B)),
-                                    (traj, (n_frames, B, nd)), (traj_e, (n_frames, B))])
-    _check_tensors("pair_mcmc", x, [(n_accepted, (B,))], dtype=torch.int32)
+    temps = _chain_launch_checks("pair_mcmc", plan, x, temperature, noise, uniforms, n_steps, n_accepted,
+                                 [(e, (B,)), (traj, (n_frames, B, nd)), (traj_e, (n_frames, B))])
     if traj is not None and traj_every < 1:
         raise ValueError("pair_mcmc: traj_every must be at least 1")
     name = "bgk_box_" if isinstance(plan, BoxPlan) else "bgk_pair_"
@@ -233,15 +242,9 @@ def pair_hmc(plan, x, e, e_valid, temperature, step_size, n_leapfrog, mass, n_st
     ``pair_mcmc``'s; noise [n_steps, B, n d] holds the standard normals of the momenta."""
     from . import _lib
     B, nd = x.shape
-    if nd != plan.n_particles * plan.n_dims:
-        raise ValueError(f"pair_hmc: x has {nd} columns, the target {plan.n_particles} x {plan.n_dims}")
-    if (noise is None) != (uniforms is None):
-        raise ValueError("pair_hmc: noise and uniforms go together")
-    temps = temperature if torch.is_tensor(temperature) else None
     n_frames = n_steps // traj_every if traj is not None else 0
-    _check_tensors("pair_hmc", x, [(x, (B, nd)), (e, (B,)), (temps, (B,)), (noise, (n_steps, B, nd)), (uniforms, (n_steps, B)),
-                                   (traj, (n_frames, B, nd)), (traj_e, (n_frames, B))])
-    _check_tensors("pair_hmc", x, [(n_accepted, (B,))], dtype=torch.int32)
+    temps = _chain_launch_checks("pair_hmc", plan, x, temperature, noise, uniforms, n_steps, n_accepted,
+                                 [(e, (B,)), (traj, (n_frames, B, nd)), (traj_e, (n_frames, B))])
     if traj is not None and traj_every < 1:
         raise ValueError("pair_hmc: traj_every must be at least 1")
     name = "bgk_box_hmc" if isinstance(plan, BoxPlan) else "bgk_pair_hmc"
@@ -268,14 +271,21 @@ def hmc_fused_by_default(plan):
     return isinstance(plan, PairPlan) and hmc_tile_rows(plan.n_particles * plan.n_dims) >= HMC_FUSED_MIN_ROWS
 
 
+def _chain_tile_rows(nd, first, second):
+    """rows of a tile of a chain kernel whose lanes keep ``first`` + ``second`` LDS tiles of rows of ``nd`` floats (csrc/bgk_chain.h,
+    ``chain_layout``): the most, at most 64, whose tiles (odd row stride, the second side starting at a multiple of 32 words) fit
+    63,488 bytes"""
+    S = nd | 1
+    rows = min(64, 63488 // (4 * (first + second) * S))
+    while (((first * rows * S + 31) & ~31) + second * rows * S) * 4 > 63488:
+        rows -= 1
+    return rows
+
+
 def hmc_tile_rows(nd):
     """rows of a tile of the HMC kernel for rows of ``nd`` floats (csrc/bgk_hmc.hip, ``hmc_run``): the most, at most 64, whose five LDS
     tiles (odd row stride, the second (position, gradient) pair starting at a multiple of 32 words) fit 63,488 bytes"""
-    S = nd | 1
-    rows = min(64, 63488 // (20 * S))
-    while (((3 * rows * S + 31) & ~31) + 2 * rows * S) * 4 > 63488:
-        rows -= 1
-    return rows
+    return _chain_tile_rows(nd, 3, 2)
 
 
 def _is_number(v):
@@ -643,11 +653,7 @@ class HMCStep(MCMCStep):
 def mcmc_tile_rows(nd):
     """rows of a tile of the chain kernel for rows of ``nd`` floats (csrc/bgk_mcmc.hip, ``mcmc_run``): the most, at most 64, whose two
     LDS tiles (odd row stride, the second one starting at a multiple of 32 words) fit 63,488 bytes"""
-    S = nd | 1
-    rows = min(64, 63488 // (8 * S))
-    while (((rows * S + 31) & ~31) + rows * S) * 4 > 63488:
-        rows -= 1
-    return rows
+    return _chain_tile_rows(nd, 1, 1)
 
 
 def exchange_permutation(energies, temperatures, r, n_replicas, parity):

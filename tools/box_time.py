@@ -73,9 +73,7 @@ def main():
             med = {k: statistics.median(v) for k, v in times.items()}
             rate = float(fused.n_accepted.float().mean()) / fused.n_proposed
             S = nd | 1
-            rows = 64
-            while (((rows * S + 31) & ~31) + rows * S) * 4 > 63488:
-                rows -= 1
+            rows = sampling.mcmc_tile_rows(nd)
             tiles = (B + rows - 1) // rows
             cfg = f"{min(tiles, 4096)} x 64, {rows}, {(((rows * S + 31) & ~31) + rows * S) * 4} B"
             print(f"<!-- {label} {B}: min .. max " + ", ".join(f"({k}) {min(v):.2f} .. {max(v):.2f}" for k, v in times.items()) + " -->")

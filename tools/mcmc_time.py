@@ -88,9 +88,7 @@ def main():
             rate = float(fused.n_accepted.float().mean()) / fused.n_proposed
             rate_b = float(general.n_accepted.float().mean()) / general.n_proposed
             S = (n * d) | 1
-            rows = 64
-            while (((rows * S + 31) & ~31) + rows * S) * 4 > 63488:
-                rows -= 1
+            rows = sampling.mcmc_tile_rows(n * d)
             tiles = (B + rows - 1) // rows
             cfg = f"{min(tiles, 4096)} x 64, {rows}, {(((rows * S + 31) & ~31) + rows * S) * 4} B"
             print(f"<!-- {label} {B}: min .. max " + ", ".join(f"({k}) {min(v):.2f} .. {max(v):.2f}" for k, v in times.items())
