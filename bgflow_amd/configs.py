@@ -174,7 +174,7 @@ def _dihedral(p, i, j, k, l):
     return float(np.arctan2(np.linalg.norm(b2) * (b1 @ n2), n1 @ n2))
 
 
-def synthetic_forcefield(z_matrix, xyz, seed=0, unit_energy=1.0):
+def synthetic_forcefield(z_matrix, xyz, seed=0, unit_energy=1.0, implicit_solvent=False):
     """A ``MolecularMechanicsEnergy`` on the topology of a global Z-matrix [n, 4] (rows ``atom, bond, angle, torsion partner``; -1: none)
     with the geometry ``xyz`` [n, 3] (nm) as its bonded minimum.  This is a molecule-SHAPED TEST TARGET, NOT AMBER or any other
     published force field: its parameters are made up.
@@ -184,7 +184,9 @@ def synthetic_forcefield(z_matrix, xyz, seed=0, unit_energy=1.0):
       * per-atom charge (uniform in [-0.5, 0.5], shifted to a neutral molecule), sigma (uniform in [0.15, 0.35] nm) and epsilon (uniform
         in [0.05, 0.5] kJ/mol) from ``numpy.random.RandomState(seed)``;
       * 1-2 and 1-3 pairs of the bond graph excluded; 1-4 pairs as exceptions with the Coulomb product scaled by 1 / 1.2 and the
-        Lennard-Jones epsilon by 0.5."""
+        Lennard-Jones epsilon by 0.5;
+      * ``implicit_solvent=True``: a GBSA-OBC solvent on top, with the charges above, radii (uniform in [0.11, 0.20] nm) and scales (uniform
+        in [0.70, 0.90]) drawn next from the same generator, and the default dielectrics and surface energy."""
     from .molecule import MolecularMechanicsEnergy
     z = np.asarray(z_matrix, np.int64)
     p = np.asarray(xyz, np.float64).reshape(-1, 3)
@@ -203,6 +205,7 @@ def synthetic_forcefield(z_matrix, xyz, seed=0, unit_energy=1.0):
     charge = rng.uniform(-0.5, 0.5, n)
     charge -= charge.mean()
     sigma, epsilon = rng.uniform(0.15, 0.35, n), rng.uniform(0.05, 0.5, n)
+    solvent = (charge, rng.uniform(0.11, 0.20, n), rng.uniform(0.70, 0.90, n)) if implicit_solvent else None
     near = np.eye(n, dtype=bool)                          # the bond graph's neighbours within 1, 2, 3 bonds
     adj = np.zeros((n, n), bool)
     adj[bonds[:, 0], bonds[:, 1]] = adj[bonds[:, 1], bonds[:, 0]] = True
@@ -221,15 +224,16 @@ def synthetic_forcefield(z_matrix, xyz, seed=0, unit_energy=1.0):
         nonbonded=(charge, sigma, epsilon),
         exceptions=(np.stack([i, j], axis=1), np.where(one_four, charge[i] * charge[j] / 1.2, 0.0), 0.5 * (sigma[i] + sigma[j]),
                     np.where(one_four, 0.5 * np.sqrt(epsilon[i] * epsilon[j]), 0.0)),
-        unit_energy=unit_energy)
+        unit_energy=unit_energy, implicit_solvent=solvent)
 
 
-def make_ala2_mm_generator(device=None, dtype=torch.float32, seed=0, unit_energy=2.494, **kwargs):
+def make_ala2_mm_generator(device=None, dtype=torch.float32, seed=0, unit_energy=2.494, implicit_solvent=False, **kwargs):
     """the alanine-dipeptide spline generator (``make_ala2_spline_generator``, same flow and prior) with the synthetic force field of
     ``synthetic_forcefield(ala2_global_z_matrix(), xyz, seed)`` as its target in place of the Gaussian; ``unit_energy``: kT in kJ/mol
-    (2.494 at 300 K)"""
+    (2.494 at 300 K); ``implicit_solvent``: the force field's GBSA-OBC solvent on top"""
     _, _, xyz = ala2_system()
-    target = synthetic_forcefield(ala2_global_z_matrix(), xyz.reshape(-1, 3), seed=seed, unit_energy=unit_energy)
+    target = synthetic_forcefield(ala2_global_z_matrix(), xyz.reshape(-1, 3), seed=seed, unit_energy=unit_energy,
+                                  implicit_solvent=implicit_solvent)
     return make_ala2_spline_generator(device=device, dtype=dtype, target=target, **kwargs)
 
 

@@ -14,11 +14,19 @@
  * Envelope: 2 <= n <= 64 (S <= 193), at most 256 bonds, 512 angles, 1024 torsion terms.  Dynamic LDS below 64 KiB:
  *   forward   64 rows: 64 x 193 x 4 B = 49,408 B at n = 64 (alanine dipeptide, n = 22, S = 67: 17,152 B)
  *   backward  x tile + gradient tile + 64 row scales: 64 rows while 2 x 64 x S x 4 + 256 <= 65,536 B (S <= 127; n = 22: 34,560 B),
- *             else 32 rows: 2 x 32 x 193 x 4 + 256 = 49,664 B at n = 64 (lanes 32..63 only stage and store) */
+ *             else 32 rows: 2 x 32 x 193 x 4 + 256 = 49,664 B at n = 64 (lanes 32..63 only stage and store)
+ *
+ * The bgk_molecule_solvent_* entries add an implicit solvent (Generalised Born, OBC2, plus the surface term; bgk_solvent_terms.h) in the SAME
+ * launch on the row tile staged once: the kernels' SOLVENT instantiations run the vacuum functions unchanged, then the solvent functions
+ * on the same LDS row.  Each lane owns an extension behind the tiles, at an odd stride: forward n | 1 floats (the Born radii), backward
+ * (3 n) | 1 (B_i, d E / d B_i, the chain factors).  Rows per tile are the most of 64 / 32 / 16 that fit 64 KiB:
+ *   forward   64 x (67 + 23) x 4 = 23,040 B at n = 22; n = 64: 64 x (193 + 65) x 4 = 66,048 B does not fit, 32 rows: 33,024 B
+ *   backward  64 x (2 x 67 + 67) x 4 + 256 = 51,712 B at n = 22; n = 64: 16 rows, 16 x (2 x 193 + 193) x 4 + 256 = 37,312 B */
 #include "bgk_common.h"
 #include "bgk_pair_tile.h"
 #include "bgk_reduce.h"
 #include "bgk_molecule_terms.h"
+#include "bgk_solvent_terms.h"
 
 namespace {
 
@@ -30,10 +38,13 @@ struct MolArgs {
     float inv;                                          /* 1 / (unit_energy temperature) */
     float* u; const float* dlogp; int drop_nonfinite; double* partial;                    /* forward (+ loss partials [gridDim.x][2]) */
     const float* g_u; const float* g_scalar; float* g_dlogp; float* g_x;                  /* backward */
+    BgkSolvent sv; int ext;                             /* the solvent kernels: the lane's stride in the extension after the tiles */
 };
 
+template <bool SOLVENT>
 __global__ __launch_bounds__(BGK_TILE_THREADS) void molecule_energy_kernel(MolArgs a, const int4* __restrict__ terms,
-                                                                            const float* __restrict__ pairs) {
+                                                                            const float* __restrict__ pairs,
+                                                                            const float4* __restrict__ atoms) {
     extern __shared__ float s_x[];
     const int tid = threadIdx.x, S = a.nd | 1;
     const int64_t n_tiles = (a.B + a.rows - 1) / a.rows;
@@ -44,7 +55,10 @@ __global__ __launch_bounds__(BGK_TILE_THREADS) void molecule_energy_kernel(MolAr
         tile_stage(a.x, b0, rows, a.nd, a.magic, s_x);
         __syncthreads();
         if (tid < rows) {
-            const float u = bgk_mm_row_energy(s_x + tid * S, terms, pairs, a.m) * a.inv;
+            float e = bgk_mm_row_energy(s_x + tid * S, terms, pairs, a.m);
+            if constexpr (SOLVENT)                     /* E_vacuum + (E_GB + E_SA), on the same staged row; +inf + +inf stays +inf */
+                e += bgk_gb_row_energy(s_x + tid * S, s_x + a.rows * S + tid * a.ext, atoms, a.sv);
+            const float u = e * a.inv;
             a.u[b0 + tid] = u;
             if (a.partial) {
                 const float loss = u - a.dlogp[b0 + tid];
@@ -71,8 +85,10 @@ __global__ __launch_bounds__(BGK_WAVE) void molecule_loss_merge_kernel(const dou
     if (threadIdx.x == 0) { loss_sums[0] = s; loss_sums[1] = c; }
 }
 
+template <bool SOLVENT>
 __global__ __launch_bounds__(BGK_TILE_THREADS) void molecule_energy_bwd_kernel(MolArgs a, const int4* __restrict__ terms,
-                                                                                const float* __restrict__ pairs) {
+                                                                                const float* __restrict__ pairs,
+                                                                                const float4* __restrict__ atoms) {
     extern __shared__ float s_mem[];
     const int tid = threadIdx.x, nd = a.nd, S = nd | 1;
     float* s_x = s_mem;
@@ -93,6 +109,8 @@ __global__ __launch_bounds__(BGK_TILE_THREADS) void molecule_energy_bwd_kernel(M
             if (a.g_dlogp) a.g_dlogp[b] = -gr;          /* d(sum_i (u_i - dlogp_i)) / d dlogp_i = -1 for the kept samples */
             s_scale[tid] = gr * a.inv;
             bgk_mm_row_gradient(s_x + tid * S, s_g + tid * S, terms, pairs, a.m);
+            if constexpr (SOLVENT)
+                bgk_gb_row_gradient(s_x + tid * S, s_g + tid * S, s_scale + BGK_TILE_THREADS + tid * a.ext, atoms, a.sv);
         }
         __syncthreads();
         for (int i = tid; i < rows * nd; i += BGK_TILE_THREADS) {    /* tile_store, scaled by the row's g / (unit_energy T) */
@@ -128,14 +146,34 @@ int molecule_common(const char* what, const float* x, int64_t B, int32_t n_atoms
     return 0;
 }
 
-/* loss_sums != NULL: also the KL loss sums, over dlogp, through the [nblk, 2] f64 workspace `partial` */
+/* the solvent table and prefactor of the bgk_molecule_solvent_* entries */
+struct SolventSpec { const float* table; double prefactor; };
+
+/* checks the solvent arguments and fills the record's solvent part */
+int molecule_solvent(const char* what, const SolventSpec& sol, int64_t B, MolArgs* a, const float4** atoms) {
+    BGK_CHECK_ARG(B == 0 || (sol.table && (uintptr_t)sol.table % 16 == 0), "%s: null solvent table / not aligned to 16 bytes", what);
+    BGK_CHECK_ARG(std::isfinite(sol.prefactor), "%s: the solvent prefactor is not finite", what);
+    a->sv = BgkSolvent{a->m.n, (float)sol.prefactor};
+    *atoms = reinterpret_cast<const float4*>(sol.table);
+    return 0;
+}
+
+/* the most rows of a tile (64, 32 or 16) whose LDS stays within the limit: rows x words_per_row + fixed_words floats */
+int molecule_rows(int words_per_row, int fixed_words) {
+    int rows = BGK_TILE_THREADS;
+    while (rows > 16 && (rows * words_per_row + fixed_words) * (int)sizeof(float) > MM_LDS_LIMIT) rows /= 2;
+    return rows;
+}
+
+/* loss_sums != NULL: also the KL loss sums, over dlogp, through the [nblk, 2] f64 workspace `partial`; sol != NULL: with the solvent terms */
 int molecule_forward(const char* what, const float* x, int64_t B, int32_t n_atoms, int32_t n_bonds, int32_t n_angles, int32_t n_torsions,
                      int32_t n_pairs, const int32_t* tables, double unit_energy, double temperature, float* u, const float* dlogp,
-                     int32_t drop_nonfinite, double* partial, int32_t nblk, double* loss_sums, void* stream) {
+                     int32_t drop_nonfinite, double* partial, int32_t nblk, double* loss_sums, void* stream, const SolventSpec* sol = nullptr) {
     MolArgs a{};
-    const int4* terms; const float* pairs;
-    const int st = molecule_common(what, x, B, n_atoms, n_bonds, n_angles, n_torsions, n_pairs, tables, unit_energy, temperature, &a, &terms, &pairs);
+    const int4* terms; const float* pairs; const float4* atoms = nullptr;
+    int st = molecule_common(what, x, B, n_atoms, n_bonds, n_angles, n_torsions, n_pairs, tables, unit_energy, temperature, &a, &terms, &pairs);
     if (st) return st;
+    if (sol && (st = molecule_solvent(what, *sol, B, &a, &atoms))) return st;
     BGK_CHECK_ARG(!loss_sums || (dlogp && partial && nblk >= 1), "%s: the loss sums need dlogp and a [nblk, 2] f64 workspace", what);
     hipStream_t s = (hipStream_t)stream;
     if (B == 0) {               /* an empty batch: the loss sums are zero */
@@ -143,16 +181,42 @@ int molecule_forward(const char* what, const float* x, int64_t B, int32_t n_atom
         return 0;
     }
     BGK_CHECK_ARG(u, "%s: null output", what);
-    a.rows = BGK_TILE_THREADS;
+    a.ext = sol ? (n_atoms | 1) : 0;                    /* the Born radii of a lane, at an odd stride */
+    a.rows = sol ? molecule_rows((a.nd | 1) + a.ext, 0) : BGK_TILE_THREADS;
     a.u = u; a.drop_nonfinite = drop_nonfinite;
     if (loss_sums) { a.dlogp = dlogp; a.partial = partial; }
-    const size_t lds = (size_t)a.rows * (a.nd | 1) * sizeof(float);
+    const size_t lds = (size_t)a.rows * ((a.nd | 1) + a.ext) * sizeof(float);
     int grid = tile_grid(B, a.rows);
     if (loss_sums && grid > nblk) grid = nblk;
-    hipLaunchKernelGGL(molecule_energy_kernel, dim3(grid), dim3(BGK_TILE_THREADS), lds, s, a, terms, pairs);
+    if (sol) hipLaunchKernelGGL(molecule_energy_kernel<true>, dim3(grid), dim3(BGK_TILE_THREADS), lds, s, a, terms, pairs, atoms);
+    else hipLaunchKernelGGL(molecule_energy_kernel<false>, dim3(grid), dim3(BGK_TILE_THREADS), lds, s, a, terms, pairs, atoms);
     const int st2 = bgk_launch_status(what);
     if (st2 || !loss_sums) return st2;
     hipLaunchKernelGGL(molecule_loss_merge_kernel, dim3(1), dim3(BGK_WAVE), 0, s, partial, grid, loss_sums);
+    return bgk_launch_status(what);
+}
+
+int molecule_backward(const char* what, const float* x, int64_t B, int32_t n_atoms, int32_t n_bonds, int32_t n_angles, int32_t n_torsions,
+                      int32_t n_pairs, const int32_t* tables, double unit_energy, double temperature, const float* g_u, const float* g_scalar,
+                      const float* u, const float* dlogp, int32_t drop_nonfinite, float* g_dlogp, float* g_x, void* stream,
+                      const SolventSpec* sol = nullptr) {
+    MolArgs a{};
+    const int4* terms; const float* pairs; const float4* atoms = nullptr;
+    int st = molecule_common(what, x, B, n_atoms, n_bonds, n_angles, n_torsions, n_pairs, tables, unit_energy, temperature, &a, &terms, &pairs);
+    if (st) return st;
+    if (sol && (st = molecule_solvent(what, *sol, B, &a, &atoms))) return st;
+    BGK_CHECK_ARG(g_u || (g_scalar && u && dlogp), "%s: need g_u [B] or (g_scalar, u, dlogp)", what);
+    if (B == 0) return 0;
+    BGK_CHECK_ARG(g_x, "%s: null output", what);
+    const int S = a.nd | 1;
+    a.ext = sol ? (a.nd | 1) : 0;                       /* B_i, d E / d B_i and the chain factors of a lane, at an odd stride */
+    a.rows = molecule_rows(2 * S + a.ext, BGK_TILE_THREADS);                                        /* x tile, gradient tile, row scales */
+    a.u = const_cast<float*>(u); a.dlogp = dlogp; a.drop_nonfinite = drop_nonfinite;
+    a.g_u = g_u; a.g_scalar = g_scalar; a.g_dlogp = g_dlogp; a.g_x = g_x;
+    const size_t lds = ((size_t)a.rows * (2 * S + a.ext) + BGK_TILE_THREADS) * sizeof(float);
+    const dim3 grid(tile_grid(B, a.rows));
+    if (sol) hipLaunchKernelGGL(molecule_energy_bwd_kernel<true>, grid, dim3(BGK_TILE_THREADS), lds, (hipStream_t)stream, a, terms, pairs, atoms);
+    else hipLaunchKernelGGL(molecule_energy_bwd_kernel<false>, grid, dim3(BGK_TILE_THREADS), lds, (hipStream_t)stream, a, terms, pairs, atoms);
     return bgk_launch_status(what);
 }
 
@@ -177,20 +241,35 @@ extern "C" int bgk_molecule_energy_backward(const float* x, int64_t B, int32_t n
                                             int32_t n_pairs, const int32_t* tables, double unit_energy, double temperature, const float* g_u,
                                             const float* g_scalar, const float* u, const float* dlogp, int32_t drop_nonfinite,
                                             float* g_dlogp, float* g_x, void* stream) {
-    const char* what = "bgk_molecule_energy_backward";
-    MolArgs a{};
-    const int4* terms; const float* pairs;
-    const int st = molecule_common(what, x, B, n_atoms, n_bonds, n_angles, n_torsions, n_pairs, tables, unit_energy, temperature, &a, &terms, &pairs);
-    if (st) return st;
-    BGK_CHECK_ARG(g_u || (g_scalar && u && dlogp), "%s: need g_u [B] or (g_scalar, u, dlogp)", what);
-    if (B == 0) return 0;
-    BGK_CHECK_ARG(g_x, "%s: null output", what);
-    const int S = a.nd | 1;
-    const int bytes_at_64 = (2 * BGK_TILE_THREADS * S + BGK_TILE_THREADS) * (int)sizeof(float);     /* x tile, gradient tile, row scales */
-    a.rows = bytes_at_64 <= MM_LDS_LIMIT ? BGK_TILE_THREADS : BGK_TILE_THREADS / 2;
-    a.u = const_cast<float*>(u); a.dlogp = dlogp; a.drop_nonfinite = drop_nonfinite;
-    a.g_u = g_u; a.g_scalar = g_scalar; a.g_dlogp = g_dlogp; a.g_x = g_x;
-    const size_t lds = ((size_t)2 * a.rows * S + BGK_TILE_THREADS) * sizeof(float);
-    hipLaunchKernelGGL(molecule_energy_bwd_kernel, dim3(tile_grid(B, a.rows)), dim3(BGK_TILE_THREADS), lds, (hipStream_t)stream, a, terms, pairs);
-    return bgk_launch_status(what);
+    return molecule_backward("bgk_molecule_energy_backward", x, B, n_atoms, n_bonds, n_angles, n_torsions, n_pairs, tables, unit_energy,
+                             temperature, g_u, g_scalar, u, dlogp, drop_nonfinite, g_dlogp, g_x, stream);
+}
+
+extern "C" int bgk_molecule_solvent_energy(const float* x, int64_t B, int32_t n_atoms, int32_t n_bonds, int32_t n_angles, int32_t n_torsions,
+                                           int32_t n_pairs, const int32_t* tables, double unit_energy, double temperature,
+                                           const float* solvent, double gb_prefactor, float* u, void* stream) {
+    const SolventSpec sol{solvent, gb_prefactor};
+    return molecule_forward("bgk_molecule_solvent_energy", x, B, n_atoms, n_bonds, n_angles, n_torsions, n_pairs, tables, unit_energy,
+                            temperature, u, nullptr, 0, nullptr, 0, nullptr, stream, &sol);
+}
+
+extern "C" int bgk_molecule_solvent_energy_kl_sums(const float* x, int64_t B, int32_t n_atoms, int32_t n_bonds, int32_t n_angles,
+                                                   int32_t n_torsions, int32_t n_pairs, const int32_t* tables, double unit_energy,
+                                                   double temperature, const float* solvent, double gb_prefactor, float* u,
+                                                   const float* dlogp, int32_t drop_nonfinite, double* partial, int32_t nblk,
+                                                   double* loss_sums, void* stream) {
+    BGK_CHECK_ARG(loss_sums, "bgk_molecule_solvent_energy_kl_sums: loss_sums is NULL");
+    const SolventSpec sol{solvent, gb_prefactor};
+    return molecule_forward("bgk_molecule_solvent_energy_kl_sums", x, B, n_atoms, n_bonds, n_angles, n_torsions, n_pairs, tables, unit_energy,
+                            temperature, u, dlogp, drop_nonfinite, partial, nblk, loss_sums, stream, &sol);
+}
+
+extern "C" int bgk_molecule_solvent_energy_backward(const float* x, int64_t B, int32_t n_atoms, int32_t n_bonds, int32_t n_angles,
+                                                    int32_t n_torsions, int32_t n_pairs, const int32_t* tables, double unit_energy,
+                                                    double temperature, const float* solvent, double gb_prefactor, const float* g_u,
+                                                    const float* g_scalar, const float* u, const float* dlogp, int32_t drop_nonfinite,
+                                                    float* g_dlogp, float* g_x, void* stream) {
+    const SolventSpec sol{solvent, gb_prefactor};
+    return molecule_backward("bgk_molecule_solvent_energy_backward", x, B, n_atoms, n_bonds, n_angles, n_torsions, n_pairs, tables,
+                             unit_energy, temperature, g_u, g_scalar, u, dlogp, drop_nonfinite, g_dlogp, g_x, stream, &sol);
 }

@@ -7,6 +7,9 @@ The general path is the formulas in torch ops -- any device, dtype and layout, t
 [B, 3 n] of 2..64 atoms (at most ``MOLECULE_MAX_BONDS`` bonds, ``MOLECULE_MAX_ANGLES`` angles, ``MOLECULE_MAX_TORSIONS`` torsion terms) at
 a scalar temperature runs on csrc/bgk_molecule.hip instead: one launch for the energy (optionally with the KL integrand's sums, so
 ``KLTrainer`` keeps its fused loss path), one for the gradient.  The kernel's arithmetic is defined in csrc/bgk_molecule_terms.h.
+
+``implicit_solvent=(charge, radius, scale)`` adds a GBSA-OBC solvent (Generalised Born, OBC2, plus the surface-area term: the arithmetic
+of OpenMM's ``GBSAOBCForce``, csrc/bgk_solvent_terms.h) to both paths; on the kernel path the vacuum and solvent terms are one launch.
 """
 import numpy as np
 import torch
@@ -19,6 +22,8 @@ COULOMB = 138.935458                                  # 1 / (4 pi eps0) in kJ nm
 MOLECULE_MAX_ATOMS = 64                               # the envelope of csrc/bgk_molecule.hip (BGK_MOLECULE_MAX_* of include/bgflow_amd.h)
 MOLECULE_MAX_BONDS, MOLECULE_MAX_ANGLES, MOLECULE_MAX_TORSIONS = 256, 512, 1024
 _MAX_BLOCKS = 2048                                    # block partials of the loss sums
+GB_OFFSET, GB_PROBE = 0.009, 0.14                     # GBSAOBCForce (OBC2): dielectric offset and probe radius in nm
+GB_ALPHA, GB_BETA, GB_GAMMA = 1.0, 0.8, 4.85          # 1 / B = 1 / rho - tanh(alpha Psi - beta Psi^2 + gamma Psi^3) / r
 
 # the term groups: name -> (atoms per term, the float tables, the integer tables)
 _GROUPS = {"bond": (2, ("r0", "k"), ()), "angle": (3, ("theta0", "k"), ()), "torsion": (4, ("phase", "k"), ("periodicity",)),
@@ -69,39 +74,49 @@ def _scale(plan):
     return (float(plan.unit_energy), float(plan.temperature))
 
 
+def _solvent(plan, device):
+    """the extra arguments of the bgk_molecule_solvent_* entries: (the solvent table's pointer, the prefactor), or () for a vacuum energy"""
+    from . import _lib
+    d = plan.dist
+    return (_lib.ptr(d._device_solvent(device)), d.gb_prefactor()) if d.has_solvent else ()
+
+
 def _launch_energy(plan, tables, x2, dlogp=None, drop_nonfinite=False, want_sums=False):
-    """one launch of bgk_molecule_energy / bgk_molecule_energy_kl_sums on the contiguous rows x2: u [B] (and the f64 loss sums [2])"""
+    """one launch of bgk_molecule_energy / bgk_molecule_energy_kl_sums (with solvent tables: bgk_molecule_solvent_energy / _kl_sums) on the
+    contiguous rows x2: u [B] (and the f64 loss sums [2])"""
     from . import _lib
     B, dev = x2.shape[0], x2.device
     u = torch.empty(B, dtype=torch.float32, device=dev)
     sums = None
+    head = "bgk_molecule_solvent_energy" if plan.dist.has_solvent else "bgk_molecule_energy"
     with torch.cuda.device(dev):
+        common = (_lib.ptr(x2), B, *_counts(plan), _lib.ptr(tables), *_scale(plan), *_solvent(plan, dev), _lib.ptr(u))
         if want_sums:
             partial = torch.empty((_MAX_BLOCKS, 2), dtype=torch.float64, device=dev)
             sums = torch.empty(2, dtype=torch.float64, device=dev)
-            name = "bgk_molecule_energy_kl_sums"
-            st = _lib.lib().bgk_molecule_energy_kl_sums(_lib.ptr(x2), B, *_counts(plan), _lib.ptr(tables), *_scale(plan), _lib.ptr(u),
-                                                        _lib.ptr(dlogp), int(bool(drop_nonfinite)), _lib.ptr(partial), _MAX_BLOCKS,
-                                                        _lib.ptr(sums), _lib.stream_ptr(dev))
+            name = head + "_kl_sums"
+            st = getattr(_lib.lib(), name)(*common, _lib.ptr(dlogp), int(bool(drop_nonfinite)), _lib.ptr(partial), _MAX_BLOCKS,
+                                           _lib.ptr(sums), _lib.stream_ptr(dev))
         else:
-            name = "bgk_molecule_energy"
-            st = _lib.lib().bgk_molecule_energy(_lib.ptr(x2), B, *_counts(plan), _lib.ptr(tables), *_scale(plan), _lib.ptr(u),
-                                                _lib.stream_ptr(dev))
+            name = head
+            st = getattr(_lib.lib(), name)(*common, _lib.stream_ptr(dev))
     _lib.check(st, name)
     return u, sums
 
 
 def _launch_backward(plan, tables, x2, g_u=None, g_scalar=None, u=None, dlogp=None, drop_nonfinite=False, want_gdl=False):
-    """one launch of bgk_molecule_energy_backward: (g_x [B, 3 n], g_dlogp [B] or None)"""
+    """one launch of bgk_molecule_energy_backward (with solvent tables: bgk_molecule_solvent_energy_backward): (g_x [B, 3 n], g_dlogp [B]
+    or None)"""
     from . import _lib
     B, dev = x2.shape[0], x2.device
     gx = torch.empty_like(x2)
     g_dl = torch.empty(B, dtype=torch.float32, device=dev) if want_gdl else None
+    name = "bgk_molecule_solvent_energy_backward" if plan.dist.has_solvent else "bgk_molecule_energy_backward"
     with torch.cuda.device(dev):
-        st = _lib.lib().bgk_molecule_energy_backward(_lib.ptr(x2), B, *_counts(plan), _lib.ptr(tables), *_scale(plan), _lib.ptr(g_u),
-                                                     _lib.ptr(g_scalar), _lib.ptr(u), _lib.ptr(dlogp), int(bool(drop_nonfinite)),
-                                                     _lib.ptr(g_dl), _lib.ptr(gx), _lib.stream_ptr(dev))
-    _lib.check(st, "bgk_molecule_energy_backward")
+        st = getattr(_lib.lib(), name)(_lib.ptr(x2), B, *_counts(plan), _lib.ptr(tables), *_scale(plan), *_solvent(plan, dev), _lib.ptr(g_u),
+                                       _lib.ptr(g_scalar), _lib.ptr(u), _lib.ptr(dlogp), int(bool(drop_nonfinite)),
+                                       _lib.ptr(g_dl), _lib.ptr(gx), _lib.stream_ptr(dev))
+    _lib.check(st, name)
     return gx, g_dl
 
 
@@ -189,14 +204,19 @@ class MolecularMechanicsEnergy(Energy):
                                                                     eps_ij = sqrt(e_i e_j), qq_ij = q_i q_j (Lorentz-Berthelot):
                     4 eps_ij ((sigma_ij / r)^12 - (sigma_ij / r)^6) + 138.935458 qq_ij / r            NonbondedForce, NoCutoff
         exceptions  (idx int[Ne, 2], chargeprod[Ne], sigma[Ne], epsilon[Ne])   replaces that pair's (qq, sigma, eps); (0, ., 0) excludes it
+        implicit_solvent  (charge[n], radius[n], scale[n])          Generalised Born (OBC2) + surface area over ALL pairs        GBSAOBCForce
+                    with ``solute_dielectric``, ``solvent_dielectric`` and ``surface_area_energy`` (kJ/mol/nm^2; 0: no surface term); the
+                    charges are the solvent force's own, so no nonbonded tables are needed (formulas: csrc/bgk_solvent_terms.h)
 
     phi is the IUPAC dihedral of atoms (i, j, k, l) (trans = pi), the sign OpenMM uses; several torsion terms may name the same four
     atoms (Fourier series, impropers).  ``energy(x, temperature)`` is the reduced energy ``E / unit_energy / temperature`` of shape
     [B, 1] (``unit_energy``: kT in kJ/mol), ``force(x)`` minus its gradient.  Two coincident atoms of a pair that is not excluded give
-    the energy +inf (never NaN) and contribute no gradient.
+    the energy +inf (never NaN) and contribute no gradient; with an implicit solvent ANY two coincident atoms do, and the solvent terms
+    then add nothing to that row's gradient.
 
     The constructor raises ``ValueError``, naming the term, for an atom outside ``0..n_atoms-1``, an atom twice within a term, a
-    non-positive ``r0`` or ``sigma``, a periodicity outside 1..6 and two exceptions for one pair.  ``to_arrays`` / ``from_arrays`` /
+    non-positive ``r0`` or ``sigma``, a periodicity outside 1..6 and two exceptions for one pair; naming the atom, for a solvent array of the
+    wrong length, a non-finite entry, a ``radius <= 0.009`` and a ``scale <= 0``; and for a dielectric ``<= 0`` or a negative surface energy.  ``to_arrays`` / ``from_arrays`` /
     ``save`` / ``load`` carry the tables through a dict / an ``.npz`` of numbers only.
 
     A contiguous f32 HIP tensor [B, 3 n] of 2..64 atoms at a scalar temperature runs on csrc/bgk_molecule.hip (energy, gradient, KL loss
@@ -204,12 +224,13 @@ class MolecularMechanicsEnergy(Energy):
     "Molecular mechanics energy"), False (the torch formulas).  Everything else -- CPU, f64, strided rows, second derivatives, more
     atoms or terms than the kernel's envelope -- runs the torch formulas, which form angles and dihedrals with ``atan2``.
 
-    Out of scope: periodic boxes and cutoffs, constraints, implicit solvent, CMAP and other torsion forms, chain kernels for MCMC /
+    Out of scope: periodic boxes and cutoffs, constraints, other Generalised Born models, CMAP and other torsion forms, chain kernels for MCMC /
     HMC on this target (the samplers run their torch path on it), and folding ``LinLogCutEnergy`` / ``GradientClippedEnergy`` into the
     launch (the wrappers evaluate this energy and apply their own stand-alone kernels)."""
     fused = True
 
-    def __init__(self, n_atoms, bonds=None, angles=None, torsions=None, nonbonded=None, exceptions=None, unit_energy=1.0):
+    def __init__(self, n_atoms, bonds=None, angles=None, torsions=None, nonbonded=None, exceptions=None, unit_energy=1.0,
+                 implicit_solvent=None, solute_dielectric=1.0, solvent_dielectric=78.5, surface_area_energy=2.25936):
         if not (isinstance(n_atoms, (int, np.integer)) and n_atoms >= 1):
             raise ValueError(f"MolecularMechanicsEnergy: n_atoms must be a positive integer, got {n_atoms!r}")
         n_atoms = int(n_atoms)
@@ -266,6 +287,28 @@ class MolecularMechanicsEnergy(Energy):
             raise ValueError(f"MolecularMechanicsEnergy: nonbonded atom {int(t)} has sigma <= 0")
         for t in np.flatnonzero(self.nonbonded_epsilon.numpy() < 0):
             raise ValueError(f"MolecularMechanicsEnergy: nonbonded atom {int(t)} has epsilon < 0")
+        self.has_solvent = implicit_solvent is not None
+        for name, v in (("solute_dielectric", solute_dielectric), ("solvent_dielectric", solvent_dielectric)):
+            if not (_is_number(v) and np.isfinite(v) and v > 0):
+                raise ValueError(f"MolecularMechanicsEnergy: {name} must be a positive number, got {v!r}")
+        if not (_is_number(surface_area_energy) and np.isfinite(surface_area_energy) and surface_area_energy >= 0):
+            raise ValueError(f"MolecularMechanicsEnergy: surface_area_energy must be a non-negative number, got {surface_area_energy!r}")
+        self.solute_dielectric, self.solvent_dielectric = float(solute_dielectric), float(solvent_dielectric)
+        self.surface_area_energy = float(surface_area_energy)
+        if self.has_solvent:
+            if len(implicit_solvent) != 3:
+                raise ValueError("MolecularMechanicsEnergy: implicit_solvent must be (charge, radius, scale)")
+            for name, v in zip(("charge", "radius", "scale"), implicit_solvent):
+                v = np.asarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float64).reshape(-1)
+                if len(v) != n_atoms:
+                    raise ValueError(f"MolecularMechanicsEnergy: implicit_solvent {name} has {len(v)} entries for {n_atoms} atoms")
+                for t in np.flatnonzero(~np.isfinite(v)):
+                    raise ValueError(f"MolecularMechanicsEnergy: implicit_solvent atom {int(t)} has a non-finite {name}")
+                self.register_buffer(f"solvent_{name}", torch.from_numpy(v.copy()))
+            for t in np.flatnonzero(~(self.solvent_radius.numpy() > GB_OFFSET)):
+                raise ValueError(f"MolecularMechanicsEnergy: implicit_solvent atom {int(t)} has radius <= {GB_OFFSET}")
+            for t in np.flatnonzero(~(self.solvent_scale.numpy() > 0)):
+                raise ValueError(f"MolecularMechanicsEnergy: implicit_solvent atom {int(t)} has scale <= 0")
 
     n_bonds = property(lambda self: len(self.bond_idx))
     n_angles = property(lambda self: len(self.angle_idx))
@@ -278,6 +321,10 @@ class MolecularMechanicsEnergy(Energy):
         out = {"n_atoms": np.array(self.n_atoms, np.int64), "unit_energy": np.array(self.unit_energy, np.float64),
                "has_nonbonded": np.array(int(self.has_nonbonded), np.int64)}
         out.update({name: buf.detach().cpu().numpy().copy() for name, buf in self.named_buffers()})
+        if self.has_solvent:                # (the three solvent arrays are buffers)
+            out.update(has_solvent=np.array(1, np.int64), solute_dielectric=np.array(self.solute_dielectric, np.float64),
+                       solvent_dielectric=np.array(self.solvent_dielectric, np.float64),
+                       surface_area_energy=np.array(self.surface_area_energy, np.float64))
         return out
 
     @classmethod
@@ -289,8 +336,12 @@ class MolecularMechanicsEnergy(Energy):
             return (a[f"{g}_idx"].astype(np.int64),) + tuple(a[f"{g}_{name}"] for name in ints + floats)
 
         nonbonded = tuple(a[f"nonbonded_{name}"] for name in ("charge", "sigma", "epsilon")) if int(a["has_nonbonded"]) else None
+        solvent = {}
+        if int(a.get("has_solvent", 0)):
+            solvent = dict(implicit_solvent=tuple(a[f"solvent_{name}"] for name in ("charge", "radius", "scale")),
+                           **{name: float(a[name]) for name in ("solute_dielectric", "solvent_dielectric", "surface_area_energy")})
         return cls(int(a["n_atoms"]), group("bond"), group("angle"), group("torsion"), nonbonded, group("exception"),
-                   unit_energy=float(a["unit_energy"]))
+                   unit_energy=float(a["unit_energy"]), **solvent)
 
     def save(self, path):
         with open(path, "wb") as f:
@@ -359,6 +410,31 @@ class MolecularMechanicsEnergy(Energy):
             host["packed"] = np.ascontiguousarray(words)
         return host["packed"]
 
+    def gb_prefactor(self):
+        """-138.935458 (1 / solute_dielectric - 1 / solvent_dielectric), in double"""
+        return -COULOMB * (1.0 / self.solute_dielectric - 1.0 / self.solvent_dielectric)
+
+    def _packed_solvent(self):
+        """the kernel's solvent table (csrc/bgk_solvent_terms.h), f32: [n, 4] (q_i, rho_i = r_i - 0.009, sigma_i = s_i rho_i, r_i), then [n]
+        sa_i = 4 pi surface_area_energy (r_i + 0.14)^2 r_i^6, padded to a multiple of four words; formed in double and rounded once"""
+        host = self._tables()[1]
+        if "solvent" not in host:
+            q, r, sc = (self._host(f"solvent_{name}") for name in ("charge", "radius", "scale"))
+            rho = r - GB_OFFSET
+            atoms = np.stack([q, rho, sc * rho, r], axis=1)
+            sa = 4.0 * np.pi * self.surface_area_energy * (r + GB_PROBE) ** 2 * r ** 6
+            words = np.concatenate([atoms.reshape(-1), sa, np.zeros(-len(sa) % 4)])
+            host["solvent"] = np.ascontiguousarray(words.astype(np.float32))
+        return host["solvent"]
+
+    def _device_solvent(self, device):
+        packed = self._packed_solvent()
+        cache = self._tables()[2]
+        key = ("solvent", str(device))
+        if key not in cache:
+            cache[key] = torch.from_numpy(packed).to(device)
+        return cache[key]
+
     def _device_tables(self, device):
         packed = self._packed_tables()
         cache = self._tables()[2]
@@ -386,6 +462,12 @@ class MolecularMechanicsEnergy(Energy):
                 live = (pairs[:, 0] != 0) | (pairs[:, 2] != 0)
                 t["pair_i"], t["pair_j"] = torch.from_numpy(i[live]).to(device), torch.from_numpy(j[live]).to(device)
                 t["pair_qq"], t["pair_sigma"], t["pair_eps4"] = (torch.from_numpy(pairs[live, c]).to(device=device, dtype=dtype) for c in range(3))
+            if self.has_solvent:
+                n = self.n_atoms
+                q, r, sc = (getattr(self, f"solvent_{name}").to(device=device, dtype=dtype) for name in ("charge", "radius", "scale"))
+                i, j = _pair_index(n)
+                t.update(gb_q=q, gb_r=r, gb_rho=r - GB_OFFSET, gb_sigma=sc * (r - GB_OFFSET), gb_i=torch.from_numpy(i).to(device),
+                         gb_j=torch.from_numpy(j).to(device), gb_eye=torch.eye(n, dtype=torch.bool, device=device))
             cache[key] = t
         return cache[key]
 
@@ -418,7 +500,35 @@ class MolecularMechanicsEnergy(Energy):
             s6 = (t["pair_sigma"] ** 2 / d2s) ** 3
             pair = t["pair_eps4"] * (s6 * s6 - s6) + t["pair_qq"] * d2s.rsqrt()
             e = e + torch.where(apart, pair, torch.full_like(pair, float("inf"))).sum(-1)
+        if self.has_solvent:
+            e = e + self._solvent_energy(p, t)
         return (e / self.unit_energy).reshape(*lead, 1)
+
+    def _solvent_energy(self, p, t):
+        """E_GB + E_SA [B] of the positions p [B, n, 3] (GBSAOBCForce's arithmetic, OBC2) in torch ops; +inf where two atoms coincide.  Every
+        branch is a ``torch.where`` over values formed from safe arguments, so no NaN reaches a gradient."""
+        eye = t["gb_eye"]
+        d2 = (p[:, :, None] - p[:, None, :]).pow(2).sum(-1)                   # [B, n, n]: atom i along dim 1, atom j along dim 2
+        apart = (d2 > 0) | eye
+        d2s = torch.where((d2 > 0) & ~eye, d2, torch.ones_like(d2))
+        r = d2s.sqrt()
+        rho, sigma = t["gb_rho"][:, None], t["gb_sigma"][None, :]
+        l = 1.0 / torch.maximum(rho.expand_as(r), (r - sigma).abs())
+        u = 1.0 / (r + sigma)
+        l2u2 = l * l - u * u
+        h = l - u - 0.25 * r * l2u2 + 0.5 * torch.log(u / l) / r + 0.25 * sigma ** 2 * l2u2 / r
+        h = h + torch.where(rho < sigma - r, 2.0 * (1.0 / rho - l), torch.zeros_like(h))
+        h = torch.where((rho >= r + sigma) | eye, torch.zeros_like(h), h)
+        psi = 0.5 * t["gb_rho"] * h.sum(-1)                                   # [B, n]
+        inv_b = 1.0 / t["gb_rho"] - torch.tanh(GB_ALPHA * psi - GB_BETA * psi ** 2 + GB_GAMMA * psi ** 3) / t["gb_r"]
+        born = 1.0 / inv_b
+        i, j = t["gb_i"], t["gb_j"]
+        r2, bb = d2s[:, i, j], born[:, i] * born[:, j]
+        f = (r2 + bb * torch.exp(-r2 / (4.0 * bb))).sqrt()
+        q = t["gb_q"]
+        e_gb = self.gb_prefactor() * ((q[i] * q[j] / f).sum(-1) + (0.5 * q * q * inv_b).sum(-1))
+        e_sa = (4.0 * np.pi * self.surface_area_energy * (t["gb_r"] + GB_PROBE) ** 2 * (t["gb_r"] * inv_b) ** 6).sum(-1)
+        return torch.where(apart.all(-1).all(-1), e_gb + e_sa, torch.full_like(e_gb, float("inf")))
 
     # ---- the kernel path ----
     def _molecule_kernel(self, temperature=1.0):

@@ -1035,6 +1035,27 @@ int bgk_molecule_energy_backward(const float* x, int64_t B, int32_t n_atoms, int
                                  const float* g_scalar, const float* u, const float* dlogp, int32_t drop_nonfinite,
                                  float* g_dlogp, float* g_x, void* stream);
 
+/* The same three entries with an implicit solvent added in the SAME launch, on the row tile staged once (the formulas:
+ * csrc/bgk_solvent_terms.h): Generalised Born (OBC2) plus the surface-area term, the arithmetic of OpenMM's GBSAOBCForce stated from its
+ * published form, over ALL pairs of atoms (no exclusions, no exceptions).  E = E_vacuum + E_GB + E_SA.
+ * `solvent`: one device buffer of floats, 16-byte aligned: [n_atoms][4] (q_i, rho_i = r_i - 0.009, sigma_i = s_i rho_i, r_i), then
+ *   [n_atoms] sa_i = 4 pi surface_area_energy (r_i + 0.14)^2 r_i^6; gb_prefactor = -138.935458 (1 / eps_solute - 1 / eps_solvent).
+ * ANY two atoms at distance 0 give u = +inf, and the solvent terms then add no gradient to the row.  The other arguments, the envelope
+ * and the statuses are those of the vacuum entries; BGK_EINVAL for a null or misaligned solvent table.  Rows per tile (64 / 32 / 16) follow
+ * from the LDS a row needs: n_atoms more floats in the forward, 3 n_atoms more in the backward. */
+int bgk_molecule_solvent_energy(const float* x, int64_t B, int32_t n_atoms, int32_t n_bonds, int32_t n_angles, int32_t n_torsions,
+                                int32_t n_pairs, const int32_t* tables, double unit_energy, double temperature, const float* solvent,
+                                double gb_prefactor, float* u, void* stream);
+int bgk_molecule_solvent_energy_kl_sums(const float* x, int64_t B, int32_t n_atoms, int32_t n_bonds, int32_t n_angles, int32_t n_torsions,
+                                        int32_t n_pairs, const int32_t* tables, double unit_energy, double temperature,
+                                        const float* solvent, double gb_prefactor, float* u, const float* dlogp, int32_t drop_nonfinite,
+                                        double* partial, int32_t nblk, double* loss_sums, void* stream);
+int bgk_molecule_solvent_energy_backward(const float* x, int64_t B, int32_t n_atoms, int32_t n_bonds, int32_t n_angles, int32_t n_torsions,
+                                         int32_t n_pairs, const int32_t* tables, double unit_energy, double temperature,
+                                         const float* solvent, double gb_prefactor, const float* g_u, const float* g_scalar,
+                                         const float* u, const float* dlogp, int32_t drop_nonfinite, float* g_dlogp, float* g_x,
+                                         void* stream);
+
 /* Column map of one [B, n_in] f32 field with contiguous rows into a [B, n_out] one, in one launch: output column j is a function of
  * at most one input column, given by table[j] = (int32 kind, int32 src, float p0, float p1) (device memory, 16 bytes per entry):
  *   0 COPY        in[src]                           index SplitFlow / MergeFlow (nn/flow/coupling.py:13-110)
